@@ -6,7 +6,9 @@ above 2^60 (goodQs rule, ZqBasic.hs:71-73), batch = 4096 polynomials per GPU,
 operands and results in the powerful basis, resident in HBM.  One step = one fused
 poly-mul launch over the whole batch (c = crtInv(crt a * crt b)).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+--dump-outputs writes what the last timed step computed to DIR/*.npy (dump_outputs below); the
+operands come from a seeded generator, so the same arguments give the same inputs on every run.
 N > 1 runs one rank per GPU.  Either the caller starts the ranks (torch.distributed.run sets
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; WORLD_SIZE must then equal --gpus), or — plain
 `python bench.py --gpus N` with no WORLD_SIZE in the environment — this process starts N fresh
@@ -355,6 +357,23 @@ def timed_steps(step, steps, dist, sync, device, before=None, after=None):
     return elapsed
 
 
+DUMP_POLYS = 256          # 256 polys x 8192 coefficients x 2 float64 halves = 32 MiB
+
+
+def dump_outputs(out_dir, c):
+    """--dump-outputs: the result slab the timed step hands its caller, c [B, n, T] int64 residues in [0, q),
+    q < 2^61.  A fixed sample of min(B, DUMP_POLYS) polynomials (rows chosen by a seeded generator, the same for
+    every run with the same --batch), each residue split exactly into float64 halves v = hi * 2^32 + lo."""
+    import numpy as np
+    import torch
+    B = c.shape[0]
+    idx = np.sort(np.random.default_rng(0).choice(B, size=min(B, DUMP_POLYS), replace=False))
+    v = c.index_select(0, torch.as_tensor(idx, device=c.device)).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "polymul_hi32.npy"), (v >> 32).astype(np.float64))
+    np.save(os.path.join(out_dir, "polymul_lo32.npy"), (v & 0xFFFFFFFF).astype(np.float64))
+
+
 def launcher_selftest(args, rank, world):
     """CPU-only: the rank start-up, rendezvous, barrier/MAX timing and rank-0 reporting of the N > 1
     path on gloo, with a step that launches nothing.  tests/test_dist.py runs it at N = 2."""
@@ -440,9 +459,14 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU-only check of the rank launcher and the rendezvous/timing protocol (gloo, no kernel): "
                          "prints a line whose metric says so; never a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's poly-mul results of the last step to DIR/*.npy "
+                         "(a fixed sample of polynomials, float64 hi/lo 32-bit halves; see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(sys.argv[1:], args.gpus))
@@ -505,6 +529,8 @@ def main():
     elapsed = timed_steps(step, args.steps, dist, torch.cuda.synchronize, "cuda",
                           before=lambda: ev0.record(stream), after=lambda: ev1.record(stream))
     kern_ms = ev0.elapsed_time(ev1) / max(1, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, c)            # before secondary(), which reuses c
 
     # ---- N > 1: the one optional collective, all-gather of the result shards ----
     gather = None

@@ -21,17 +21,6 @@ def cpuref():
 
 
 @pytest.fixture(scope="session")
-def ctref():
-    """The reference's own lol-cpp C++ (oracle/_ref), when it has been built."""
-    from oracle.oracle import CTRef, CTREF_SO, build
-    if not os.path.exists(CTREF_SO) and os.path.isdir("/root/reference"):
-        build(ref=True)
-    if not os.path.exists(CTREF_SO):
-        pytest.skip("oracle/_ref/libctensor.so not built (no /root/reference here)")
-    return CTRef()
-
-
-@pytest.fixture(scope="session")
 def golden():
     path = os.path.join(ROOT, "tests", "golden", "golden_ct.npz")
     z = np.load(path, allow_pickle=False)

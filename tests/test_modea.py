@@ -1,24 +1,26 @@
-"""Mode A of INTEGRATION.md, proved once at link level (a `not gpu` test; needs /root/reference and binutils):
-lol-cpp's own sources, partially linked with the nine Z_q symbols localised (haskell/lol-hip/modeA/Makefile), plus
+"""Mode A of INTEGRATION.md, proved once at link level (a `not gpu` test; needs binutils and oracle/_ref/modea):
+lol-cpp's own sources, partially linked with the nine Z_q symbols localised (haskell/lol-hip/modeA/Makefile, run by
+build() through oracle/Makefile where the reference tree is present), plus
 liblolhip.so satisfy all 29 imports of lol-cpp/Crypto/Lol/Cyclotomic/Tensor/CPP/Backend.hs:304-337 — the Z_q ones
 from liblolhip, the other twenty from lol-cpp — with no duplicate definition."""
 import os
+import pathlib
 import shutil
 import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/lol-cpp"
+MODEA = os.path.join(ROOT, "oracle", "_ref", "modea")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not on this machine")
+@pytest.mark.skipif(not os.path.exists(os.path.join(MODEA, "liblolcpp_rest.a")),
+                    reason="oracle/_ref/modea not built (build() found no reference tree)")
 def test_mode_a_links_and_splits_the_29_symbols(tmp_path, lolhip):
     for tool in ("ld", "objcopy", "ar", "g++", "gcc"):
         if shutil.which(tool) is None:
             pytest.skip(f"{tool} not installed")
-    out = tmp_path / "modea"
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "haskell", "lol-hip", "modeA"), f"LOLCPP={REF}", f"OUT={out}"], check=True)
+    out = pathlib.Path(MODEA)
     # the partially linked object still CONTAINS the nine Z_q symbols, but as local ones
     nm = subprocess.run(["nm", str(out / "lolcpp_rest.o")], capture_output=True, text=True, check=True).stdout
     kinds = {ln.split()[-1]: ln.split()[-2] for ln in nm.splitlines() if len(ln.split()) >= 2}

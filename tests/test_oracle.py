@@ -1,9 +1,11 @@
 """CPU tests of the ORACLE itself (no GPU): the C restatement oracle/cpu_ref.c is pinned
  (a) against the committed golden vectors, which are outputs of the reference's own C++,
- (b) against the reference's C++ live, when oracle/_ref is present,
+ (b) against the reference's C++ on seeded inputs (tests/golden/golden_live.npz),
  (c) against the closed-form definition incl. 61-bit moduli,
  (d) through the reference's property list (lol/Crypto/Lol/Tests/TensorTests.hs:38-78,133-234).
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -78,27 +80,32 @@ def test_twace_embed_restatement_matches_golden(cpuref, golden, i):
     assert np.array_equal(cpuref.embed_dec(Pl, Ph, lo), _i64(golden[f"t2_{i}/embed_dec"]))
 
 
-def test_restatement_matches_reference_live(cpuref, ctref):
-    """Fresh random inputs through the reference's own C++ (only where oracle/_ref exists)."""
-    rng = np.random.default_rng(11)
-    for m, qs in TENSOR1 + [(45, [1171, 1531]), (1155, [1051051]), (432, [1297]), (2048, [12289])]:
+@pytest.fixture(scope="module")
+def live():
+    """The reference's own C++ on seeded inputs, stored by tests/golden/make_golden_live.py."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_live.npz"), allow_pickle=False)
+    return {k: z[k] for k in z.files}
+
+
+def test_restatement_matches_reference_live(cpuref, live):
+    """Seeded random inputs against the reference's own C++ answers (tests/golden/golden_live.npz)."""
+    for k, (m, qs) in enumerate(TENSOR1 + [(45, [1171, 1531]), (1155, [1051051]), (432, [1297]), (2048, [12289])]):
         P = Params(lm.factor_pps(m), qs)
-        y, z = P.random(rng, 2), P.random(rng, 2)
+        y, z = live[f"zq/{k}/y"], live[f"zq/{k}/z"]
         for op in ("crt", "crtinv") + PRIME_OPS:
-            a, b = getattr(cpuref, op)(P, y), getattr(ctref, op)(P, y)
+            a, b = getattr(cpuref, op)(P, y), live.get(f"zq/{k}/{op}")
             assert (a is None) == (b is None), (op, m)
             if a is not None:
                 assert np.array_equal(a.reshape(b.shape), b), (op, m, qs)
-        assert np.array_equal(cpuref.mul(P, y, z).reshape(2, P.n, P.T), ctref.mul(P, y, z))
+        assert np.array_equal(cpuref.mul(P, y, z).reshape(2, P.n, P.T), live[f"zq/{k}/mul"])
 
 
-def test_negative_inputs_like_reference(cpuref, ctref):
+def test_negative_inputs_like_reference(cpuref, live):
     """The C side accepts representatives in (-q, q) (types.h:52-57) and returns [0, q)."""
-    rng = np.random.default_rng(12)
     P = Params(lm.factor_pps(21), [8191])
-    y = P.random(rng, 1) - 8191 // 2
+    y = live["neg/y"]
     for op in ("crt", "crtinv", "l", "linv", "gpow", "gdec", "ginvpow", "ginvdec"):
-        a, b = getattr(cpuref, op)(P, y), getattr(ctref, op)(P, y)
+        a, b = getattr(cpuref, op)(P, y), live[f"neg/{op}"]
         assert np.array_equal(a.reshape(b.shape), b), op
         assert a.min() >= 0 and a.max() < 8191
 
