@@ -113,7 +113,10 @@ LOLHIP_API int lolhip_plan_has_crt(const lolhip_plan *p);
  *          3 gCRT  4 gInvCRT (CPP.hs:444-454; [n*T] AoS)            5 qs
  *          10 / 11 (inspection, tests): the stage program a lone crt / crtInv of an index that is not a power
  *          of two launches, four values per stage: kind, prime (first level for the 2-power tiles), vector
- *          length (levels for the tiles), stride                                  */
+ *          length (levels for the tiles), stride
+ *          12 (inspection, tests): the lift constants of errorTerm / decrypt, [T + T*T + T]: (q_0 ... q_{i-1})^-1
+ *          mod q_i (1 for i = 0); q_j mod q_i at [T + i*T + j]; the mixed-radix digits of floor((Q-1)/2),
+ *          Q = prod q_t, least significant first                                  */
 LOLHIP_API int64_t lolhip_plan_table(const lolhip_plan *p, int which, int k, int64_t *out, int64_t len);
 
 /* smallest prime > lower congruent to 1 mod m (head of goodQs, ZqBasic.hs:71-73) */
@@ -246,6 +249,33 @@ LOLHIP_API int lolhip_keyswitch_batch(const lolhip_plan *p, void *stream, const 
  * c [B][n][T] -> out [B][n][T-1].  LOLHIP_ERR_MODULUS if q_0 is not invertible mod some q_s. */
 LOLHIP_API int lolhip_rescale_drop_batch(const lolhip_plan *p, void *stream, const int64_t *c, int64_t *out,
                                          int64_t B);
+
+/* errorTerm / decrypt (lol-apps SymmSHE.hs:153-178; decryptUnrestricted :200-208).
+ * cs: ncs ciphertext components c_0..c_{ncs-1}, [ncs][B][n'][T], powerful basis (cs_crt = 0) or
+ *     CRT basis (cs_crt = 1), over pq (index m', moduli q_0..q_{T-1}, CRT basis required).
+ * s_crt: the secret key reduced into pq, CRT basis, [n'][T], shared by the whole batch.
+ * enc: 0 = LSD, 1 = MSD (toLSD first, SymmSHE.hs:214-230; msdToLSD, Prelude.hs:139-140,311-315).
+ * p: the plaintext modulus.
+ * lolhip_error_term_batch: e_dec [B][n'] int64 = liftCyc Dec (evaluate c s) after toLSD, the centred lift mod
+ *   Q = prod q_t of every decoding-basis coefficient ([-(Q-1)/2, (Q-1)/2] for odd Q); a lift that does not fit
+ *   int64 is written as INT64_MIN (no status, no synchronisation).
+ * lolhip_decrypt_batch: pt_pow [B][n_m] residues in [0, p), powerful basis of R_m, = l' twace (divG^k (reduce_p e))
+ *   with e the error term (divGDec, then twacePowDec): l' = l for LSD, l (-Q)^-1 mod p for MSD.  pp: the plan of
+ *   index m' over the single modulus p (any p >= 2, no CRT basis needed); x_p: an extension from the plan of
+ *   (m, p) to pp, or NULL for m = m'.
+ * Status: LOLHIP_ERR_INVALID for ncs < 1, pp not of index m' or not of one modulus, x_p not ending in pp's ring
+ *   and modulus, T > 16; LOLHIP_ERR_NO_CRT when pq has no CRT basis; LOLHIP_ERR_MODULUS for MSD with gcd(Q, p) != 1
+ *   (or moduli of pq that are not pairwise coprime); LOLHIP_ERR_NOT_DIVISIBLE for k > 0 when divGDec is impossible
+ *   mod p.  Every one of these is decided on the host before any launch: e_dec / pt_pow are then not written.
+ * work: caller-provided device scratch of lolhip_decrypt_work_len(pq, ncs, B) int64 (re-entrant calls); cs and
+ *   s_crt are only read. */
+LOLHIP_API int64_t lolhip_decrypt_work_len(const lolhip_plan *pq, int ncs, int64_t B);
+LOLHIP_API int lolhip_error_term_batch(const lolhip_plan *pq, void *stream, const int64_t *cs, int ncs,
+                                       int cs_crt, const int64_t *s_crt, int enc, int64_t p, int64_t *e_dec,
+                                       int64_t *work, int64_t B);
+LOLHIP_API int lolhip_decrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp, const lolhip_ext *x_p,
+                                    void *stream, const int64_t *cs, int ncs, int cs_crt, const int64_t *s_crt, int enc,
+                                    int64_t k, int64_t l, int64_t *pt_pow, int64_t *work, int64_t B);
 
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "capi_internal.h"
 #include "kernels.h"
 #include "pipeline.h"
 #include "lolhip.h"
@@ -42,9 +43,6 @@ bool sw(Switch which) {
   return g_switch[which].load(std::memory_order_relaxed) != 0;
 }
 }  // namespace lolhip
-
-struct lolhip_plan { Plan P; };
-struct lolhip_ext { ExtPlan X; };
 
 namespace {
 
@@ -260,6 +258,10 @@ int64_t lolhip_plan_table(const lolhip_plan* p, int which, int k, int64_t* out, 
       src = &tmp;
       break;
     }
+    case 12:                 // the lift constants of errorTerm / decrypt (plan.h lift_consts), [T + T*T + T]
+      tmp.assign(P.lift_consts.begin(), P.lift_consts.end());
+      src = &tmp;
+      break;
     default: break;
   }
   if (!src) return 0;
@@ -1018,3 +1020,13 @@ int16_t tensorGInvDecRq(int16_t T, int64_t* y, int64_t totm, lolhip_pp* pe, int1
 }
 
 }  // extern "C"
+
+// ---- for the other host translation units of the C ABI (capi_internal.h) -----------------
+namespace lolhip {
+int capi_need_device(const lolhip_plan* p) { return need_device(p); }
+int capi_run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
+  return run_prog(P, sp, s, y, B, src);
+}
+int capi_do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse) { return do_crt(P, s, y, B, inverse); }
+int capi_divg_ok(const Plan& P) { return divg_ok(P); }
+}  // namespace lolhip

@@ -22,6 +22,17 @@ struct RescaleParams {
   u64 qa_inv[PIPE_MAX_T];      // q_0^-1 mod q_s, s >= 1
 };
 
+// p-dependent constants of decrypt.hip k_lift (the p-independent ones are the plan's lift_consts)
+struct LiftParams {
+  int T;                       // components
+  int msd;                     // 1: scale every residue by scale[t] first (toLSD of an MSD ciphertext)
+  u64 scale[PIPE_MAX_T];       // p mod q_t
+  ModCtx mp;                   // p mode: the plaintext modulus (any p >= 2: generic division, no Montgomery form)
+  u64 pw[PIPE_MAX_T];          // (q_0 ... q_(i-1)) mod p
+  u64 qp;                      // Q mod p
+  u64 lp;                      // l' mod p
+};
+
 hipError_t launch_ctmul(hipStream_t s, const i64* c0, const i64* c1, const i64* d0, const i64* d1, i64* e0, i64* e1,
                         i64* e2, const i64* gcrt, i64 B, i64 n, int T, const ModCtx* mod);
 hipError_t launch_decompose(hipStream_t s, const i64* c, i64* digits, i64 B, i64 n, const DecompParams& p,
@@ -34,5 +45,14 @@ hipError_t launch_rescale(hipStream_t s, const i64* c, i64* out, i64 B, i64 n, c
 // coeffs (Extension.hs:90-93): out[i1][b][i0][t] = in[b][idx[i1*n_lo + i0]][t]
 hipError_t launch_coeffs(hipStream_t s, i64* out, const i64* in, const int32_t* idx, i64 B, i64 n_lo, i64 n_hi, int T,
                          const ModCtx* mod);
+
+// decrypt.hip: errorTerm / decrypt (lol-apps SymmSHE.hs:153-178)
+// out = (sum_k comps_k s^k) (* s when times_s), CRT basis; comps_k = comps + k * B*n*T; out may alias comps
+hipError_t launch_sk_eval(hipStream_t s, const i64* comps, int ncomp, bool times_s, const i64* s_crt, i64* out, i64 B,
+                          i64 n, int T, const ModCtx* mod);
+hipError_t launch_addmod(hipStream_t s, i64* y, const i64* a, i64 B, i64 n, int T, const ModCtx* mod);
+// rows = B * n coefficients [rows][T] (+ add, may be null) -> [rows] int64: p mode (pmode) or the centred lift
+hipError_t launch_lift(hipStream_t s, const i64* in, const i64* add, i64* out, i64 rows, const LiftParams& p, bool pmode,
+                       const u64* lift_consts, const ModCtx* mod);
 
 }  // namespace lolhip

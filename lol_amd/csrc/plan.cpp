@@ -396,6 +396,29 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
   P.oddrad_inv.assign((size_t)T, 0);
   for (int t = 0; t < T; ++t) P.oddrad_inv[(size_t)t] = invmod(odd_rad(pps) % qs[(size_t)t], qs[(size_t)t]);
 
+  // ---- lift constants (Garner / mixed radix) ---------------------------------
+  P.lift_consts.assign((size_t)(T + T * T + T), 0);
+  P.lift_ok = true;
+  for (int i = 0; i < T; ++i) {
+    const u64 qi = qs[(size_t)i];
+    u64 prefix = 1 % qi;                                   // q_0 ... q_(i-1) mod q_i
+    for (int j = 0; j < T; ++j) {
+      P.lift_consts[(size_t)(T + i * T + j)] = qs[(size_t)j] % qi;
+      if (j < i) prefix = mulmod(prefix, qs[(size_t)j] % qi, qi);
+    }
+    const u64 inv = i == 0 ? 1 % qi : invmod(prefix, qi);
+    if (inv == 0 && qi > 1) P.lift_ok = false;
+    P.lift_consts[(size_t)i] = inv;
+  }
+  {  // Q - 1 has the digits q_i - 1; halve it most significant digit first
+    u64 carry = 0;
+    for (int i = T - 1; i >= 0; --i) {
+      const u128 cur = (u128)carry * qs[(size_t)i] + (qs[(size_t)i] - 1);
+      P.lift_consts[(size_t)(T + T * T + i)] = (u64)(cur >> 1);
+      carry = (u64)(cur & 1);
+    }
+  }
+
   // ---- generic stage programs + constant pool ---------------------------------
   auto magic40 = [](i64 v) -> uint64_t { return (uint64_t)(((unsigned __int128)1 << 40) / (uint64_t)(v > 0 ? v : 1)) + 1; };
   // class 3 of the vector interpreter (as plan_upload decides it): the dense stages of odd primes take the
@@ -660,6 +683,7 @@ int plan_upload(Plan& P) {
   if ((rc = upload(&P.d_rconsts, P.host_rconsts))) return rc;
   if ((rc = upload(&P.d_gcrt, P.gcrt))) return rc;
   if ((rc = upload(&P.d_ginvcrt, P.ginvcrt))) return rc;
+  if ((rc = upload(&P.d_lift, P.lift_consts))) return rc;
 
   if (P.is_pow2 || P.pow2_part) {
     const int L = P.pow2.L;
@@ -778,7 +802,7 @@ int plan_upload(Plan& P) {
 
 void plan_free_device(Plan& P) {
   auto fr = [](void* p) { if (p) (void)hipFree(p); };
-  fr(P.d_mod); fr(P.d_consts); fr(P.d_consts_mont); fr(P.d_consts32); P.d_consts32 = nullptr; fr(P.d_gcrt); fr(P.d_ginvcrt); fr(P.d_cconsts); fr(P.d_rconsts);
+  fr(P.d_mod); fr(P.d_lift); P.d_lift = nullptr; fr(P.d_consts); fr(P.d_consts_mont); fr(P.d_consts32); P.d_consts32 = nullptr; fr(P.d_gcrt); fr(P.d_ginvcrt); fr(P.d_cconsts); fr(P.d_rconsts);
   P.d_cconsts = nullptr; P.d_rconsts = nullptr; P.d_consts_mont = nullptr;
   fr(P.pow2.d_tw_fwd); fr(P.pow2.d_tw_inv); fr(P.pow2.d_scale);
   fr(P.pow2.d_tw_fwd32); fr(P.pow2.d_tw_inv32); fr(P.pow2.d_scale32);

@@ -91,6 +91,13 @@ struct Plan {
   std::vector<u64> oddrad_inv;              // [T], 0 when not invertible
   bool has_ginvcrt = false;                 // every odd p | m invertible mod every q_t
   std::vector<u64> host_consts;             // [T][consts_per_comp] generic-path constant pool
+  // lift from Z_q0 x ... x Z_q(T-1) to the integers (decrypt.hip k_lift, mixed-radix / Garner form), [T + T*T + T]:
+  //   pinv[i]        (q_0 ... q_(i-1))^-1 mod q_i            (1 for i = 0)
+  //   qmod[i*T + j]  q_j mod q_i
+  //   half[i]        digit i of floor((Q-1)/2) in the mixed radix (q_0, q_1, ...), Q = prod q_t
+  // lift_ok: the moduli are pairwise coprime (every pinv exists)
+  std::vector<u64> lift_consts;
+  bool lift_ok = false;
 
   // device tables
   ModCtx* d_mod = nullptr;                  // [T]
@@ -118,6 +125,7 @@ struct Plan {
   // transforms and the fused poly-mul take them, the fused key switch at <= 12 coefficients per thread.
   StageProgram prog_crt_mg, prog_crtinv_mg, prog_crt_mg_big, prog_crtinv_mg_big, prog_crt_fused_big, prog_crtinv_fused_big;
   i64* d_gcrt = nullptr;                    // [n*T]
+  u64* d_lift = nullptr;                    // lift_consts
   i64* d_ginvcrt = nullptr;                 // [n*T]
   Pow2Tables pow2;
   bool is_pow2 = false;

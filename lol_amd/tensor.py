@@ -103,6 +103,10 @@ def lib():
     L.lolhip_knapsack_batch.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, i64]
     L.lolhip_keyswitch_batch.argtypes = [vp, vp, vp, i64, vp, ci, vp, vp, vp, i64]
     L.lolhip_rescale_drop_batch.argtypes = [vp, vp, vp, vp, i64]
+    L.lolhip_decrypt_work_len.argtypes = [vp, ci, i64]
+    L.lolhip_decrypt_work_len.restype = i64
+    L.lolhip_error_term_batch.argtypes = [vp, vp, vp, ci, ci, vp, ci, i64, vp, vp, i64]
+    L.lolhip_decrypt_batch.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, i64, i64, vp, vp, i64]
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
     L.lolhip_ext_destroy.argtypes = [vp]
     L.lolhip_ext_destroy.restype = None
@@ -460,6 +464,12 @@ class Plan:
     def gCRT(self): return self._table(3).reshape(self.n, self.T)
     def gInvCRT(self): return self._table(4).reshape(self.n, self.T)
 
+    def liftConsts(self):
+        """Constants of the lift to the integers (errorTerm / decrypt): dict of `pinv` [T] ((q_0...q_(i-1))^-1 mod q_i),
+        `qmod` [T][T] (qmod[i][j] = q_j mod q_i) and `half` [T] (mixed-radix digits of floor((Q-1)/2))."""
+        t, T = self._table(12), self.T
+        return {"pinv": t[:T], "qmod": t[T:T + T * T].reshape(T, T), "half": t[T + T * T:]}
+
     def program(self, inverse=False):
         """Stage program of a lone crt / crtInv (inspection): rows (kind, prime or first level, length or levels, stride)."""
         return self._table(11 if inverse else 10).reshape(-1, 4)
@@ -636,6 +646,60 @@ class Plan:
         B = self._batch_t(c)
         out = torch.empty((B, self.n, self.T - 1), dtype=torch.int64, device=c.device)
         _check(lib().lolhip_rescale_drop_batch(self._h, _stream(stream), _devptr(c), _devptr(out), B))
+        return self._unstage(host, out)
+
+    # ---- errorTerm / decrypt (lol-apps SymmSHE.hs:153-178) ------------------------------
+    def _ct_args(self, cs, s_crt):
+        """(host?, stacked cs [ncs][B][n][T] and s_crt [n][T] as device tensors, ncs, B); numpy stays on the host side
+        until _stage, so the host checks of the library run first"""
+        import torch
+        if isinstance(cs, (list, tuple)):
+            host = isinstance(cs[0], np.ndarray)
+            cs = np.stack([np.asarray(c, dtype=np.int64) for c in cs]) if host else torch.stack(list(cs))
+        else:
+            host = isinstance(cs, np.ndarray)
+        ncs = int(cs.shape[0])
+        B = (cs.size if host else cs.numel()) // max(ncs * self.n * self.T, 1)
+        if ncs * B * self.n * self.T != (cs.size if host else cs.numel()):
+            raise ValueError("cs is not [ncs][B][n][T]")
+        return host, cs, s_crt, ncs, B
+
+    @staticmethod
+    def _enc(enc):
+        return {"LSD": 0, "MSD": 1, 0: 0, 1: 1}[enc]
+
+    def errorTerm(self, cs, s_crt, p, enc="LSD", cs_crt=False, stream=None):
+        """liftCyc Dec (evaluate c s) after toLSD (SymmSHE.hs:153-157): ciphertext components cs (a list of [B][n][T]
+        or one [ncs][B][n][T] array; powerful basis, or CRT basis with cs_crt), secret key s_crt [n][T] in the CRT
+        basis -> [B][n] int64 centred lifts mod Q (INT64_MIN where the lift does not fit)."""
+        import torch
+        L = lib()
+        host, cs, s_crt, ncs, B = self._ct_args(cs, s_crt)
+        e = self._enc(enc)
+        _check(L.lolhip_error_term_batch(self._h, None, None, ncs, int(cs_crt), None, e, int(p), None, None, 0))
+        host, (cs, s_crt) = self._stage(cs, s_crt) if host else (False, (cs, s_crt))
+        work = torch.empty((max(L.lolhip_decrypt_work_len(self._h, ncs, B), 1),), dtype=torch.int64, device=cs.device)
+        out = torch.empty((B, self.n), dtype=torch.int64, device=cs.device)
+        _check(L.lolhip_error_term_batch(self._h, _stream(stream), _devptr(cs), ncs, int(cs_crt), _devptr(s_crt), e, int(p),
+                                         _devptr(out), _devptr(work), B))
+        return self._unstage(host, out)
+
+    def decrypt(self, cs, s_crt, pp, ext=None, enc="LSD", k=0, l=1, cs_crt=False, stream=None):
+        """SymmSHE decrypt (SymmSHE.hs:169-174): l' twace (divG^k (reduce_p (errorTerm))).  pp: the Plan of index m' over
+        the plaintext modulus p alone; ext: an Ext from the Plan of (m, p) to pp, or None for m = m'.  Returns [B][n_m]
+        residues mod p in the powerful basis of R_m."""
+        import torch
+        L = lib()
+        host, cs, s_crt, ncs, B = self._ct_args(cs, s_crt)
+        e, xh = self._enc(enc), (None if ext is None else ext._h)
+        args = (int(k), int(l))
+        _check(L.lolhip_decrypt_batch(self._h, pp._h, xh, None, None, ncs, int(cs_crt), None, e, *args, None, None, 0))
+        host, (cs, s_crt) = self._stage(cs, s_crt) if host else (False, (cs, s_crt))
+        n_out = pp.n if ext is None else ext.lo.n
+        work = torch.empty((max(L.lolhip_decrypt_work_len(self._h, ncs, B), 1),), dtype=torch.int64, device=cs.device)
+        out = torch.empty((B, n_out), dtype=torch.int64, device=cs.device)
+        _check(L.lolhip_decrypt_batch(self._h, pp._h, xh, _stream(stream), _devptr(cs), ncs, int(cs_crt), _devptr(s_crt), e,
+                                      *args, _devptr(out), _devptr(work), B))
         return self._unstage(host, out)
 
 

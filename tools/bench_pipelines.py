@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/bench_pipelines.py — throughput of the SymmSHE pipeline kernels on one MI355X
-(BASELINE configs 3 and 5 shapes).  Operands resident in HBM, HIP events on
+(BASELINE configs 3 and 5 shapes) and of decrypt (`--decrypt`: that leg alone).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -44,8 +44,43 @@ def good_qs(m, lower, T):
     return out
 
 
+def decrypt_leg(gen):
+    """SymmSHE errorTerm / decrypt (lolhip_error_term_batch / lolhip_decrypt_batch).  alg_bytes: the ncs component
+    slabs read once and the [B][n_m] output written once (the key, shared by the batch, is not counted)."""
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    # (label, m, m', moduli, p, B, ncs, k): config 3's product; the reference's decBenches shape (Default.hs:43-44)
+    for label, m, m2, qs, p, B, ncs, k in (("m'=2^15 T=4 59-bit", 2 ** 15, 2 ** 15, good_qs(2 ** 15, 2 ** 59, 4), 65537, 256, 3, 1),
+                                           ("m=16 in m'=2048 q=1017857", 16, 2048, [1017857], 16, 8192, 2, 0)):
+        pq = lol_amd.Plan.for_index(m2, qs)
+        pp = lol_amd.Plan.for_index(m2, [p])
+        x_p = None if m == m2 else lol_amd.Ext(lol_amd.Plan.for_index(m, [p]), pp)
+        n_out = pp.n if x_p is None else x_p.lo.n
+        cs = torch.stack([rnd(gen, qs, B, pq.n) for _ in range(ncs)])
+        s_crt = rnd(gen, qs, pq.n)
+        work = torch.empty((L.lolhip_decrypt_work_len(pq._h, ncs, B),), dtype=torch.int64, device="cuda")
+        out = torch.empty((B, n_out), dtype=torch.int64, device="cuda")
+        e_out = torch.empty((B, pq.n), dtype=torch.int64, device="cuda")
+        slab = B * pq.n * pq.T * 8
+        xh = None if x_p is None else x_p._h
+        cfg = f"{label} B={B} ncs={ncs} k={k} p={p}"
+        for cs_crt in (0, 1):
+            rc = L.lolhip_decrypt_batch(pq._h, pp._h, xh, st, ptr(cs), ncs, cs_crt, ptr(s_crt), 0, k, 1, ptr(out), ptr(work), B)
+            assert rc == 0, rc
+            ms = timeit(lambda: L.lolhip_decrypt_batch(pq._h, pp._h, xh, st, ptr(cs), ncs, cs_crt, ptr(s_crt), 0, k, 1, ptr(out),
+                                                       ptr(work), B))
+            report("decrypt" + ("_crt_in" if cs_crt else ""), cfg, ms, B, ncs * slab + B * n_out * 8)
+        ms = timeit(lambda: L.lolhip_error_term_batch(pq._h, st, ptr(cs), ncs, 0, ptr(s_crt), 0, p, ptr(e_out), ptr(work), B))
+        report("errorTerm", cfg, ms, B, ncs * slab + B * pq.n * 8)
+        del cs, work, out, e_out
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--decrypt" in sys.argv:          # the decrypt leg alone
+        decrypt_leg(gen)
+        return
     L = lol_amd.lib()
     st = torch.cuda.current_stream().cuda_stream
     # ---- config 3: ciphertext product, m = 2^15, T = 4, ~59-bit moduli ------------------
@@ -105,6 +140,7 @@ def main():
     report("rescale_drop", f"m=2^15 T=4->3 B={B}", ms, B, B * P.n * 7 * 8)
 
     streaming(gen)
+    decrypt_leg(gen)
 
 
 def streaming(gen):
