@@ -277,6 +277,43 @@ LOLHIP_API int lolhip_decrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp
                                     void *stream, const int64_t *cs, int ncs, int cs_crt, const int64_t *s_crt, int enc,
                                     int64_t k, int64_t l, int64_t *pt_pow, int64_t *work, int64_t B);
 
+/* encrypt / genSK (lol-apps SymmSHE.hs:120-146): samplers over the ChaCha20 stream cipher (RFC 8439 §2.3 block function,
+ * counter mode), so every sample is a pure function of (key, position) and does not depend on launch shape, stream or how
+ * a batch is split.  Stream layout: batch item b of a call with offset ctr uses the nonce (domain, lo32(ctr + b),
+ * hi32(ctr + b)) and block counters from 0; domain 0 = the Gaussians of encrypt, 1 = the uniform c1, 2 = errorRounded.
+ *   Gaussian coefficient j (decoding basis): pair i = j >> 1 from block i >> 2, words w[4(i&3) .. 4(i&3)+3];
+ *     a = w0 | w1 << 32, c = w2 | w3 << 32, u1 = ((a >> 11) + 1) 2^-53, u2 = (c >> 11) 2^-53, r = sigma sqrt(-2 ln u1),
+ *     g_2i = r cos(2 pi u2), g_2i+1 = r sin(2 pi u2) (basic Box-Muller); for an index that is not a power of two the
+ *     map of lolhip_gaussian_dec_batch follows.  sigma = sqrt(v (m'/rad m') / (2 pi)) (tGaussianDec v: scaled
+ *     variance), v = svar * (p * p) (in double) for encrypt and svar for errorRounded.
+ *   Uniform CRT-basis residue [j][t]: r = j*T + t from block r >> 2, (w0 + 2^32 w1 + 2^64 w2 + 2^96 w3) mod q_t.
+ * THE CALLER'S DUTY: never use the same (key, ctr + b) twice for one domain: after a call with batch B, advance ctr by B
+ * (a repeated nonce repeats the noise and c1, which gives the secret key away).
+ * lolhip_encrypt_batch: cs_out [2][B][n'][T] = (c0, c1) of CT LSD 0 1 [reduce e - c1 s, c1] over pq (index m', CRT
+ *   basis required), in the CRT basis (out_crt = 1) or the powerful basis; the two are the same integers up to crtInv.
+ *   e = errorCoset (svar) (embed pt): rep_j + p round((g_j - rep_j) / p) per decoding-basis coefficient (half to even),
+ *   rep_j the centred ([-p/2, p/2)) decoding-basis coefficient of embed pt mod p.  pt_pow [B][n_m] in (-p, p), powerful
+ *   basis of R_m; pp: the plan of index m' over p alone; x_p: an extension from the plan of (m, p) to pp, or NULL for
+ *   m = m'.  s_crt [n'][T]: the secret key reduced into pq, CRT basis, shared by the batch.  work:
+ *   lolhip_encrypt_work_len(pq, B) int64 of device scratch.
+ * lolhip_error_rounded_batch: z_dec [B][n'] = errorRounded svar (genSK's key, SymmSHE.hs:120-122; UCyc.hs:422-429), the
+ *   decoding-basis coefficients rounded half to even; the plan supplies the index only.  work is not used (the sampler
+ *   runs in place in z_dec) and may be NULL.
+ * Limits: T <= 16; n' <= 16384 for m' = 2^k; otherwise the limits of lolhip_gaussian_dec_batch (n' <= 8192, primes
+ *   <= 13).
+ * Status: LOLHIP_ERR_INVALID for svar <= 0 or not finite, B < 0, pp not of index m' or not of one modulus, x_p not
+ *   ending in pp's ring and modulus, T > 16, an index beyond the limits; LOLHIP_ERR_NO_CRT when pq has no CRT basis;
+ *   LOLHIP_ERR_MODULUS for p < 2; LOLHIP_ERR_NO_DEVICE on a host-only plan.  Every one is decided on the host before
+ *   any launch: the output is then not written.  No call synchronises or allocates. */
+LOLHIP_API int64_t lolhip_encrypt_work_len(const lolhip_plan *pq, int64_t B);
+LOLHIP_API int lolhip_encrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp, const lolhip_ext *x_p, void *stream,
+                                    const int64_t *pt_pow, const int64_t *s_crt, double svar, const uint8_t key[32],
+                                    uint64_t ctr, int out_crt, int64_t *cs_out, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_error_rounded_batch(const lolhip_plan *p, void *stream, double svar, const uint8_t key[32],
+                                          uint64_t ctr, int64_t *z_dec, int64_t *work, int64_t B);
+/* inspection (tests): the ChaCha20 block function the kernels run, on the host; out[i] = word i of the block */
+LOLHIP_API void lolhip_chacha20_block(const uint8_t key[32], uint32_t counter, const uint32_t nonce[3], uint32_t out[16]);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

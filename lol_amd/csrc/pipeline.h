@@ -55,4 +55,18 @@ hipError_t launch_addmod(hipStream_t s, i64* y, const i64* a, i64 B, i64 n, int 
 hipError_t launch_lift(hipStream_t s, const i64* in, const i64* add, i64* out, i64 rows, const LiftParams& p, bool pmode,
                        const u64* lift_consts, const ModCtx* mod);
 
+// encrypt.hip: SymmSHE encrypt / errorRounded samplers over the ChaCha20 stream (rng_dev.h)
+struct ChaChaKey;
+enum { ENC_WRITE = 0, ENC_ADD = 1, ENC_INT = 2 };
+// Gaussians of deviation sigma, [B][n] doubles
+hipError_t launch_enc_gauss(hipStream_t s, double* d, i64 B, i64 n, const ChaChaKey& key, u64 ctr, int domain,
+                            double sigma);
+// e = rep + p round((g - rep) / p) per coefficient, g from d (when given) or the stream; rep [B][n] in (-p, p) or null;
+// mode ENC_WRITE / ENC_ADD: residues [B][n][T] (mod), ENC_INT: int64 [B][n] (out may alias d)
+hipError_t launch_enc_error(hipStream_t s, const double* d, const i64* rep, i64 p, i64* out, i64 B, i64 n, int T,
+                            const ModCtx* mod, int mode, const ChaChaKey& key, u64 ctr, int domain, double sigma);
+// c1 = uniform c^1 (CRT basis); c0 = c0 - c^1 s^ (combine) or -c^1 s^
+hipError_t launch_enc_c1(hipStream_t s, bool combine, i64* c0, i64* c1, const i64* s_crt, i64 B, i64 n, int T,
+                         const ModCtx* mod, const ChaChaKey& key, u64 ctr);
+
 }  // namespace lolhip

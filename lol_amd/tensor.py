@@ -107,6 +107,12 @@ def lib():
     L.lolhip_decrypt_work_len.restype = i64
     L.lolhip_error_term_batch.argtypes = [vp, vp, vp, ci, ci, vp, ci, i64, vp, vp, i64]
     L.lolhip_decrypt_batch.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, i64, i64, vp, vp, i64]
+    L.lolhip_encrypt_work_len.argtypes = [vp, i64]
+    L.lolhip_encrypt_work_len.restype = i64
+    L.lolhip_encrypt_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, C.c_char_p, C.c_uint64, ci, vp, vp, i64]
+    L.lolhip_error_rounded_batch.argtypes = [vp, vp, C.c_double, C.c_char_p, C.c_uint64, vp, vp, i64]
+    L.lolhip_chacha20_block.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.lolhip_chacha20_block.restype = None
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
     L.lolhip_ext_destroy.argtypes = [vp]
     L.lolhip_ext_destroy.restype = None
@@ -701,6 +707,60 @@ class Plan:
         _check(L.lolhip_decrypt_batch(self._h, pp._h, xh, _stream(stream), _devptr(cs), ncs, int(cs_crt), _devptr(s_crt), e,
                                       *args, _devptr(out), _devptr(work), B))
         return self._unstage(host, out)
+
+    # ---- encrypt / genSK (lol-apps SymmSHE.hs:120-146) -------------------------------------
+    @staticmethod
+    def _key(key):
+        key = os.urandom(32) if key is None else bytes(key)
+        if len(key) != 32:
+            raise ValueError("key must be 32 bytes")
+        return key
+
+    def encrypt(self, pt, s_crt, pp, svar, key=None, ctr=0, ext=None, out_crt=False, stream=None):
+        """SymmSHE encrypt (SymmSHE.hs:138-146) of B plaintexts pt [B][n_m] (in (-p, p), powerful basis of R_m) under
+        the key s_crt [n][T] (CRT basis) -> [2][B][n][T] = (c0, c1) of CT LSD 0 1, powerful basis or the CRT basis with
+        out_crt.  pp: the Plan of index m' over p alone; ext: an Ext from the Plan of (m, p) to pp, or None for m = m'.
+        Samples from the ChaCha20 stream of (key, ctr + b) (include/lolhip.h); key None draws a fresh one.  Never reuse
+        (key, ctr + b): advance ctr by B between calls."""
+        import torch
+        L = lib()
+        kb, xh = self._key(key), (None if ext is None else ext._h)
+        host = isinstance(pt, np.ndarray)
+        n_m = pp.n if ext is None else ext.lo.n
+        size = pt.size if host else pt.numel()
+        B = size // max(n_m, 1)
+        if B * n_m != size:
+            raise ValueError("pt is not [B][n_m]")
+        _check(L.lolhip_encrypt_batch(self._h, pp._h, xh, None, None, None, float(svar), kb, int(ctr), int(out_crt), None,
+                                      None, 0))
+        host, (pt, s_crt) = self._stage(pt, s_crt) if host else (False, (pt, s_crt))
+        work = torch.empty((max(L.lolhip_encrypt_work_len(self._h, B), 1),), dtype=torch.int64, device=pt.device)
+        out = torch.empty((2, B, self.n, self.T), dtype=torch.int64, device=pt.device)
+        _check(L.lolhip_encrypt_batch(self._h, pp._h, xh, _stream(stream), _devptr(pt), _devptr(s_crt), float(svar), kb,
+                                      int(ctr), int(out_crt), _devptr(out), _devptr(work), B))
+        return self._unstage(host, out)
+
+    def errorRounded(self, svar, B=1, key=None, ctr=0, stream=None):
+        """errorRounded svar (UCyc.hs:422-429; genSK, SymmSHE.hs:120-122): [B][n] int64 decoding-basis coefficients,
+        from the ChaCha20 stream of (key, ctr + b); key None draws a fresh one."""
+        import torch
+        L = lib()
+        kb = self._key(key)
+        _check(L.lolhip_error_rounded_batch(self._h, None, float(svar), kb, int(ctr), None, None, 0))
+        out = torch.empty((int(B), self.n), dtype=torch.int64, device="cuda")
+        _check(L.lolhip_error_rounded_batch(self._h, _stream(stream), float(svar), kb, int(ctr), _devptr(out), None, int(B)))
+        return out
+
+
+def chacha20_block(key, counter, nonce):
+    """The ChaCha20 block function the samplers run (RFC 8439 §2.3), on the host: 16 uint32 words."""
+    kb = bytes(key)
+    if len(kb) != 32:
+        raise ValueError("key must be 32 bytes")
+    nn = (C.c_uint32 * 3)(*[int(x) & 0xFFFFFFFF for x in nonce])
+    out = (C.c_uint32 * 16)()
+    lib().lolhip_chacha20_block(kb, int(counter) & 0xFFFFFFFF, nn, out)
+    return np.array(list(out), dtype=np.uint32)
 
 
 class Ext:

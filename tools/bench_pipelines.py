@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_pipelines.py — throughput of the SymmSHE pipeline kernels on one MI355X
-(BASELINE configs 3 and 5 shapes) and of decrypt (`--decrypt`: that leg alone).  Operands resident in HBM, HIP events on
+(BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone) and of encrypt / errorRounded
+(`--encrypt`: that leg alone).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -76,10 +77,54 @@ def decrypt_leg(gen):
         del cs, work, out, e_out
 
 
+def encrypt_leg(gen):
+    """SymmSHE encrypt (lolhip_encrypt_batch, both output bases) and errorRounded (lolhip_error_rounded_batch).
+    alg_bytes: the [B][n_m] plaintext read and the [2][B][n'][T] ciphertext written once (encrypt), the [B][n'] output
+    written once (errorRounded); the key, shared by the batch, is not counted."""
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    key = bytes(range(32))
+    # (label, m, m', moduli, p, B, svar): config 3's ring; the reference's sheBenches encrypt shapes (SHEBenches.hs:82-86,
+    # Default.hs:40-41); the reference's key-switch index
+    for label, m, m2, qs, p, B, svar in (
+            ("m'=2^15 T=4 59-bit", 2 ** 15, 2 ** 15, good_qs(2 ** 15, 2 ** 59, 4), 65537, 256, 1.0),
+            ("m=16 in m'=1024 q=1017857", 16, 1024, [1017857], 8, 8192, 1.0),
+            ("m=16 in m'=2048 q=1017857", 16, 2048, [1017857], 16, 8192, 1.0),
+            ("m'=14400 T=2 30-bit", 14400, 14400, good_qs(14400, 2 ** 29, 2), 11, 1024, 1.0)):
+        pq = lol_amd.Plan.for_index(m2, qs)
+        pp = lol_amd.Plan.for_index(m2, [p])
+        x_p = None if m == m2 else lol_amd.Ext(lol_amd.Plan.for_index(m, [p]), pp)
+        n_m = pp.n if x_p is None else x_p.lo.n
+        pt = torch.randint(0, p, (B, n_m), dtype=torch.int64, device="cuda", generator=gen)
+        s_crt = rnd(gen, qs, pq.n)
+        work = torch.empty((L.lolhip_encrypt_work_len(pq._h, B),), dtype=torch.int64, device="cuda")
+        out = torch.empty((2, B, pq.n, pq.T), dtype=torch.int64, device="cuda")
+        z = torch.empty((B, pq.n), dtype=torch.int64, device="cuda")
+        xh = None if x_p is None else x_p._h
+        cfg = f"{label} B={B} p={p}"
+        for out_crt in (1, 0):
+            ctr = [0]
+
+            def enc():
+                rc = L.lolhip_encrypt_batch(pq._h, pp._h, xh, st, ptr(pt), ptr(s_crt), svar, key, ctr[0], out_crt, ptr(out),
+                                            ptr(work), B)
+                assert rc == 0, rc
+                ctr[0] += B
+            ms = timeit(enc)
+            report("encrypt" + ("_crt_out" if out_crt else ""), cfg, ms, B, B * n_m * 8 + 2 * B * pq.n * pq.T * 8)
+        ms = timeit(lambda: L.lolhip_error_rounded_batch(pq._h, st, svar, key, 0, ptr(z), None, B))
+        report("errorRounded", cfg, ms, B, B * pq.n * 8)
+        del pt, s_crt, work, out, z
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
     if "--decrypt" in sys.argv:          # the decrypt leg alone
         decrypt_leg(gen)
+        return
+    if "--encrypt" in sys.argv:          # the encrypt leg alone
+        encrypt_leg(gen)
         return
     L = lol_amd.lib()
     st = torch.cuda.current_stream().cuda_stream
@@ -141,6 +186,7 @@ def main():
 
     streaming(gen)
     decrypt_leg(gen)
+    encrypt_leg(gen)
 
 
 def streaming(gen):
