@@ -447,6 +447,7 @@ int lolhip_ctmul_crt_batch(const lolhip_plan* p, void* stream, const int64_t* c0
                            const int64_t* d0, const int64_t* d1, int64_t* e0, int64_t* e1, int64_t* e2, int64_t B) {
   int rc = need_device(p); if (rc) return rc;
   if (!p->P.has_crt) return LOLHIP_ERR_NO_CRT;
+  if (p->P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (B < 0 || (B > 0 && (!c0 || !c1 || !d0 || !d1 || !e0 || !e1 || !e2))) return LOLHIP_ERR_INVALID;
   return launch_ctmul((hipStream_t)stream, c0, c1, d0, d1, e0, e1, e2, p->P.d_gcrt, B, p->P.n, p->P.T, p->P.d_mod)
                  == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
@@ -486,7 +487,7 @@ int lolhip_decompose_batch(const lolhip_plan* p, void* stream, const int64_t* c_
 int lolhip_knapsack_batch(const lolhip_plan* p, void* stream, const int64_t* xs_crt, int L, const int64_t* hint,
                           int K, const int64_t* addend, int64_t* out, int64_t B) {
   int rc = need_device(p); if (rc) return rc;
-  if (L < 0 || K < 1 || K > 3 || B < 0) return LOLHIP_ERR_INVALID;
+  if (L < 0 || K < 1 || K > 3 || B < 0 || p->P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (B > 0 && (!out || (L > 0 && (!xs_crt || !hint)))) return LOLHIP_ERR_INVALID;
   return launch_knapsack((hipStream_t)stream, xs_crt, L, hint, K, addend, out, B, p->P.n, p->P.T, p->P.d_mod, q_below(p->P, 29))
                  == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
@@ -660,6 +661,7 @@ int lolhip_evallin_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* s
   if (!ER.d_coeffs || !ES.d_embed_dec) return LOLHIP_ERR_NO_DEVICE;
   if (ER.host.phi != ES.host.phi || ER.lo->T != ES.lo->T || ER.lo->qs != ES.lo->qs || ER.lo->pps.size() != ES.lo->pps.size())
     return LOLHIP_ERR_INVALID;                                     // the two extensions must share E
+  if (ER.lo->T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (!ES.hi->has_crt) return LOLHIP_ERR_NO_CRT;
   if (B < 0 || (B > 0 && (!r_dec || !ys_crt || !out || !work))) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
@@ -699,7 +701,8 @@ int lolhip_tunnel_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* st
   if (!x_er || !x_es) return LOLHIP_ERR_INVALID;
   const ExtPlan &ER = x_er->X, &ES = x_es->X;
   if (!ER.d_coeffs || !ES.d_embed_pow) return LOLHIP_ERR_NO_DEVICE;
-  if (ER.host.phi != ES.host.phi || ER.lo->T != ES.lo->T || ER.lo->qs != ES.lo->qs) return LOLHIP_ERR_INVALID;
+  if (ER.host.phi != ES.host.phi || ER.lo->T != ES.lo->T || ER.lo->qs != ES.lo->qs || ER.lo->T > PIPE_MAX_T)
+    return LOLHIP_ERR_INVALID;
   if (B < 0 || (B > 0 && (!c0_dec || !c1_pow || !ys_crt || !hints || !out || !work))) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
   const Plan& PS = *ES.hi;
