@@ -280,7 +280,8 @@ LOLHIP_API int lolhip_decrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp
 /* encrypt / genSK (lol-apps SymmSHE.hs:120-146): samplers over the ChaCha20 stream cipher (RFC 8439 §2.3 block function,
  * counter mode), so every sample is a pure function of (key, position) and does not depend on launch shape, stream or how
  * a batch is split.  Stream layout: batch item b of a call with offset ctr uses the nonce (domain, lo32(ctr + b),
- * hi32(ctr + b)) and block counters from 0; domain 0 = the Gaussians of encrypt, 1 = the uniform c1, 2 = errorRounded.
+ * hi32(ctr + b)) and block counters from 0; domain 0 = the Gaussians of encrypt, 1 = the uniform c1, 2 = errorRounded,
+ * 3 / 4 = the Gaussians / uniform c1 of key-switch hints (lolhip_kshint_batch below, where the item is an LWE sample).
  *   Gaussian coefficient j (decoding basis): pair i = j >> 1 from block i >> 2, words w[4(i&3) .. 4(i&3)+3];
  *     a = w0 | w1 << 32, c = w2 | w3 << 32, u1 = ((a >> 11) + 1) 2^-53, u2 = (c >> 11) 2^-53, r = sigma sqrt(-2 ln u1),
  *     g_2i = r cos(2 pi u2), g_2i+1 = r sin(2 pi u2) (basic Box-Muller); for an index that is not a power of two the
@@ -288,7 +289,9 @@ LOLHIP_API int lolhip_decrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp
  *     variance), v = svar * (p * p) (in double) for encrypt and svar for errorRounded.
  *   Uniform CRT-basis residue [j][t]: r = j*T + t from block r >> 2, (w0 + 2^32 w1 + 2^64 w2 + 2^96 w3) mod q_t.
  * THE CALLER'S DUTY: never use the same (key, ctr + b) twice for one domain: after a call with batch B, advance ctr by B
- * (a repeated nonce repeats the noise and c1, which gives the secret key away).
+ * (a repeated nonce repeats the noise and c1, which gives the secret key away).  A hint call uses B*L items of domains 3
+ * and 4 (advance ctr by B*L); its own domains keep hint noise disjoint from genSK's (2) and encrypt's (0, 1) at equal
+ * ctr, so one counter may serve all three kinds of call.
  * lolhip_encrypt_batch: cs_out [2][B][n'][T] = (c0, c1) of CT LSD 0 1 [reduce e - c1 s, c1] over pq (index m', CRT
  *   basis required), in the CRT basis (out_crt = 1) or the powerful basis; the two are the same integers up to crtInv.
  *   e = errorCoset (svar) (embed pt): rep_j + p round((g_j - rep_j) / p) per decoding-basis coefficient (half to even),
@@ -313,6 +316,40 @@ LOLHIP_API int lolhip_error_rounded_batch(const lolhip_plan *p, void *stream, do
                                           uint64_t ctr, int64_t *z_dec, int64_t *work, int64_t B);
 /* inspection (tests): the ChaCha20 block function the kernels run, on the host; out[i] = word i of the block */
 LOLHIP_API void lolhip_chacha20_block(const uint8_t key[32], uint32_t counter, const uint32_t nonce[3], uint32_t out[16]);
+
+/* key-switch hints (lol-apps SymmSHE.hs:262-296 lweSample / ksHint; ksLinearHint / ksQuadCircHint :330-355 are ksHint
+ * with val = s_in and val = s*s; tunnelHint :531-545).  ksHint skout val is L rows over pq, one per gadget entry g_j
+ * (the rows of lolhip_gadget, [L][T]; L = lolhip_decompose_len(pq, base)):
+ *     hint_j = [ g_j val + c1_j (-s) + reduce e_j ,  c1_j ]      (CRT basis)
+ *   e_j = errorRounded svar (svar: skout's scaled variance), a decoding-basis vector taken to the CRT basis by l and
+ *   crt; c1_j uniform in the CRT basis.
+ * Stream layout: row j of batch item b is LWE sample i = ctr + b*L + j.  Its Gaussians are those of errorRounded at
+ *   item i of domain 3 (sigma = sqrt(svar (m'/rad m') / (2 pi)), then the map of lolhip_gaussian_dec_batch for an index
+ *   that is not a power of two, rounded half to even); its c1 is the uniform residue sampler at item i of domain 4
+ *   (residue r = c*T + t from block r >> 2, as for encrypt).  Advance ctr by B*L after a call.
+ * lolhip_kshint_batch: hints_out [B][L][2][n][T] (hints_out + b*L*2*n*T is exactly the [L][K=2][n][T] hint of
+ *   lolhip_keyswitch_batch) for vals_crt [B][n][T] in the CRT basis of pq; s_crt [n][T]: skout reduced into pq, CRT
+ *   basis, shared by the batch.  work: lolhip_kshint_work_len(pq, base, B) = B*L*n*T int64 (m' = 2^k) or B*L*n*(T+1).
+ * lolhip_tunnel_hint_batch: hints_out [rel][L][2][n_S][T] (rel = n_R/n_E; the hints of lolhip_tunnel_batch) with
+ *   comps_i = evalLin f' (s_in p_i) for the relative powerful-basis elements p_i of R'/E' (p_i the powerful-basis unit
+ *   vector at lolhip_ext_table(x_er, 5)[i*n_E], the pairing of lolhip_tunnel_batch); hint i = ksHint skout comps_i over
+ *   the S' plan, items ctr .. ctr + rel*L - 1.  ys_crt [rel][n_S][T]: the linearDec table of f'q that
+ *   lolhip_tunnel_batch takes (reduce commutes with the Z-linear evalLin); s_in_crt [n_R][T], s_out_crt [n_S][T]: the
+ *   two keys in the CRT bases of R' and S'.  work: lolhip_tunnel_hint_work_len(x_er, x_es, base) int64.
+ * Limits: T <= 16 and the sampler's index limits of lolhip_encrypt_batch (for S').
+ * Status: LOLHIP_ERR_INVALID for svar <= 0 or not finite, B < 0, an invalid base, T > 16, an index beyond the limits,
+ *   extensions that do not share E' and the moduli, NULL pointers; LOLHIP_ERR_NO_CRT when pq (S', R') has no CRT
+ *   basis; LOLHIP_ERR_NO_DEVICE on a host-only plan.  Every one is decided on the host before any launch: the output is
+ *   then not written.  No call synchronises or allocates. */
+LOLHIP_API int64_t lolhip_kshint_work_len(const lolhip_plan *pq, int64_t base, int64_t B);
+LOLHIP_API int lolhip_kshint_batch(const lolhip_plan *pq, void *stream, const int64_t *s_crt, const int64_t *vals_crt,
+                                   double svar, int64_t base, const uint8_t key[32], uint64_t ctr, int64_t *hints_out,
+                                   int64_t *work, int64_t B);
+LOLHIP_API int64_t lolhip_tunnel_hint_work_len(const lolhip_ext *x_er, const lolhip_ext *x_es, int64_t base);
+LOLHIP_API int lolhip_tunnel_hint_batch(const lolhip_ext *x_er, const lolhip_ext *x_es, void *stream,
+                                        const int64_t *ys_crt, const int64_t *s_in_crt, const int64_t *s_out_crt,
+                                        double svar, int64_t base, const uint8_t key[32], uint64_t ctr,
+                                        int64_t *hints_out, int64_t *work);
 
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */

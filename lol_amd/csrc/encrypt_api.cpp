@@ -1,66 +1,11 @@
 // lol_amd/csrc/encrypt_api.cpp — the C ABI of SymmSHE encrypt / genSK (include/lolhip.h; lol-apps SymmSHE.hs:120-146):
-// host checks, the deviation of the samplers and the launch plan over the kernels of encrypt.hip and the existing
-// transforms.
+// host checks and the launch plan over the kernels of encrypt.hip and the existing transforms (the sampler's limits,
+// deviation and key words are in sampler_internal.h).
 #include <hip/hip_runtime_api.h>
 
-#include <cmath>
-
-#include "capi_internal.h"
-#include "kernels.h"
-#include "rng_dev.h"
+#include "sampler_internal.h"
 
 using namespace lolhip;
-
-namespace {
-
-constexpr int64_t POW2_MAX_N = 16384;        // 2-powers: no map, one fused pass (k_enc_error from the stream)
-
-// every prime of the index is 2 (m' = 2^k, or 1): L and the Gaussian map are identities
-bool two_power(const Plan& P) {
-  for (const PP& pe : P.pps) if (pe.p != 2) return false;
-  return true;
-}
-
-// LOLHIP_OK when the sampler takes this index: a 2-power up to n' = 16384, else the limits of the Gaussian map
-int sampler_ok(const Plan& P) {
-  if (two_power(P)) return P.n <= POW2_MAX_N ? LOLHIP_OK : LOLHIP_ERR_INVALID;
-  return P.float_ok ? LOLHIP_OK : LOLHIP_ERR_INVALID;
-}
-
-// sigma = sqrt(v (m'/rad m') / 2 pi): the deviation of tGaussianDec v (scaled variance = 2 pi x variance,
-// GaussRandom.hs:27-44; CPP.hs:376-389)
-double deviation(const Plan& P, double v) {
-  double mrad = 1.0;
-  for (const PP& pe : P.pps)
-    for (int i = 1; i < pe.e; ++i) mrad *= pe.p;
-  return std::sqrt(v * mrad / 6.283185307179586);
-}
-
-ChaChaKey make_key(const uint8_t key[32]) {
-  ChaChaKey k;
-  for (int i = 0; i < 8; ++i)
-    k.k[i] = (uint32_t)key[4 * i] | (uint32_t)key[4 * i + 1] << 8 | (uint32_t)key[4 * i + 2] << 16 |
-             (uint32_t)key[4 * i + 3] << 24;
-  return k;
-}
-
-bool svar_ok(double svar) { return std::isfinite(svar) && svar > 0; }
-
-// the double slab of the map and the sampled coefficients into [B][n] int64 / residues: one pass from the stream for a
-// 2-power, else Gaussians -> k_gauss (the decoding-basis map of tGaussianDec) -> the rounding pass
-int sample_error(const Plan& P, hipStream_t s, double* d, const int64_t* rep, int64_t p, int64_t* out, int mode,
-                 const ChaChaKey& key, uint64_t ctr, int domain, double sigma, int64_t B) {
-  if (two_power(P))
-    return launch_enc_error(s, nullptr, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma) == hipSuccess
-               ? LOLHIP_OK : LOLHIP_ERR_HIP;
-  if (launch_enc_gauss(s, d, B, P.n, key, ctr, domain, sigma) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (launch_gauss(s, d, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
-    return LOLHIP_ERR_HIP;
-  return launch_enc_error(s, d, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
-}
-
-}  // namespace
 
 extern "C" {
 

@@ -1,0 +1,124 @@
+// lol_amd/csrc/kshint_api.cpp — the C ABI of SymmSHE's key-switch and tunnel hints (include/lolhip.h; lol-apps
+// SymmSHE.hs:262-296 lweSample / ksHint, :531-545 tunnelHint): host checks and the launch plan over the samplers of
+// encrypt.hip, the existing transforms, evalLin and the combine kernel of kshint.hip.
+#include <hip/hip_runtime_api.h>
+
+#include "sampler_internal.h"
+
+using namespace lolhip;
+
+namespace {
+
+// the digit counts of `base` over the plan's moduli: the part of the decomposition parameters the gadget needs
+// (make_decomp of the key switch, capi.cpp, decides the same statuses: T > 16, base neither 0 nor >= 2)
+int hint_decomp(const Plan& P, int64_t base, DecompParams& d) {
+  if (P.T > PIPE_MAX_T || (base != 0 && base < 2)) return LOLHIP_ERR_INVALID;
+  d = DecompParams{};
+  d.T = P.T;
+  d.base = base;
+  for (int t = 0; t < P.T; ++t) {
+    int k = 0;
+    if (base == 0) k = 1;
+    else for (u64 q = P.qs[t]; q != 0; q /= (u64)base) ++k;      // gadlen (ZqBasic.hs:238-240)
+    d.k[t] = k;
+    d.L += k;
+  }
+  return LOLHIP_OK;
+}
+
+// every status of a ksHint call over plan p (B rows of L samples each), decided on the host
+int hint_status(const Plan& P, double svar, int64_t base, int64_t B, DecompParams& d) {
+  if (!svar_ok(svar) || B < 0) return LOLHIP_ERR_INVALID;
+  int rc = hint_decomp(P, base, d); if (rc) return rc;
+  rc = sampler_ok(P); if (rc) return rc;
+  if (!P.has_crt) return LOLHIP_ERR_NO_CRT;
+  return LOLHIP_OK;
+}
+
+int64_t hint_work_len(const Plan& P, int64_t L, int64_t B) {
+  return B * L * P.n * (two_power(P) ? P.T : P.T + 1);
+}
+
+// work: e^ [B][L][n][T] | the double slab [B][L][n] of the Gaussian map (an index that is not a 2-power)
+//   rounded Gaussians (domain 3) -> residues -> l -> one crt of B*L polynomials -> k_kshint_combine (domain 4)
+int kshint_launch(const Plan& P, hipStream_t s, const int64_t* s_crt, const int64_t* vals_crt, double svar,
+                  const DecompParams& d, const uint8_t key[32], uint64_t ctr, int64_t* hints, int64_t* work, int64_t B) {
+  const int64_t BL = B * d.L;
+  const ChaChaKey k = make_key(key);
+  int64_t* e = work;
+  double* dbl = two_power(P) ? nullptr : reinterpret_cast<double*>(work + BL * P.n * P.T);
+  int rc = sample_error(P, s, dbl, nullptr, 1, e, ENC_WRITE, k, ctr, CHACHA_DOM_HINT_GAUSS, deviation(P, svar), BL);
+  if (rc) return rc;
+  if (!P.prog_l.stages.empty()) { rc = capi_run_prog(P, P.prog_l, s, e, BL, nullptr); if (rc) return rc; }
+  rc = capi_do_crt(P, s, e, BL, false); if (rc) return rc;
+  return launch_kshint_combine(s, e, vals_crt, s_crt, hints, B, P.n, d, P.d_mod, k, ctr) == hipSuccess
+             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lolhip_kshint_work_len(const lolhip_plan* pq, int64_t base, int64_t B) {
+  if (!pq || B < 0) return LOLHIP_ERR_INVALID;
+  DecompParams d;
+  const int rc = hint_decomp(pq->P, base, d); if (rc) return rc;
+  return hint_work_len(pq->P, d.L, B);
+}
+
+int lolhip_kshint_batch(const lolhip_plan* pq, void* stream, const int64_t* s_crt, const int64_t* vals_crt, double svar,
+                        int64_t base, const uint8_t key[32], uint64_t ctr, int64_t* hints_out, int64_t* work, int64_t B) {
+  int rc = capi_need_device(pq); if (rc) return rc;
+  DecompParams d;
+  rc = hint_status(pq->P, svar, base, B, d); if (rc) return rc;
+  if (B > 0 && (!s_crt || !vals_crt || !key || !hints_out || !work)) return LOLHIP_ERR_INVALID;
+  if (B == 0) return LOLHIP_OK;
+  return kshint_launch(pq->P, (hipStream_t)stream, s_crt, vals_crt, svar, d, key, ctr, hints_out, work, B);
+}
+
+// work: comps [rel][n_S][T] | then either (p_i s_in [rel][n_R][T] | evalLin scratch rel * rel * (n_E + n_S) * T)
+// or, once evalLin is done, the ksHint scratch of rel rows over the S' plan
+int64_t lolhip_tunnel_hint_work_len(const lolhip_ext* x_er, const lolhip_ext* x_es, int64_t base) {
+  if (!x_er || !x_es) return LOLHIP_ERR_INVALID;
+  const ExtPlan &ER = x_er->X, &ES = x_es->X;
+  DecompParams d;
+  const int rc = hint_decomp(*ES.hi, base, d); if (rc) return rc;
+  const int64_t rel = ER.host.phi2 / ER.host.phi, T = ER.lo->T, nE = ER.host.phi, nR = ER.host.phi2,
+                nS = ES.host.phi2;
+  const int64_t lin = rel * nR * T + rel * rel * (nE + nS) * T, ks = hint_work_len(*ES.hi, d.L, rel);
+  return rel * nS * T + (lin > ks ? lin : ks);
+}
+
+// tunnelHint f skout skin (SymmSHE.hs:531-545): comps_i = evalLin f' (s_in p_i) over the relative powerful basis p_i of
+// R'/E', then hints_i = ksHint skout comps_i:
+//   unit vectors p_i -> crt (R') -> * s_in^ -> crtInv -> lInv -> evalLin (B = rel) -> ksHint (B = rel, S' plan)
+int lolhip_tunnel_hint_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* stream, const int64_t* ys_crt,
+                             const int64_t* s_in_crt, const int64_t* s_out_crt, double svar, int64_t base,
+                             const uint8_t key[32], uint64_t ctr, int64_t* hints_out, int64_t* work) {
+  if (!x_er || !x_es) return LOLHIP_ERR_INVALID;
+  const ExtPlan &ER = x_er->X, &ES = x_es->X;
+  if (!ER.d_coeffs || !ES.d_embed_dec) return LOLHIP_ERR_NO_DEVICE;
+  if (ER.host.phi != ES.host.phi || ER.lo->T != ES.lo->T || ER.lo->qs != ES.lo->qs || ER.lo->pps.size() != ES.lo->pps.size())
+    return LOLHIP_ERR_INVALID;                                     // the two extensions must share E' and the moduli
+  const Plan &PR = *ER.hi, &PS = *ES.hi;
+  DecompParams d;
+  int rc = hint_status(PS, svar, base, 0, d); if (rc) return rc;
+  if (!PR.has_crt) return LOLHIP_ERR_NO_CRT;
+  if (!ys_crt || !s_in_crt || !s_out_crt || !key || !hints_out || !work) return LOLHIP_ERR_INVALID;
+
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rel = ER.host.phi2 / ER.host.phi, T = PS.T, nR = PR.n, nS = PS.n;
+  int64_t* comps = work;                                           // [rel][n_S][T]
+  int64_t* sp = comps + rel * nS * T;                              // [rel][n_R][T]
+  int64_t* ev = sp + rel * nR * T;                                 // evalLin scratch
+  int64_t* ks = sp;                                                // ksHint scratch, after evalLin
+  if (launch_unit_rows(s, sp, ER.d_coeffs, rel, nR, (int)T, ER.host.phi) != hipSuccess) return LOLHIP_ERR_HIP;
+  rc = capi_do_crt(PR, s, sp, rel, false); if (rc) return rc;
+  if (launch_sk_eval(s, sp, 1, true, s_in_crt, sp, rel, nR, (int)T, PR.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
+  rc = capi_do_crt(PR, s, sp, rel, true); if (rc) return rc;
+  if (!PR.prog_linv.stages.empty()) { rc = capi_run_prog(PR, PR.prog_linv, s, sp, rel, nullptr); if (rc) return rc; }
+  rc = lolhip_evallin_batch(x_er, x_es, stream, sp, ys_crt, comps, ev, rel); if (rc) return rc;
+  return kshint_launch(PS, s, s_out_crt, comps, svar, d, key, ctr, hints_out, ks, rel);
+}
+
+}  // extern "C"

@@ -69,4 +69,11 @@ hipError_t launch_enc_error(hipStream_t s, const double* d, const i64* rep, i64 
 hipError_t launch_enc_c1(hipStream_t s, bool combine, i64* c0, i64* c1, const i64* s_crt, i64 B, i64 n, int T,
                          const ModCtx* mod, const ChaChaKey& key, u64 ctr);
 
+// kshint.hip: key-switch hint rows (lol-apps SymmSHE.hs:262-296).  e_crt [B][L][n][T] (the crt'd rounded Gaussians),
+// vals [B][n][T], s_crt [n][T] -> hints [B][L][2][n][T]: h1 = c^1 (domain 4, item ctr + b L + j), h0 = g_j val + e - c^1 s
+hipError_t launch_kshint_combine(hipStream_t s, const i64* e_crt, const i64* vals, const i64* s_crt, i64* hints, i64 B,
+                                 i64 n, const DecompParams& dp, const ModCtx* mod, const ChaChaKey& key, u64 ctr);
+// out [rel][n][T]: the powerful-basis unit vector at coeffs[i * n_lo] for row i (0 / 1 residues)
+hipError_t launch_unit_rows(hipStream_t s, i64* out, const int32_t* coeffs, i64 rel, i64 n, int T, i64 n_lo);
+
 }  // namespace lolhip

@@ -1,5 +1,5 @@
 // lol_amd/csrc/rng_dev.h — the ChaCha20 block function (RFC 8439 §2.3) and the stream layout of the SymmSHE
-// samplers (encrypt.hip), one source for the kernels and the host inspection entry lolhip_chacha20_block.
+// samplers (encrypt.hip, kshint.hip), one source for the kernels and the host inspection entry lolhip_chacha20_block.
 //
 // The reference draws its encryption randomness from a cryptographic generator (lol-apps SymmSHE.hs:138-146 under
 // CryptoRand).  Here every output word is a pure function of (key, nonce, block counter): the samples do not depend
@@ -20,7 +20,9 @@
 
 namespace lolhip {
 
-enum { CHACHA_DOM_ENC_GAUSS = 0, CHACHA_DOM_UNIFORM = 1, CHACHA_DOM_ERR_ROUNDED = 2 };
+// 3 / 4: the Gaussians and c1 of key-switch hint rows (kshint.hip; item = LWE sample ctr + b L + j)
+enum { CHACHA_DOM_ENC_GAUSS = 0, CHACHA_DOM_UNIFORM = 1, CHACHA_DOM_ERR_ROUNDED = 2, CHACHA_DOM_HINT_GAUSS = 3,
+       CHACHA_DOM_HINT_UNIFORM = 4 };
 
 // the 256-bit key as eight little-endian words (passed to kernels by value)
 struct ChaChaKey { uint32_t k[8]; };

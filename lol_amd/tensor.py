@@ -111,6 +111,12 @@ def lib():
     L.lolhip_encrypt_work_len.restype = i64
     L.lolhip_encrypt_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, C.c_char_p, C.c_uint64, ci, vp, vp, i64]
     L.lolhip_error_rounded_batch.argtypes = [vp, vp, C.c_double, C.c_char_p, C.c_uint64, vp, vp, i64]
+    L.lolhip_kshint_work_len.argtypes = [vp, i64, i64]
+    L.lolhip_kshint_work_len.restype = i64
+    L.lolhip_kshint_batch.argtypes = [vp, vp, vp, vp, C.c_double, i64, C.c_char_p, C.c_uint64, vp, vp, i64]
+    L.lolhip_tunnel_hint_work_len.argtypes = [vp, vp, i64]
+    L.lolhip_tunnel_hint_work_len.restype = i64
+    L.lolhip_tunnel_hint_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, i64, C.c_char_p, C.c_uint64, vp, vp]
     L.lolhip_chacha20_block.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.lolhip_chacha20_block.restype = None
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
@@ -751,6 +757,44 @@ class Plan:
         _check(L.lolhip_error_rounded_batch(self._h, _stream(stream), float(svar), kb, int(ctr), _devptr(out), None, int(B)))
         return out
 
+    # ---- key-switch hints (lol-apps SymmSHE.hs:262-296, 330-355) -------------------------
+    def ksHint(self, s_crt, vals_crt, svar, base, key=None, ctr=0, stream=None):
+        """ksHint skout val (SymmSHE.hs:286-296) for B values vals_crt [B][n][T] (CRT basis) under the key s_crt [n][T]
+        (CRT basis) -> [B][L][2][n][T] CRT-basis hints; [b] is the hint keySwitch takes.  Row j of item b is LWE sample
+        ctr + b L + j of the ChaCha20 stream (include/lolhip.h): advance ctr by B L between calls; key None draws a
+        fresh key."""
+        import torch
+        L = lib()
+        kb = self._key(key)
+        host = isinstance(vals_crt, np.ndarray)
+        size = vals_crt.size if host else vals_crt.numel()
+        per = self.n * self.T
+        B = size // per
+        if B * per != size:
+            raise ValueError("vals_crt is not [B][n][T]")
+        _check(L.lolhip_kshint_batch(self._h, None, None, None, float(svar), int(base), kb, int(ctr), None, None, 0))
+        host, (vals_crt, s_crt) = self._stage(vals_crt, s_crt) if host else (False, (vals_crt, s_crt))
+        nL = self.decomposeLen(base)
+        work = torch.empty((max(L.lolhip_kshint_work_len(self._h, int(base), B), 1),), dtype=torch.int64,
+                           device=vals_crt.device)
+        out = torch.empty((B, nL, 2, self.n, self.T), dtype=torch.int64, device=vals_crt.device)
+        _check(L.lolhip_kshint_batch(self._h, _stream(stream), _devptr(s_crt), _devptr(vals_crt), float(svar), int(base),
+                                     kb, int(ctr), _devptr(out), _devptr(work), B))
+        return self._unstage(host, out)
+
+    def ksLinearHint(self, s_out_crt, s_in_crt, svar, base, key=None, ctr=0, stream=None):
+        """ksLinearHint skout skin (SymmSHE.hs:330-335) = ksHint skout s_in: one [L][2][n][T] hint."""
+        return self.ksHint(s_out_crt, s_in_crt, svar, base, key=key, ctr=ctr, stream=stream)[0]
+
+    def ksQuadCircHint(self, s_crt, svar, base, key=None, ctr=0, stream=None):
+        """ksQuadCircHint sk (SymmSHE.hs:352-355) = ksHint sk (s*s), s*s formed on the device: one [L][2][n][T] hint."""
+        _check(lib().lolhip_kshint_batch(self._h, None, None, None, float(svar), int(base), self._key(key), int(ctr), None,
+                                         None, 0))
+        host, (s_crt,) = self._stage(s_crt)
+        s2 = s_crt.clone().contiguous()
+        self.mul(s2, s_crt, stream=stream)
+        return self._unstage(host, self.ksHint(s_crt, s2, svar, base, key=key, ctr=ctr, stream=stream)[0])
+
 
 def chacha20_block(key, counter, nonce):
     """The ChaCha20 block function the samplers run (RFC 8439 §2.3), on the host: 16 uint32 words."""
@@ -842,6 +886,29 @@ class Ext:
         out = torch.empty((2, B, S.n, S.T), dtype=torch.int64, device=c0_dec.device)
         _check(lib().lolhip_tunnel_batch(self._h, es._h, _stream(stream), _devptr(c0_dec), _devptr(c1_pow), _devptr(ys_crt),
                                          _devptr(hints), int(base), _devptr(out), _devptr(work), B))
+        return Plan._unstage(host, out)
+
+    def tunnelHint(self, es: "Ext", ys_crt, s_in_crt, s_out_crt, svar, base, key=None, ctr=0, stream=None):
+        """tunnelHint f skout skin (SymmSHE.hs:531-545): self = E' in R', es = E' in S'; ys_crt [rel][n_S][T] the
+        linearDec table of f'q (what tunnel takes), s_in_crt [n_R][T] and s_out_crt [n_S][T] the keys in the CRT bases
+        -> hints [rel][L][2][n_S][T] for tunnel.  Uses stream items ctr .. ctr + rel L - 1."""
+        import torch
+        L = lib()
+        kb = Plan._key(key)
+        R, S = self.hi, es.hi
+        rel = R.n // self.lo.n
+        shapes = [(ys_crt, rel * S.n * S.T), (s_in_crt, R.n * R.T), (s_out_crt, S.n * S.T)]
+        if any((a.size if isinstance(a, np.ndarray) else a.numel()) != want for a, want in shapes):
+            raise LolHipError(ERR_INVALID, "tunnelHint: ys_crt, s_in_crt or s_out_crt is not of the plans of the extensions")
+        wl = L.lolhip_tunnel_hint_work_len(self._h, es._h, int(base))
+        _check(min(wl, 0))
+        host, (ys_crt, s_in_crt, s_out_crt) = Plan._stage(ys_crt, s_in_crt, s_out_crt)
+        dev = ys_crt.device
+        work = torch.empty((max(wl, 1),), dtype=torch.int64, device=dev)
+        out = torch.empty((rel, S.decomposeLen(base), 2, S.n, S.T), dtype=torch.int64, device=dev)
+        _check(L.lolhip_tunnel_hint_batch(self._h, es._h, _stream(stream), _devptr(ys_crt), _devptr(s_in_crt),
+                                          _devptr(s_out_crt), float(svar), int(base), kb, int(ctr), _devptr(out),
+                                          _devptr(work)))
         return Plan._unstage(host, out)
 
     def twacePowDec(self, x, out=None, stream=None): return self._run(EXT_TWACE_POWDEC, "twace_powdec", x, False, out, stream)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/bench_pipelines.py — throughput of the SymmSHE pipeline kernels on one MI355X
-(BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone) and of encrypt / errorRounded
-(`--encrypt`: that leg alone).  Operands resident in HBM, HIP events on
+(BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone), of encrypt / errorRounded
+(`--encrypt`: that leg alone) and of the key-switch / tunnel hints (`--kshint`: that leg alone).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -118,6 +118,63 @@ def encrypt_leg(gen):
         del pt, s_crt, work, out, z
 
 
+def kshint_leg(gen):
+    """Key-switch hints (lolhip_kshint_batch) and one tunnel hint (lolhip_tunnel_hint_batch).  alg_bytes: the [B][n][T]
+    values read and the [B][L][2][n][T] hints written once (the key, shared by the batch, and the linearDec table are not
+    counted).  At config 3 encrypt to the CRT basis at B = 256 runs in the same process, as the yardstick of the hint
+    (same number of LWE samples as B = 64 TrivGad rows)."""
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    key = bytes(range(32))
+    q3 = good_qs(2 ** 15, 2 ** 59, 4)
+    pq, pp = lol_amd.Plan.for_index(2 ** 15, q3), lol_amd.Plan.for_index(2 ** 15, [65537])
+    B = 256
+    pt = torch.randint(0, 65537, (B, pq.n), dtype=torch.int64, device="cuda", generator=gen)
+    s_crt = rnd(gen, q3, pq.n)
+    work = torch.empty((L.lolhip_encrypt_work_len(pq._h, B),), dtype=torch.int64, device="cuda")
+    out = torch.empty((2, B, pq.n, pq.T), dtype=torch.int64, device="cuda")
+    ms = timeit(lambda: L.lolhip_encrypt_batch(pq._h, pp._h, None, st, ptr(pt), ptr(s_crt), 1.0, key, 0, 1, ptr(out),
+                                               ptr(work), B))
+    report("encrypt_crt_out", f"m'=2^15 T=4 59-bit B={B} p=65537", ms, B, B * pq.n * 8 + 2 * B * pq.n * pq.T * 8)
+    del pt, work, out
+    # (label, m', moduli, bases, B): config 3's ring; config 5's ring and moduli; the reference's key-switch index
+    for label, m, qs, bases, B in (("m'=2^15 T=4 59-bit", 2 ** 15, q3, (0, 2 ** 16), 64),
+                                   ("m'=2048 q=1017857*1032193", 2048, [1017857, 1032193], (256,), 64),
+                                   ("m'=14400 T=2 30-bit", 14400, good_qs(14400, 2 ** 29, 2), (0, 256), 16)):
+        P = lol_amd.Plan.for_index(m, qs)
+        s_crt = rnd(gen, qs, P.n)
+        vals = rnd(gen, qs, B, P.n)
+        for base in bases:
+            nL = P.decomposeLen(base)
+            work = torch.empty((L.lolhip_kshint_work_len(P._h, base, B),), dtype=torch.int64, device="cuda")
+            out = torch.empty((B, nL, 2, P.n, P.T), dtype=torch.int64, device="cuda")
+            ctr = [0]
+
+            def hint():
+                rc = L.lolhip_kshint_batch(P._h, st, ptr(s_crt), ptr(vals), 1.0, base, key, ctr[0], ptr(out), ptr(work), B)
+                assert rc == 0, rc
+                ctr[0] += B * nL
+            ms = timeit(hint)
+            report("ksHint", f"{label} base={base} B={B} L={nL}", ms, B * nL, B * P.n * P.T * 8 + B * nL * 2 * P.n * P.T * 8)
+            del work, out
+    # one tunnel hint at the shape of lol-apps' chain hops (e, r, s) = (128, 128*7, 128*13)
+    qs = good_qs(128 * 7 * 13, 2 ** 29, 2)
+    PE, PR, PS = (lol_amd.Plan.for_index(m, qs) for m in (128, 128 * 7, 128 * 13))
+    XR, XS = lol_amd.Ext(PE, PR), lol_amd.Ext(PE, PS)
+    rel = PR.n // PE.n
+    ys = rnd(gen, qs, rel, PS.n)
+    s_in, s_out = rnd(gen, qs, PR.n), rnd(gen, qs, PS.n)
+    for base in (0, 16):
+        nL = PS.decomposeLen(base)
+        work = torch.empty((L.lolhip_tunnel_hint_work_len(XR._h, XS._h, base),), dtype=torch.int64, device="cuda")
+        out = torch.empty((rel, nL, 2, PS.n, PS.T), dtype=torch.int64, device="cuda")
+        ms = timeit(lambda: L.lolhip_tunnel_hint_batch(XR._h, XS._h, st, ptr(ys), ptr(s_in), ptr(s_out), 1.0, base, key, 0,
+                                                       ptr(out), ptr(work)))
+        report("tunnelHint", f"e=128 r=896 s=1664 T=2 30-bit base={base} rel={rel} L={nL}", ms, rel * nL,
+               rel * nL * 2 * PS.n * PS.T * 8)
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
     if "--decrypt" in sys.argv:          # the decrypt leg alone
@@ -125,6 +182,9 @@ def main():
         return
     if "--encrypt" in sys.argv:          # the encrypt leg alone
         encrypt_leg(gen)
+        return
+    if "--kshint" in sys.argv:           # the key-switch / tunnel hint leg alone
+        kshint_leg(gen)
         return
     L = lol_amd.lib()
     st = torch.cuda.current_stream().cuda_stream
