@@ -20,6 +20,7 @@ struct Pow2Launch {
   const void *tw_fwd, *tw_inv, *scale;   // Shoup-pair tables: u64 pairs (arith 0/1) or u32 pairs (arith 2)
   const ModCtx* mod;
   int arith;         // 4: every modulus < 2^27; 2: < 2^30; 3: < 2^31 (32-bit paths); 1: every modulus < 2^61; 0: exact 64-bit
+  int trunc = 0;     // arith 1, mode 2, L >= 11: the truncated transforms with the degree-3 base case (pow2_impl.h)
 };
 // mode 0 = crt, 1 = crtInv, 2 = fused poly-mul
 hipError_t launch_pow2(const Pow2Launch& a, int mode);

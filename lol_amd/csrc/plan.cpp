@@ -691,7 +691,9 @@ int plan_upload(Plan& P) {
     // per component 8 words: Shoup pairs of S = mhat^-1, of the level-1 inverse twiddle times S, and of the
     // same two times 2^64 mod q (the 64-bit fused poly-mul's pointwise product is a Montgomery reduction,
     // which leaves a factor 2^-64 that the last inverse level takes back for free)
-    std::vector<u64> fwd((size_t)(T * n * 2), 0), inv((size_t)(T * n * 2), 0), sc((size_t)(T * 8), 0);
+    // then per component 4 words: Shoup pairs of (n/4)^-1 2^64 and of the level-1 inverse twiddle times it, the
+    // scale of the fused poly-mul's truncated route (its inverse starts at level L - 2: pow2_impl.h, pow2_base4)
+    std::vector<u64> fwd((size_t)(T * n * 2), 0), inv((size_t)(T * n * 2), 0), sc((size_t)(T * 12), 0);
     for (int t = 0; t < T; ++t) {
       const u64 q = P.qs[(size_t)t];
       const u64 S = (u64)P.mhatinv[(size_t)t];
@@ -702,6 +704,14 @@ int plan_upload(Plan& P) {
         for (int k = 0; k < 4; ++k) {
           ShoupW ss = make_shoup(vals[k], q);
           sc[(size_t)(t * 8 + 2 * k)] = ss.w; sc[(size_t)(t * 8 + 2 * k + 1)] = ss.wp;
+        }
+        if (L >= 2) {
+          const u64 S4 = mulmod(vals[2], 4 % q, q);            // (n/4)^-1 2^64 = 4 S 2^64
+          const u64 tv[2] = {S4, mulmod(vals[3], 4 % q, q)};
+          for (int k = 0; k < 2; ++k) {
+            ShoupW ss = make_shoup(tv[k], q);
+            sc[(size_t)(T * 8 + t * 4 + 2 * k)] = ss.w; sc[(size_t)(T * 8 + t * 4 + 2 * k + 1)] = ss.wp;
+          }
         }
       }
       for (int s = 1; s <= L; ++s) {
@@ -726,7 +736,7 @@ int plan_upload(Plan& P) {
     for (u64 q : P.qs) { if (q >= (1ull << 30)) P.pow2.arith32 = 3; }
     for (u64 q : P.qs) { if (q >= (1ull << 31) || !(q & 1)) P.pow2.arith32 = 0; }     // the 32-bit classes' pointwise product is a Montgomery step: odd q
     if (P.pow2.arith32) {   // 32-bit Shoup pairs: wp = floor(w * 2^32 / q)
-      std::vector<uint32_t> f32(fwd.size()), i32(inv.size()), s32(sc.size());
+      std::vector<uint32_t> f32(fwd.size()), i32(inv.size()), s32((size_t)T * 8);
       for (int t = 0; t < T; ++t) {
         const u64 q = P.qs[(size_t)t];
         for (i64 i = 0; i < n; ++i) {

@@ -69,7 +69,8 @@ struct Pow2Tables {
   // per component t, n Shoup pairs: entry (N/2 + i) = psi_N^(2i+1), N = 2..n (entry 0 unused)
   u64* d_tw_fwd = nullptr;         // [T][n][2]
   u64* d_tw_inv = nullptr;         // [T][n][2]  inverse twiddles; the level-1 entry is pre-scaled
-  u64* d_scale = nullptr;          // [T][8]     Shoup pairs of mhatInv, the level-1 inverse twiddle times mhatInv, and both times 2^64 (plan.cpp)
+  u64* d_scale = nullptr;          // [T][8]     Shoup pairs of mhatInv, the level-1 inverse twiddle times mhatInv, and both times 2^64 (plan.cpp),
+                                   // then [T][4]: both times 4 2^64 (the fused poly-mul's truncated route)
   // the same three tables as 32-bit Shoup pairs (w, floor(w*2^32/q)) when every q_t < 2^31
   uint32_t *d_tw_fwd32 = nullptr, *d_tw_inv32 = nullptr, *d_scale32 = nullptr;
   int arith32 = 0;                 // 4: every q_t < 2^27; 2: < 2^30; 3: < 2^31; 0: no 32-bit tables
@@ -164,7 +165,7 @@ void plan_free_device(Plan& P);
 // A/B switches of the launch paths (development and tests): read ONCE from the environment
 // (LOLHIP_<NAME>) into atomics; tests flip them through lolhip_debug_set, never through setenv
 // (getenv racing with setenv is undefined behaviour, and plans are used from concurrent threads).
-enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_COUNT };
+enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_COUNT };
 bool sw(Switch which);
 inline bool pow2_no_t1() { return sw(SW_NO_T1); }
 

@@ -226,7 +226,8 @@ __device__ __forceinline__ u32 shoup_pair(u32 d, u32 w, u32 wp, u32 q) {
 
 // forward (Cooley-Tukey) butterfly:  X' = X + w*Y,  Y' = X - w*Y
 // WS: the twiddle is wave-uniform (SGPR operands in the 64-bit class's multiply chains, zq_dev.h)
-template <int AR, bool WS = false>
+// L1: level 1 of the 64-bit class, whose X arrives in (0,2q) from from_i64_fwd: no conditional subtraction
+template <int AR, bool WS = false, bool L1 = false>
 __device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, const QKT<AR>& k) {
   if constexpr (AR == 3) {
     const u32 x = csub32(X, k.q);                     // [0,2q) -> [0,q)
@@ -255,7 +256,7 @@ __device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
 #ifdef LH_ABL_NO_FWD_CSUB
     const u64 x = X;                                  // timing-only ablation: results are garbage
 #else
-    const u64 x = csubn(X, k.nq4);                    // [0,8q) -> [0,4q)
+    const u64 x = L1 ? X : csubn(X, k.nq4);           // [0,8q) -> [0,4q)
 #endif
     const u64 xn = shoup_acc<WS>(Y, w, wp, k.nq, x);  // x + t, t in [0,4q)
     const u64 z = shl1_add64u(x, k.q4);                // 2x + 4q
@@ -346,11 +347,11 @@ template <int AR> __device__ __forceinline__ VT<AR> from_i64(i64 x, const QKT<AR
   else return canon_in(x, k.q);
 }
 // the same on the way INTO a forward transform, whose lazy range takes more than [0,q): one instruction.
-// 64-bit class: any value in [0,8q), and x + 4q is in (3q,5q) for every x in (-q,q) (one v_lshl_add_u64 instead
-// of a sign test and a masked add).  32-bit classes: x + q is in (0,2q), inside [0,2q) (class 3), [0,4q) (class 2)
+// 64-bit class: x + q is in (0,2q) for every x in (-q,q) (one v_lshl_add_u64 instead of a sign test and a masked
+// add), inside the [0,4q) a butterfly's X is trimmed to, so level 1 skips that trim (bfly_fwd L1).  32-bit classes: x + q is in (0,2q), inside [0,2q) (class 3), [0,4q) (class 2)
 // and the wide range of class 4 (inputs below 2q: 2q + 14 * 2q = 30q < 2^32 for q < 2^27).
 template <int AR> __device__ __forceinline__ VT<AR> from_i64_fwd(i64 x, const QKT<AR>& k) {
-  if constexpr (AR == 1) return add64u((u64)x, k.q4);
+  if constexpr (AR == 1) return add64u((u64)x, k.q);
   else if constexpr (AR >= 2) return (u32)x + k.q;
   else return from_i64<AR>(x, k);
 }
@@ -611,7 +612,7 @@ __device__ __forceinline__ void level(VT<AR> (&v)[E], const LevelTwT<VT<AR>>& t,
     const int s = level_tab<A, K>.slot[e];
     // a wave holds one polynomial component (so per-component constants are wave-uniform) from n = 1024 up
     constexpr bool WU = LOLHIP_WS && (A.ntb + R >= 10);
-    if constexpr (!INV) bfly_fwd<AR, WU && tw_uniform<A, K>()>(v[e], v[e | (1 << K)], t.w[s], t.wp[s], qk);
+    if constexpr (!INV) bfly_fwd<AR, WU && tw_uniform<A, K>(), beta == 0>(v[e], v[e | (1 << K)], t.w[s], t.wp[s], qk);
     else if constexpr (beta == 0) bfly_inv_last<AR, WU>(v[e], v[e | (1 << K)], tw.l1w, tw.l1wp, tw.sc0, tw.sc1, qk);
     else bfly_inv<AR, WU && tw_uniform<A, K>()>(v[e], v[e | (1 << K)], t.w[s], t.wp[s], qk);
   }
@@ -742,12 +743,13 @@ template <int L, bool W16 = false> struct Sched {
   static constexpr Lay final_layout() { return HAS_G ? g() : wave_end(); }
 };
 
-template <int AR, bool INV, Lay A, int K0>
+// K1: register bits K >= K1 carry no level (the truncated transforms of the fused poly-mul)
+template <int AR, bool INV, Lay A, int K0, int K1 = R>
 __device__ __forceinline__ void fetch4(LevelTwT<VT<AR>> (&t)[R], const TwCtxT<VT<AR>>& tw, int xt) {
-  if constexpr (K0 <= 0) tw_fetch<INV, A, 0>(t[0], tw, xt);
-  if constexpr (K0 <= 1) tw_fetch<INV, A, 1>(t[1], tw, xt);
-  if constexpr (K0 <= 2) tw_fetch<INV, A, 2>(t[2], tw, xt);
-  if constexpr (K0 <= 3) tw_fetch<INV, A, 3>(t[3], tw, xt);
+  if constexpr (K0 <= 0 && K1 > 0) tw_fetch<INV, A, 0>(t[0], tw, xt);
+  if constexpr (K0 <= 1 && K1 > 1) tw_fetch<INV, A, 1>(t[1], tw, xt);
+  if constexpr (K0 <= 2 && K1 > 2) tw_fetch<INV, A, 2>(t[2], tw, xt);
+  if constexpr (K0 <= 3 && K1 > 3) tw_fetch<INV, A, 3>(t[3], tw, xt);
 }
 // register-lean variant: fetch each level's twiddles right before the level (<= 32 VGPRs live)
 template <int AR, bool INV, Lay A, int K>
@@ -762,29 +764,32 @@ __device__ __forceinline__ void level_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& 
     LevelTw t; tw_fetch<INV, A, K>(t, tw, xt); level<AR, INV, A, K>(v, t, tw, qk);
   }
 }
-template <int AR, Lay A, int K0>
+template <int AR, Lay A, int K0, int K1 = R>
 __device__ __forceinline__ void levels4_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& tw, int xt, const QKT<AR>& qk) {
-  if constexpr (K0 <= 0) level_jit<AR, false, A, 0>(v, tw, xt, qk);
-  if constexpr (K0 <= 1) level_jit<AR, false, A, 1>(v, tw, xt, qk);
-  if constexpr (K0 <= 2) level_jit<AR, false, A, 2>(v, tw, xt, qk);
-  if constexpr (K0 <= 3) level_jit<AR, false, A, 3>(v, tw, xt, qk);
+  if constexpr (K0 <= 0 && K1 > 0) level_jit<AR, false, A, 0>(v, tw, xt, qk);
+  if constexpr (K0 <= 1 && K1 > 1) level_jit<AR, false, A, 1>(v, tw, xt, qk);
+  if constexpr (K0 <= 2 && K1 > 2) level_jit<AR, false, A, 2>(v, tw, xt, qk);
+  if constexpr (K0 <= 3 && K1 > 3) level_jit<AR, false, A, 3>(v, tw, xt, qk);
 }
-template <int AR, bool INV, Lay A, int K0>
+template <int AR, bool INV, Lay A, int K0, int K1 = R>
 __device__ __forceinline__ void levels4(VT<AR> (&v)[E], const LevelTwT<VT<AR>> (&t)[R], const TwCtxT<VT<AR>>& tw, const QKT<AR>& qk) {
   if constexpr (!INV) {
-    if constexpr (K0 <= 0) level<AR, false, A, 0>(v, t[0], tw, qk);
-    if constexpr (K0 <= 1) level<AR, false, A, 1>(v, t[1], tw, qk);
-    if constexpr (K0 <= 2) level<AR, false, A, 2>(v, t[2], tw, qk);
-    if constexpr (K0 <= 3) level<AR, false, A, 3>(v, t[3], tw, qk);
+    if constexpr (K0 <= 0 && K1 > 0) level<AR, false, A, 0>(v, t[0], tw, qk);
+    if constexpr (K0 <= 1 && K1 > 1) level<AR, false, A, 1>(v, t[1], tw, qk);
+    if constexpr (K0 <= 2 && K1 > 2) level<AR, false, A, 2>(v, t[2], tw, qk);
+    if constexpr (K0 <= 3 && K1 > 3) level<AR, false, A, 3>(v, t[3], tw, qk);
   } else {
-    if constexpr (K0 <= 3) level<AR, true, A, 3>(v, t[3], tw, qk);
-    if constexpr (K0 <= 2) level<AR, true, A, 2>(v, t[2], tw, qk);
-    if constexpr (K0 <= 1) level<AR, true, A, 1>(v, t[1], tw, qk);
-    if constexpr (K0 <= 0) level<AR, true, A, 0>(v, t[0], tw, qk);
+    if constexpr (K0 <= 3 && K1 > 3) level<AR, true, A, 3>(v, t[3], tw, qk);
+    if constexpr (K0 <= 2 && K1 > 2) level<AR, true, A, 2>(v, t[2], tw, qk);
+    if constexpr (K0 <= 1 && K1 > 1) level<AR, true, A, 1>(v, t[1], tw, qk);
+    if constexpr (K0 <= 0 && K1 > 0) level<AR, true, A, 0>(v, t[0], tw, qk);
   }
 }
 
 // forward transform; data arrives in registers in layout PREV, leaves in Sched<L>::final_layout().
+// TRUNC (L >= 11): stop after level L - 2.  The top two levels sit on register bits 2 and 3 of G
+// (for L = 11 the second of them is the lane-swap level on position bit 9), so the layouts and the
+// exchanges stay as they are and only butterflies and their twiddles drop out (pow2_base4 below).
 // LEAN: the caller keeps 32 more VGPRs live (a-hat during b's transform in the fused poly-mul),
 // so twiddles are fetched level by level instead of a pass ahead.
 // An opaque copy of a value: addresses derived from the copy cannot be CSE'd with (and kept
@@ -801,12 +806,15 @@ __device__ __forceinline__ int fresh(int x) {
 // order: a kernel that keeps an LDS-DMA in flight under a transform (pow2_pipe.hip) fetches these BEFORE it
 // issues the DMA, or the first such twiddle waits for the whole DMA to land.
 struct NoTop {};
-template <int AR, int L, Lay PREV, int SB = 0, bool LEAN = false, bool W16 = false, typename TOP = NoTop>
+template <int AR, int L, Lay PREV, int SB = 0, bool LEAN = false, bool W16 = false, typename TOP = NoTop, bool TRUNC = false>
 __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const QKT<AR>& qk,
                                               TOP* pre = nullptr) {
   constexpr bool PRE = !std::is_same_v<TOP, NoTop>;
   using LevelTw = LevelTwT<VT<AR>>;
   using S = Sched<L, W16>;
+  static_assert(!TRUNC || (L >= 11 && !PRE), "the truncated forward transform needs the G layout");
+  constexpr int GK1 = TRUNC ? 2 : R;                       // register bits of G with work
+  constexpr bool L10 = !(TRUNC && L == 11);                // level 10 (lane swap on bit 9) runs
   {   // W0: levels 1..4
     constexpr Lay A = S::w0();
     const int tau = fresh(tau_in);
@@ -836,7 +844,7 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       if constexpr (S::NSWAP >= 2) {
         lane_swap<5, 2>(v);
         if constexpr (PRE) { pre->wait_l10(); level<AR, false, S::w1b(), 2>(v, pre->l10, tw, qk); }
-        else level_jit<AR, false, S::w1b(), 2>(v, tw, xthr<S::w1b()>(tau), qk);
+        else if constexpr (L10) level_jit<AR, false, S::w1b(), 2>(v, tw, xthr<S::w1b()>(tau), qk);
       }
     } else {
       LevelTw t[R];
@@ -852,12 +860,12 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       if constexpr (S::NSWAP >= 1) tw_fetch<false, S::w1a(), 3>(ua, tw, xthr<S::w1a()>(tau));
       level<AR, false, A, 3>(v, t[3], tw, qk);
       LH_STAMP(SB + 5);
-      if constexpr (S::NSWAP >= 2 && !PRE) tw_fetch<false, S::w1b(), 2>(ub, tw, xthr<S::w1b()>(tau));
+      if constexpr (S::NSWAP >= 2 && !PRE && L10) tw_fetch<false, S::w1b(), 2>(ub, tw, xthr<S::w1b()>(tau));
       if constexpr (S::NSWAP >= 1) { lane_swap<4, 3>(v); level<AR, false, S::w1a(), 3>(v, ua, tw, qk); }
       if constexpr (S::NSWAP >= 2) {
         lane_swap<5, 2>(v);
         if constexpr (PRE) { pre->wait_l10(); level<AR, false, S::w1b(), 2>(v, pre->l10, tw, qk); }
-        else level<AR, false, S::w1b(), 2>(v, ub, tw, qk);
+        else if constexpr (L10) level<AR, false, S::w1b(), 2>(v, ub, tw, qk);
       }
       LH_STAMP(SB + 6);
     }
@@ -874,29 +882,33 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       LH_STAMP(SB + 8);
     } else if constexpr (LEAN) {
       transpose_get<S::wave_end(), A, true>(v, lds, tau);  // barrier, then read across blocks
-      levels4_jit<AR, A, S::G_K0>(v, tw, xthr<A>(tau), qk);
+      levels4_jit<AR, A, S::G_K0, GK1>(v, tw, xthr<A>(tau), qk);
     } else {
       LevelTw t[R];
-      fetch4<AR, false, A, S::G_K0>(t, tw, xthr<A>(tau));
+      fetch4<AR, false, A, S::G_K0, GK1>(t, tw, xthr<A>(tau));
       transpose_get<S::wave_end(), A, true>(v, lds, tau);
       LH_STAMP(SB + 7);
-      levels4<AR, false, A, S::G_K0>(v, t, tw, qk);
+      levels4<AR, false, A, S::G_K0, GK1>(v, t, tw, qk);
       LH_STAMP(SB + 8);
     }
   }
 }
 
-// inverse transform; data arrives in Sched<L>::final_layout(), leaves in layout NEXT
-template <int AR, int L, Lay NEXT, bool W16 = false>
+// inverse transform; data arrives in Sched<L>::final_layout(), leaves in layout NEXT.
+// TRUNC: start at level L - 2 (the mirror of the truncated forward transform)
+template <int AR, int L, Lay NEXT, bool W16 = false, bool TRUNC = false>
 __device__ __forceinline__ void inv_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const QKT<AR>& qk) {
   using LevelTw = LevelTwT<VT<AR>>;
   using S = Sched<L, W16>;
+  static_assert(!TRUNC || L >= 11, "the truncated inverse transform needs the G layout");
+  constexpr int GK1 = TRUNC ? 2 : R;
+  constexpr bool L10 = !(TRUNC && L == 11);
   if constexpr (S::HAS_G) {
     constexpr Lay A = S::g();
     const int tau = fresh(tau_in);
     LevelTw t[R];
-    fetch4<AR, true, A, S::G_K0>(t, tw, xthr<A>(tau));
-    levels4<AR, true, A, S::G_K0>(v, t, tw, qk);
+    fetch4<AR, true, A, S::G_K0, GK1>(t, tw, xthr<A>(tau));
+    levels4<AR, true, A, S::G_K0, GK1>(v, t, tw, qk);
     transpose_put<A, S::wave_end(), true>(v, lds, tau);    // barrier (earlier readers), write across blocks
   }
   if constexpr (S::HAS_W1) {
@@ -904,11 +916,11 @@ __device__ __forceinline__ void inv_transform(VT<AR> (&v)[E], VT<AR>* lds, const
     const int tau = fresh(tau_in);
     const int xt = xthr<A>(tau);
     LevelTw ua, ub, t[R];
-    if constexpr (S::NSWAP >= 2) tw_fetch<true, S::w1b(), 2>(ub, tw, xthr<S::w1b()>(tau));
+    if constexpr (S::NSWAP >= 2 && L10) tw_fetch<true, S::w1b(), 2>(ub, tw, xthr<S::w1b()>(tau));
     if constexpr (S::NSWAP >= 1) tw_fetch<true, S::w1a(), 3>(ua, tw, xthr<S::w1a()>(tau));
     if constexpr (S::NSWAP == 0) fetch4<AR, true, A, S::W1_K0>(t, tw, xt);
     if constexpr (S::HAS_G) transpose_get<S::g(), S::wave_end(), true>(v, lds, tau);   // barrier, read own block
-    if constexpr (S::NSWAP >= 2) { level<AR, true, S::w1b(), 2>(v, ub, tw, qk); lane_swap<5, 2>(v); }
+    if constexpr (S::NSWAP >= 2) { if constexpr (L10) level<AR, true, S::w1b(), 2>(v, ub, tw, qk); lane_swap<5, 2>(v); }
     if constexpr (S::NSWAP >= 1) {
       tw_fetch<true, A, 3>(t[3], tw, xt);
       level<AR, true, S::w1a(), 3>(v, ua, tw, qk);
@@ -932,19 +944,104 @@ __device__ __forceinline__ void inv_transform(VT<AR> (&v)[E], VT<AR>* lds, const
   }
 }
 
+// ---- base case of the truncated 61-bit fused poly-mul (AR = 1, L >= 11) -----------------------------------
+// After level L - 2 the positions x + N p (N = 2^(L-2), x < N, p = 0..3) hold coefficient bitrev2(p) of a residue
+// mod X^4 - zeta_x, zeta_x = psi^(4 (2x + 1)): the level-(L-2) twiddle of x mod N/2, negated for x >= N/2.  In G
+// those are register bits 2 (p bit 0) and 3 (p bit 1) of the four groups e = 0..3; bit 1 of e is position bit
+// L - 3 (the sign), the level-(L-2) twiddle is the one G's level on register bit 1 would read.
+// tests/test_trunc_model.py replays this route in integers and asserts every range below.
+
+// sum of four products x_i y_i of values below 2^62 (32-bit halves: hi < 2^30), as the 64-bit columns
+//   A = sum xh yh (< 2^62) plus the carries of C,  B1 = sum xl yh,  B2 = sum xh yl (each < 2^64),  C = sum xl yl mod 2^64
+// so that the sum is C + 2^32 (B1 + B2) + 2^64 A.  One block: gfx950 wants 2 wait states between a VALU write of a
+// carry SGPR and its read, which the independent mads in between provide; the other carries are never read.
+__device__ __forceinline__ void dot4_cols(const u64 (&x)[4], const u64 (&y)[4], u64& A, u64& B1, u64& B2, u64& C) {
+  u64 k1, k2, k3, sj;
+  u32 cnt;
+  asm("v_mad_u64_u32 %[C], %[sj], %[x0l], %[y0l], 0\n\t"
+      "v_mad_u64_u32 %[A], %[sj], %[x0h], %[y0h], 0\n\t"
+      "v_mad_u64_u32 %[B1], %[sj], %[x0l], %[y0h], 0\n\t"
+      "v_mad_u64_u32 %[C], %[k1], %[x1l], %[y1l], %[C]\n\t"
+      "v_mad_u64_u32 %[B2], %[sj], %[x0h], %[y0l], 0\n\t"
+      "v_mad_u64_u32 %[A], %[sj], %[x1h], %[y1h], %[A]\n\t"
+      "v_cndmask_b32_e64 %[cnt], 0, 1, %[k1]\n\t"
+      "v_mad_u64_u32 %[C], %[k2], %[x2l], %[y2l], %[C]\n\t"
+      "v_mad_u64_u32 %[B1], %[sj], %[x1l], %[y1h], %[B1]\n\t"
+      "v_mad_u64_u32 %[B2], %[sj], %[x1h], %[y1l], %[B2]\n\t"
+      "v_addc_co_u32_e64 %[cnt], %[sj], %[cnt], 0, %[k2]\n\t"
+      "v_mad_u64_u32 %[C], %[k3], %[x3l], %[y3l], %[C]\n\t"
+      "v_mad_u64_u32 %[A], %[sj], %[x2h], %[y2h], %[A]\n\t"
+      "v_mad_u64_u32 %[B1], %[sj], %[x2l], %[y2h], %[B1]\n\t"
+      "v_addc_co_u32_e64 %[cnt], %[sj], %[cnt], 0, %[k3]\n\t"
+      "v_mad_u64_u32 %[B2], %[sj], %[x2h], %[y2l], %[B2]\n\t"
+      "v_mad_u64_u32 %[A], %[sj], %[x3h], %[y3h], %[A]\n\t"
+      "v_mad_u64_u32 %[B1], %[sj], %[x3l], %[y3h], %[B1]\n\t"
+      "v_mad_u64_u32 %[B2], %[sj], %[x3h], %[y3l], %[B2]\n\t"
+      "v_mad_u64_u32 %[A], %[sj], %[cnt], 1, %[A]"
+      : [A] "=&v"(A), [B1] "=&v"(B1), [B2] "=&v"(B2), [C] "=&v"(C), [cnt] "=&v"(cnt),
+        [k1] "=&s"(k1), [k2] "=&s"(k2), [k3] "=&s"(k3), [sj] "=&s"(sj)
+      : [x0l] "v"(lo32(x[0])), [x0h] "v"(hi32(x[0])), [x1l] "v"(lo32(x[1])), [x1h] "v"(hi32(x[1])),
+        [x2l] "v"(lo32(x[2])), [x2h] "v"(hi32(x[2])), [x3l] "v"(lo32(x[3])), [x3h] "v"(hi32(x[3])),
+        [y0l] "v"(lo32(y[0])), [y0h] "v"(hi32(y[0])), [y1l] "v"(lo32(y[1])), [y1h] "v"(hi32(y[1])),
+        [y2l] "v"(lo32(y[2])), [y2h] "v"(hi32(y[2])), [y3l] "v"(lo32(y[3])), [y3h] "v"(hi32(y[3])));
+}
+// REDC of sum x_i y_i with x_i, y_i in [0,2q), q < 2^61: the sum T < 16 q^2, (T + m q) / 2^64 < 3q + 1 (as pmul)
+__device__ __forceinline__ u64 dot4_redc(const u64 (&x)[4], const u64 (&y)[4], const ModCtx& mc) {
+  u64 A, B1, B2, C;
+  dot4_cols(x, y, A, B1, B2, C);
+  const u64 u = (u64)hi32(C) + lo32(B1) + lo32(B2);            // column 1, < 3 2^32
+  const u64 lo = ((u64)lo32(u) << 32) | lo32(C);
+  const u64 hi = A + hi32(B1) + hi32(B2) + hi32(u);
+  return hi + __umul64hi(lo * mc.nqinv, mc.q) + (lo != 0);
+}
+// v: b-hat after level L - 2 (lazy, [0,8q)) in, c-hat 2^-64 (< 3q + 1, the inverse's range) out; va: a-hat parked in [0,2q)
+template <Lay G>
+__device__ __forceinline__ void pow2_base4(u64 (&v)[E], const u64 (&va)[E], const TwCtxT<u64>& tw, int xt, const ModCtx& mc, const QK& qk) {
+  LevelTwT<u64> z;
+  tw_fetch<false, G, 1>(z, tw, xt);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    constexpr int EK[4] = {0, 8, 4, 12};                           // coefficient k at register bits 2, 3 = bitrev2(k)
+    u64 zw = z.w[level_tab<G, 1>.slot[g & 1]], zwp = z.wp[level_tab<G, 1>.slot[g & 1]];
+    if (g & 2) { zw = qk.q - zw; zwp = ~zwp; }                    // Shoup pair of q - w: (q - w, 2^64 - 1 - wp)
+    // outputs in the order 3, 2, 1, 0: output k reads b_0..b_k and zeta b_(k+1)..zeta b_3, so each zeta b_j is made
+    // from b_j (any input: Shoup) right after b_j's last plain use, and four of them are live at a time
+    u64 a[4], y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      a[k] = va[g | EK[k]];
+      y[k] = csubn(csubn(v[g | EK[k]], qk.nq4), qk.nq2);           // b_k: [0,8q) -> [0,2q)
+    }
+#pragma unroll
+    for (int k = 3; k >= 0; --k) {
+      u64 x[4], w[4];                                                // output k = sum_i a_i w_i
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { x[i] = a[i]; w[i] = y[(k - i) & 3]; }
+      v[g | EK[k]] = dot4_redc(x, w, mc);
+      // materialised here: left to hipcc, the reductions sink past the LDS twiddle refill loop to their first use in
+      // the inverse and hold four 64-bit columns per output instead of one result (spills)
+      asm volatile("" : "+v"(v[g | EK[k]]));
+      if (k) y[k] = csubn(shoup_acc<false>(y[k], zw, zwp, qk.nq, 0), qk.nq2);   // zeta b_k in [0,2q)
+    }
+  }
+}
+
 constexpr int pow2_threads(int L) { return (1 << (L - R)) >= 256 ? (1 << (L - R)) : 256; }
 
 // MODE 0: crt in place, 1: crtInv in place, 2: c = crtInv(crt(a) * crt(b))
 // T1: the launch has a single modulus (T = 1) and 16-byte-aligned slabs: t = 0 for every lane even
 // when a wave holds several short polynomials — the per-modulus constants stay in SGPRs — and
 // global memory moves 16 bytes per lane (Sched<L, true>)
-template <int L, int MODE, int AR, bool T1 = false>
+// TR: the truncated route of the 61-bit fused poly-mul (MODE 2, AR 1, L >= 11): both forward transforms stop after
+// level L - 2, pow2_base4 multiplies the degree-3 residues, the inverse starts at level L - 2 with (n/4)^-1 2^64
+template <int L, int MODE, int AR, bool T1 = false, bool TR = false>
 __global__ void __launch_bounds__(pow2_threads(L), AR >= 2 ? 8 : 4)
 k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
        const VT<AR>* __restrict__ tw_fwd, const VT<AR>* __restrict__ tw_inv, const VT<AR>* __restrict__ scale,
        const ModCtx* __restrict__ mod, int xcd_map) {
   using S = Sched<L, T1>;
   using V = VT<AR>;
+  static_assert(!TR || (MODE == 2 && AR == 1 && L >= 11), "the truncated route is the 61-bit fused poly-mul's");
   constexpr int n = 1 << L;
   constexpr int NT = 1 << (L - R);                  // threads per polynomial
   constexpr int PPW = NT >= 256 ? 1 : 256 / NT;     // polynomials per workgroup
@@ -994,10 +1091,12 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
   // polynomial's own wave does both the fill and the reads.
   if constexpr (L >= TWL_MIN_L) tw_fill_lds<NT>(lds_tw, (MODE == 1) ? tw.inv : tw.fwd, tw.comp, n, tau);
   constexpr int SC = (MODE == 2 && AR == 1) ? 4 : 0;       // the 2^64-scaled pairs: see pmul
-  tw.sc0 = scale[(size_t)t * 8 + SC];
-  tw.sc1 = scale[(size_t)t * 8 + SC + 1];
-  tw.l1w = scale[(size_t)t * 8 + SC + 2];
-  tw.l1wp = scale[(size_t)t * 8 + SC + 3];
+  // the truncated route's (n/4)^-1 2^64 pairs follow the [T][8] block as [T][4] (plan.cpp)
+  const V* scp = TR ? scale + (size_t)T * 8 + (size_t)t * 4 : scale + (size_t)t * 8 + SC;
+  tw.sc0 = scp[0];
+  tw.sc1 = scp[1];
+  tw.l1w = scp[2];
+  tw.l1wp = scp[3];
 
   constexpr Lay LIO = S::io();              // global I/O of powerful-basis data
   constexpr Lay LFIN = S::final_layout();   // where the forward transform leaves the CRT coefficients
@@ -1020,7 +1119,7 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
     const rsrc_t src = (MODE == 2) ? ra : ry;
     load_poly<LIO, T1>(src, off_io, uT8, [&](int e, u64 x) { v[e] = from_i64_fwd<AR>((i64)x, qk); });
     LH_STAMP(1);
-    fwd_transform<AR, L, LIO, 0, false, T1>(v, lds, tw, tau, qk);
+    fwd_transform<AR, L, LIO, 0, false, T1, NoTop, TR>(v, lds, tw, tau, qk);
     if constexpr (MODE == 0) LH_STAMP(20);
   }
   if constexpr (MODE == 2) {
@@ -1029,7 +1128,12 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
     // both operands are fully read before the first store to c.
     V va[E];
 #pragma unroll
-    for (int e = 0; e < E; ++e) va[e] = park_fwd<AR>(v[e], qk);
+    for (int e = 0; e < E; ++e) {
+      va[e] = park_fwd<AR>(v[e], qk);
+      // the base case reads a-hat as 32-bit halves: without this hipcc sinks the selects of park_fwd into it and
+      // holds both operands of each across b's transform (32 more VGPRs: spills)
+      if constexpr (TR) asm volatile("" : "+v"(va[e]));
+    }
     LH_STAMP(9);
     const bool square = (a_in == b_in);
     if (!square) {
@@ -1043,12 +1147,16 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
 #pragma unroll
       for (int e = 0; e < E; ++e) v[e] = from_i64_fwd<AR>((i64)raw[e], qk);
       LH_STAMP(11);
-      fwd_transform<AR, L, LIO, 10, true, T1>(v, lds, tw, tau, qk);
+      fwd_transform<AR, L, LIO, 10, true, T1, NoTop, TR>(v, lds, tw, tau, qk);
     }
     LH_STAMP(19);
     const ModCtx mc = mod[t];     // re-read here: keeping it live across the transforms costs registers
+    if constexpr (TR) {
+      pow2_base4<LFIN>(v, va, tw, xthr<LFIN>(fresh(tau)), mc, qk);   // squaring: v still holds a-hat (lazy)
+    } else {
 #pragma unroll
-    for (int e = 0; e < E; ++e) v[e] = pmul<AR>(va[e], (AR < 2 && square) ? va[e] : v[e], mc, qk);   // squaring: v still holds a-hat (lazy)
+      for (int e = 0; e < E; ++e) v[e] = pmul<AR>(va[e], (AR < 2 && square) ? va[e] : v[e], mc, qk);   // squaring: v still holds a-hat (lazy)
+    }
     LH_STAMP(22);
   }
   if constexpr (MODE == 2 && L >= TWL_MIN_L) {
@@ -1065,7 +1173,7 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
     LH_STAMP(21);
   } else {
     LH_STAMP(23);
-    inv_transform<AR, L, LIO, T1>(v, lds, tw, tau, qk);
+    inv_transform<AR, L, LIO, T1, TR>(v, lds, tw, tau, qk);
     LH_STAMP(24);
     store_poly<LIO, T1>(ry, off_io, uT8, [&](int e) { return (u64)canon_inv<AR>(v[e], qk); });
     LH_STAMP(25);
@@ -1096,8 +1204,11 @@ static hipError_t kernel_dev_setup(KernelDev (&tab)[MAX_DEV], Setup&& setup) {
   return hipSuccess;
 }
 
-template <int L, int MODE, int AR, bool T1>
+template <int L, int MODE, int AR, bool T1, bool TR = false>
 static hipError_t launch_pow2_L(const Pow2Launch& a) {
+  if constexpr (MODE == 2 && AR == 1 && L >= 11 && !TR) {
+    if (a.trunc) return launch_pow2_L<L, MODE, AR, T1, true>(a);
+  }
   constexpr int n = 1 << L;
   constexpr int NT = 1 << (L - R);
   constexpr int PPW = NT >= 256 ? 1 : 256 / NT;
@@ -1110,12 +1221,12 @@ static hipError_t launch_pow2_L(const Pow2Launch& a) {
   if (lds_bytes > 64 * 1024) {
     static KernelDev tab[MAX_DEV];
     hipError_t e = kernel_dev_setup(tab, [&]() -> hipError_t {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pow2<L, MODE, AR, T1>),
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pow2<L, MODE, AR, T1, TR>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     });
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((k_pow2<L, MODE, AR, T1>), dim3((unsigned)grid), dim3(NT * PPW), lds_bytes, a.stream,
+  hipLaunchKernelGGL((k_pow2<L, MODE, AR, T1, TR>), dim3((unsigned)grid), dim3(NT * PPW), lds_bytes, a.stream,
                      a.y, a.a, a.b, a.B, a.T, static_cast<const VT<AR>*>(a.tw_fwd), static_cast<const VT<AR>*>(a.tw_inv),
                      static_cast<const VT<AR>*>(a.scale), a.mod, xcd_map);
   return hipGetLastError();
