@@ -351,6 +351,42 @@ LOLHIP_API int lolhip_tunnel_hint_batch(const lolhip_ext *x_er, const lolhip_ext
                                         double svar, int64_t base, const uint8_t key[32], uint64_t ctr,
                                         int64_t *hints_out, int64_t *work);
 
+/* key-homomorphic ring PRF of [BP14] (lol-apps KeyHomomorphicPRF.hs: buildDecTree, ringPRF'), one modulus q (T = 1).
+ * A family is a full binary tree of k leaves (1 <= k <= 62) and two 1 x L row vectors a0, a1 over R_q, L =
+ * lolhip_decompose_len(pq, base) (base 0 = TrivGad, b >= 2 = BaseBGad b, as for lolhip_decompose_batch).  For an input x:
+ *     A_leaf(x) = a_x (x in {0, 1});   A_(I c l r)(x) = A_l(x >> c_r) * G^-1(A_r(x & (2^c_r - 1)))   (c_r: leaves of r)
+ *   G^-1 = decomposeMatrix: column j of the L x L matrix holds the L digits of entry j, decomposed in the powerful basis
+ *   and reduced mod q, so A(x)_j = sum_i A_l(..)_i digit_i(A_r(..)_j).  The rightmost leaf reads bit 0 of x.
+ *     ringPRF s x = (rescaleDec . (s *)) <$> A_T(x):  y = fst (divModCent (p lift z) q) mod p per decoding-basis
+ *   coefficient z of s A_T(x)_j (lift centred; divModCent a q = floor((a + q div 2) / q)).
+ * lolhip_khprf_create: tree = the preorder list of leaf counts, 1 for a leaf, a node of count c > 1 followed by its left
+ *   and then its right subtree (I 3 L (I 2 L L) = {3,1,2,1,1}); a0_crt, a1_crt: HOST arrays [L][n] in the CRT basis.  On
+ *   a device plan it uploads a0, a1 and crt(G^-1(a0)), crt(G^-1(a1)) [L][L][n] each (allocates and synchronises; the
+ *   family belongs to the plan's device and must be destroyed before the plan).  A host-only plan makes a family that
+ *   only answers work_len.  LOLHIP_ERR_INVALID for a malformed tree, T != 1, an invalid base, NULL pointers;
+ *   LOLHIP_ERR_NO_CRT when q has no CRT basis for m — which is the case of the reference's own toy shapes over Zq 8.
+ * lolhip_khprf_work_len: the int64 scratch of both calls below over inputs [x0, x0 + B) (negative status on error).
+ *   Node v with c_v leaves and s_v leaves to its right sees (x >> s_v) & (2^c_v - 1), which takes
+ *   U_v = min(2^c_v, ((x0 + B - 1) >> s_v) - (x0 >> s_v) + 1) values over the range; each is computed once per call.  The
+ *   scratch is sum over internal nodes v (the root included) of U_v L n, plus sum over internal right children r of
+ *   L U_r L n (their digits); 0 for B = 0 or a one-leaf tree.
+ * lolhip_khprf_eval_batch: out [B][L][n] = A_T(x) for x = x0 .. x0 + B - 1, CRT basis (exact mod q).
+ * lolhip_khprf_batch: out [nkeys][B][L][n] = ringPRF s_key x, int64 in [0, p), decoding basis of R_p (lolhip_l_batch on a
+ *   plan mod p gives the powerful basis); s_crt [nkeys][n] on the device, CRT basis.  A_T is computed once for all keys.
+ * Status: LOLHIP_ERR_INVALID for x0 < 0, B < 0, x0 + B > 2^k, nkeys < 1, NULL pointers; LOLHIP_ERR_MODULUS for p < 2,
+ *   p >= q or p q >= 2^63 (the reference computes p lift z in Int64); LOLHIP_ERR_NO_DEVICE on a host-only plan;
+ *   LOLHIP_ERR_DEVICE when the calling thread's current device is not the plan's.  Every one is decided on the host
+ *   before any launch: the output is then not written.  No call synchronises or allocates. */
+typedef struct lolhip_khprf lolhip_khprf;
+LOLHIP_API int lolhip_khprf_create(const lolhip_plan *pq, int64_t base, const int32_t *tree, int ntree,
+                                   const int64_t *a0_crt, const int64_t *a1_crt, lolhip_khprf **out);
+LOLHIP_API void lolhip_khprf_destroy(lolhip_khprf *f);
+LOLHIP_API int64_t lolhip_khprf_work_len(const lolhip_khprf *f, int64_t x0, int64_t B);
+LOLHIP_API int lolhip_khprf_eval_batch(const lolhip_khprf *f, void *stream, int64_t x0, int64_t B, int64_t *out,
+                                       int64_t *work);
+LOLHIP_API int lolhip_khprf_batch(const lolhip_khprf *f, void *stream, const int64_t *s_crt, int nkeys, int64_t p,
+                                  int64_t x0, int64_t B, int64_t *out, int64_t *work);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

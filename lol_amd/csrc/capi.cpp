@@ -1033,4 +1033,5 @@ int capi_run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t*
 }
 int capi_do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse) { return do_crt(P, s, y, B, inverse); }
 int capi_divg_ok(const Plan& P) { return divg_ok(P); }
+int capi_make_decomp(const Plan& P, int64_t base, DecompParams& d) { return make_decomp(P, base, d); }
 }  // namespace lolhip

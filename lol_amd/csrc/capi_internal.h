@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "lolhip.h"
+#include "pipeline.h"
 #include "plan.h"
 
 struct lolhip_plan { lolhip::Plan P; };
@@ -18,4 +19,6 @@ int capi_run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t*
 int capi_do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse);
 // 1 when divG is possible modulo every q_t of the plan
 int capi_divg_ok(const Plan& P);
+// digit counts and the invariant-divisor constants of `base` over the plan's moduli (lolhip_decompose_batch's own)
+int capi_make_decomp(const Plan& P, int64_t base, DecompParams& d);
 }  // namespace lolhip

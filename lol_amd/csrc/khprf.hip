@@ -1,0 +1,184 @@
+// lol_amd/csrc/khprf.hip — the kernels of the key-homomorphic ring PRF of [BP14] (lol-apps KeyHomomorphicPRF.hs:
+// buildDecTree, ringPRF') that no other file provides.  gfx950 only.  One modulus (T = 1): slabs are [.][n] int64.
+//
+//   k_khprf_node    A_v = A_l * G^-1(A_r) for every slot of node v over an input window: out[k][j][c] =
+//                   sum_i L[slot_l(k)][i][c] * D[i][slot_r(k)][j][c] mod q, CRT basis, the slots derived in the kernel
+//                   from KhprfNode (by value)
+//   k_khprf_keymul  s_key * A for nkeys keys in one pass: [nkeys][B][ell][n], CRT basis
+//   k_khprf_round   rescaleDec to Z_p of decoding-basis residues, in place: fst (divModCent (p lift x) q) mod p
+//
+// The slot scheme (include/lolhip.h, lolhip_khprf_eval_batch): node v sees w_v = x >> s_v; its slot is w_v & (2^c_v - 1)
+// when every one of the 2^c_v sub-inputs occurs in the window ("full") and w_v - (x0 >> s_v) otherwise.  Slot k of v
+// stands for w_v = k (full) or (x0 >> s_v) + k, and its children's prefixes are w_v >> (s_child - s_v).  When the
+// right child r is full, slots k, k + 2^c_r, k + 2 * 2^c_r, ... have one right slot: a thread takes KG of them, so
+// each D word it loads serves KG left slots (and each L word JG entries) from registers.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "pipeline.h"
+#include "zq_dev.h"
+
+namespace lolhip {
+
+namespace {
+constexpr int TPB = 256;
+constexpr int KG = 4;          // slots of v per thread that share one right slot
+constexpr int JG = 4;          // output entries per thread
+constexpr i64 MAX_BLOCKS = 1 << 20;
+typedef unsigned __int128 u128;
+
+__device__ __forceinline__ i64 child_slot(i64 w_v, const KhprfChild& ch) {
+  const i64 w = w_v >> ch.shift;
+  return ch.full ? (w & ch.mask) : w - ch.lo;
+}
+
+unsigned grid_for(i64 total) {
+  const i64 b = (total + TPB - 1) / TPB;
+  return (unsigned)(b < 1 ? 1 : (b < MAX_BLOCKS ? b : MAX_BLOCKS));
+}
+}  // namespace
+
+// ---------------------------------------------------------------------------------------
+// One thread per (coefficient c, group of JG entries, group of KG slots sharing a right slot): acc[KG][JG] over the ell
+// digits.  Q32 (q < 2^32): 32x32-bit products into 64-bit sums, folded (Barrett, mu = floor(2^64/q)) every `fold` digits,
+// fold (q - 1)^2 + q < 2^64 (the knapsack's q32 bound, per modulus).  Otherwise 128-bit sums folded every 8 digits
+// (each term < q^2 < 2^124).  Threads are ordered c fastest, then the entry group, then the slot group: a wave reads
+// 64 consecutive coefficients of one row, and the waves that read the same L rows are neighbours.
+// ---------------------------------------------------------------------------------------
+template <bool Q32>
+__global__ void __launch_bounds__(TPB)
+k_khprf_node(const i64* __restrict__ Lv, const i64* __restrict__ D, i64* __restrict__ out, KhprfNode nd, ModCtx mc,
+             int fold, i64 nT, i64 nJ, i64 total) {
+  const i64 n = nd.n, ln = (i64)nd.ell * n;
+  for (i64 g = (i64)blockIdx.x * TPB + threadIdx.x; g < total; g += (i64)gridDim.x * TPB) {
+    const i64 tile = g / n, c = g - tile * n;
+    const i64 kq = tile / nJ, jg = tile - kq * nJ;
+    const i64 k0 = kq / nT, tg = kq - k0 * nT;
+    const i64 kb = k0 + tg * KG * nd.R;                         // first slot of the group
+    if (kb >= nd.U) continue;
+    const i64 wb = nd.full ? kb : nd.lo + kb;
+    const i64* dp = D + child_slot(wb, nd.r) * ln + c;         // right slot: one for the whole group
+    const i64* lp[KG];
+    bool kok[KG];
+#pragma unroll
+    for (int t = 0; t < KG; ++t) {
+      const i64 k = kb + t * nd.R;
+      kok[t] = k < nd.U;
+      const i64 w = (nd.full ? 0 : nd.lo) + (kok[t] ? k : kb);  // a slot past U repeats the first one (not stored)
+      lp[t] = Lv + child_slot(w, nd.l) * ln + c;
+    }
+    int jc[JG];
+#pragma unroll
+    for (int jj = 0; jj < JG; ++jj) {
+      const int j = (int)jg * JG + jj;
+      jc[jj] = j < nd.ell ? j : nd.ell - 1;                     // an entry past ell repeats the last one (not stored)
+    }
+    using Acc = std::conditional_t<Q32, u64, u128>;
+    Acc acc[KG][JG];
+#pragma unroll
+    for (int t = 0; t < KG; ++t)
+#pragma unroll
+      for (int jj = 0; jj < JG; ++jj) acc[t][jj] = 0;
+    auto red = [&](Acc a) -> u64 {
+      if constexpr (Q32) {
+        const u64 r = a - __umul64hi(a, mc.mu) * mc.q;          // [0, 2q)
+        return r >= mc.q ? r - mc.q : r;
+      } else {
+        return reduce128((u64)(a >> 64), (u64)a, mc);
+      }
+    };
+    for (int i0 = 0; i0 < nd.ell; i0 += fold) {
+      const int i1 = i0 + fold < nd.ell ? i0 + fold : nd.ell;
+      for (int i = i0; i < i1; ++i) {
+        u64 d[JG], a[KG];
+#pragma unroll
+        for (int jj = 0; jj < JG; ++jj) d[jj] = (u64)dp[i * nd.d_digit + (i64)jc[jj] * n];
+#pragma unroll
+        for (int t = 0; t < KG; ++t) a[t] = (u64)lp[t][(i64)i * n];
+#pragma unroll
+        for (int t = 0; t < KG; ++t)
+#pragma unroll
+          for (int jj = 0; jj < JG; ++jj) {
+            if constexpr (Q32) acc[t][jj] += (u64)(u32)a[t] * (u32)d[jj];
+            else acc[t][jj] += (u128)a[t] * d[jj];
+          }
+      }
+#pragma unroll
+      for (int t = 0; t < KG; ++t)
+#pragma unroll
+        for (int jj = 0; jj < JG; ++jj) acc[t][jj] = red(acc[t][jj]);
+    }
+#pragma unroll
+    for (int t = 0; t < KG; ++t) {
+      if (!kok[t]) continue;
+      i64* o = out + (kb + t * nd.R) * ln + c;
+#pragma unroll
+      for (int jj = 0; jj < JG; ++jj)
+        if ((int)jg * JG + jj < nd.ell) o[(i64)((int)jg * JG + jj) * n] = (i64)acc[t][jj];
+    }
+  }
+}
+
+hipError_t launch_khprf_node(hipStream_t s, const i64* L, const i64* D, i64* out, const KhprfNode& nd, const ModCtx& mc,
+                             int fold) {
+  if (nd.U <= 0 || nd.ell <= 0 || nd.n <= 0) return hipSuccess;
+  if (nd.R < 1 || fold < 1) return hipErrorInvalidValue;
+  const i64 nk0 = nd.R < nd.U ? nd.R : nd.U;
+  const i64 per = (nd.U + nd.R - 1) / nd.R;                     // slots per right slot
+  const i64 nT = (per + KG - 1) / KG, nJ = (nd.ell + JG - 1) / JG;
+  const i64 total = nk0 * nT * nJ * nd.n;
+  const bool q32 = mc.q < ((u64)1 << 32);
+  if (q32) hipLaunchKernelGGL(k_khprf_node<true>, dim3(grid_for(total)), dim3(TPB), 0, s, L, D, out, nd, mc, fold, nT, nJ, total);
+  else hipLaunchKernelGGL(k_khprf_node<false>, dim3(grid_for(total)), dim3(TPB), 0, s, L, D, out, nd, mc, 8, nT, nJ, total);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// out[key][r] = s[key][r % n] * A[r] mod q, r over the B*ell*n words of A: the nkeys products in one pass (A is read
+// once per key, from L2 after the first)
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(TPB)
+k_khprf_keymul(const i64* __restrict__ A, const i64* __restrict__ s_crt, i64* __restrict__ out, i64 per, i64 n,
+               i64 total, ModCtx mc) {
+  for (i64 g = (i64)blockIdx.x * TPB + threadIdx.x; g < total; g += (i64)gridDim.x * TPB) {
+    const i64 key = g / per, r = g - key * per;
+    const i64 c = r % n;
+    out[g] = (i64)mulmod(canon_in(s_crt[key * n + c], mc.q), canon_in(A[r], mc.q), mc);
+  }
+}
+
+hipError_t launch_khprf_keymul(hipStream_t s, const i64* A, const i64* s_crt, i64* out, i64 nkeys, i64 rows, i64 n,
+                               const ModCtx& mc) {
+  const i64 per = rows * n, total = nkeys * per;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_khprf_keymul, dim3(grid_for(total)), dim3(TPB), 0, s, A, s_crt, out, per, n, total, mc);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// rescaleMod (Prelude.hs:144-153) of every word, in place: v = lift x (centred, q odd), y = floor((p v + q div 2) / q)
+// mod p.  Shifted by p q to stay unsigned: a = p (v + q) + q div 2 < 1.5 p q + q / 2 < 2^64 (p q < 2^63, q < 2^62), the
+// quotient floor(a / q) < 2p is exact through q^-1 mod 2^64 once the remainder is off, and equals y + p mod p.
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(TPB)
+k_khprf_round(i64* __restrict__ y, i64 total, u64 p, ModCtx mc, u64 qinv) {
+  const u64 q = mc.q;
+  for (i64 g = (i64)blockIdx.x * TPB + threadIdx.x; g < total; g += (i64)gridDim.x * TPB) {
+    const u64 x = canon_in(y[g], q);
+    const u64 vq = 2 * x < q ? x + q : x;                       // lift x + q, in (q/2, 3q/2)
+    const u64 a = p * vq + (q >> 1);
+    const u64 quot = (a - rem128(0, a, mc)) * qinv;
+    y[g] = (i64)(quot >= p ? quot - p : quot);
+  }
+}
+
+hipError_t launch_khprf_round(hipStream_t s, i64* y, i64 total, i64 p, const ModCtx& mc) {
+  if (total == 0) return hipSuccess;
+  if (!(mc.q & 1) || p < 2) return hipErrorInvalidValue;
+  const u64 qinv = 0 - mc.nqinv;                                // q^-1 mod 2^64
+  hipLaunchKernelGGL(k_khprf_round, dim3(grid_for(total)), dim3(TPB), 0, s, y, total, (u64)p, mc, qinv);
+  return hipGetLastError();
+}
+
+}  // namespace lolhip

@@ -76,4 +76,31 @@ hipError_t launch_kshint_combine(hipStream_t s, const i64* e_crt, const i64* val
 // out [rel][n][T]: the powerful-basis unit vector at coeffs[i * n_lo] for row i (0 / 1 residues)
 hipError_t launch_unit_rows(hipStream_t s, i64* out, const int32_t* coeffs, i64 rel, i64 n, int T, i64 n_lo);
 
+// khprf.hip: the key-homomorphic ring PRF (lol-apps KeyHomomorphicPRF.hs), one modulus.  A child of node v as the node
+// kernel sees it: its prefix is w_v >> shift, its slot w & mask when full, else w - lo (a leaf: full, mask 1)
+struct KhprfChild {
+  i64 lo;                      // x0 >> s_child
+  i64 mask;                    // 2^c_child - 1
+  int full;                    // the child's slots are its sub-inputs
+  int shift;                   // s_child - s_v
+};
+struct KhprfNode {
+  i64 U;                       // slots of v
+  i64 lo;                      // x0 >> s_v
+  int full;                    // U = 2^c_v: slot k stands for w_v = k, else for lo + k
+  int ell;                     // gadget length
+  i64 n;                       // coefficients per polynomial
+  i64 R;                       // slots k, k + R, ... share one right slot (2^c_r for a full right child, else U)
+  i64 d_digit;                 // stride of digit i in D = [ell][U_r][ell][n]: U_r * ell * n
+  KhprfChild l, r;
+};
+// out [U][ell][n] = L [U_l][ell][n] x D [ell][U_r][ell][n] per slot, CRT basis; fold: Q32 digits per 64-bit sum
+hipError_t launch_khprf_node(hipStream_t s, const i64* L, const i64* D, i64* out, const KhprfNode& nd, const ModCtx& mc,
+                             int fold);
+// out [nkeys][rows][n] = s_crt [key][n] * A [rows][n], CRT basis
+hipError_t launch_khprf_keymul(hipStream_t s, const i64* A, const i64* s_crt, i64* out, i64 nkeys, i64 rows, i64 n,
+                               const ModCtx& mc);
+// y = fst (divModCent (p lift y) q) mod p in place (rescaleMod, q odd, p q < 2^63)
+hipError_t launch_khprf_round(hipStream_t s, i64* y, i64 total, i64 p, const ModCtx& mc);
+
 }  // namespace lolhip

@@ -117,6 +117,13 @@ def lib():
     L.lolhip_tunnel_hint_work_len.argtypes = [vp, vp, i64]
     L.lolhip_tunnel_hint_work_len.restype = i64
     L.lolhip_tunnel_hint_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, i64, C.c_char_p, C.c_uint64, vp, vp]
+    L.lolhip_khprf_create.argtypes = [vp, i64, _i32p, ci, _i64p, _i64p, C.POINTER(vp)]
+    L.lolhip_khprf_destroy.argtypes = [vp]
+    L.lolhip_khprf_destroy.restype = None
+    L.lolhip_khprf_work_len.argtypes = [vp, i64, i64]
+    L.lolhip_khprf_work_len.restype = i64
+    L.lolhip_khprf_eval_batch.argtypes = [vp, vp, i64, i64, vp, vp]
+    L.lolhip_khprf_batch.argtypes = [vp, vp, vp, ci, i64, i64, i64, vp, vp]
     L.lolhip_chacha20_block.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.lolhip_chacha20_block.restype = None
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
@@ -916,3 +923,96 @@ class Ext:
     def embedPow(self, x, out=None, stream=None): return self._run(EXT_EMBED_POW, "embed_pow", x, True, out, stream)
     def embedDec(self, x, out=None, stream=None): return self._run(EXT_EMBED_DEC, "embed_dec", x, True, out, stream)
     def embedCRT(self, x, out=None, stream=None): return self._run(EXT_EMBED_CRT, "embed_crt", x, True, out, stream)
+
+
+# ---- key-homomorphic ring PRF (lol-apps KeyHomomorphicPRF.hs) -------------------------------
+# Trees are preorder lists of leaf counts: 1 for a leaf, a node of c > 1 leaves followed by its left, then its right
+# subtree (I 3 L (I 2 L L) = [3, 1, 2, 1, 1]).
+
+def left_spine_tree(k):
+    """leftSpineTree k (KeyHomomorphicPRF.hs): I k (leftSpineTree (k-1)) L"""
+    return [1] if k == 1 else [k] + left_spine_tree(k - 1) + [1]
+
+
+def right_spine_tree(k):
+    """rightSpineTree k: I k L (rightSpineTree (k-1))"""
+    return [1] if k == 1 else [k, 1] + right_spine_tree(k - 1)
+
+
+def balanced_tree(k):
+    """balancedTree k: the left subtree takes min(2^floor(log2 k), k - 2^floor(log2 k) / 2) leaves"""
+    if k == 1:
+        return [1]
+    full = 1 << (k.bit_length() - 1)
+    lsize = min(full, k - full // 2)
+    return [k] + balanced_tree(lsize) + balanced_tree(k - lsize)
+
+
+def gray_code(k):
+    """grayCode k: the (k-1)-bit code, then its reverse with bit k-1 set"""
+    if k == 1:
+        return [0, 1]
+    g = gray_code(k - 1)
+    return g + [x + (1 << (k - 1)) for x in reversed(g)]
+
+
+class KHPRF:
+    """A family of the key-homomorphic ring PRF of [BP14] over a one-modulus plan (lolhip_khprf_create): a full binary
+    tree (preorder leaf counts) and a0, a1 [L][n] in the CRT basis, L = plan.decomposeLen(base).  On a device plan a0,
+    a1 and their crt'd gadget decompositions go to HBM once; a host-only plan answers workLen only."""
+
+    def __init__(self, plan: Plan, base, tree, a0, a1):
+        self.plan, self.base = plan, int(base)
+        self.tree = [int(c) for c in tree]
+        self.L = plan.decomposeLen(base) if plan.T == 1 else 0
+        a0 = np.ascontiguousarray(np.asarray(a0, dtype=np.int64).reshape(-1))
+        a1 = np.ascontiguousarray(np.asarray(a1, dtype=np.int64).reshape(-1))
+        if a0.size != self.L * plan.n or a1.size != self.L * plan.n:
+            raise ValueError("a0 and a1 must be [L][n]")
+        tr = (C.c_int32 * max(1, len(self.tree)))(*self.tree)
+        h = C.c_void_p()
+        _check(lib().lolhip_khprf_create(plan._h, self.base, tr, len(self.tree), a0.ctypes.data_as(_i64p),
+                                         a1.ctypes.data_as(_i64p), C.byref(h)), f"khprf_create(tree={self.tree})")
+        self._h = h
+        self.k = self.tree[0]
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.lolhip_khprf_destroy(h)
+
+    def workLen(self, x0, B):
+        w = lib().lolhip_khprf_work_len(self._h, int(x0), int(B))
+        _check(min(w, 0))
+        return w
+
+    def eval(self, x0, B, stream=None):
+        """A_T(x) for x = x0 .. x0 + B - 1: a CUDA tensor [B][L][n] in the CRT basis (lolhip_khprf_eval_batch)."""
+        import torch
+        L = lib()
+        _check(L.lolhip_khprf_eval_batch(self._h, None, int(x0), 0, None, None))      # the host statuses first
+        if int(x0) + int(B) > (1 << self.k) or int(B) < 0:
+            _check(ERR_INVALID, "x0 + B > 2^k")
+        work = torch.empty((max(self.workLen(x0, B), 1),), dtype=torch.int64, device="cuda")
+        out = torch.empty((int(B), self.L, self.plan.n), dtype=torch.int64, device="cuda")
+        _check(L.lolhip_khprf_eval_batch(self._h, _stream(stream), int(x0), int(B), _devptr(out), _devptr(work)))
+        return out
+
+    def __call__(self, s, p, x0, B, stream=None):
+        """ringPRF s x for x = x0 .. x0 + B - 1 (lolhip_khprf_batch): s [n] or [nkeys][n] in the CRT basis (numpy or a
+        CUDA tensor) -> [nkeys][B][L][n] int64 in [0, p), decoding basis of R_p ([B][L][n] for a single key s [n])."""
+        import torch
+        L = lib()
+        single = len(s.shape) == 1
+        nkeys = 1 if single else int(s.shape[0])
+        _check(L.lolhip_khprf_batch(self._h, None, None, nkeys, int(p), int(x0), 0, None, None))
+        if int(x0) + int(B) > (1 << self.k) or int(B) < 0:
+            _check(ERR_INVALID, "x0 + B > 2^k")
+        if isinstance(s, np.ndarray):
+            s = torch.from_numpy(np.ascontiguousarray(s, dtype=np.int64)).cuda()
+        s = s.reshape(nkeys, self.plan.n).contiguous()
+        work = torch.empty((max(self.workLen(x0, B), 1),), dtype=torch.int64, device=s.device)
+        out = torch.empty((nkeys, int(B), self.L, self.plan.n), dtype=torch.int64, device=s.device)
+        _check(L.lolhip_khprf_batch(self._h, _stream(stream), _devptr(s), nkeys, int(p), int(x0), int(B), _devptr(out),
+                                    _devptr(work)))
+        return out[0] if single else out

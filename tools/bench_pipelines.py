@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """tools/bench_pipelines.py — throughput of the SymmSHE pipeline kernels on one MI355X
 (BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone), of encrypt / errorRounded
-(`--encrypt`: that leg alone) and of the key-switch / tunnel hints (`--kshint`: that leg alone).  Operands resident in HBM, HIP events on
+(`--encrypt`: that leg alone), of the key-switch / tunnel hints (`--kshint`: that leg alone) and of the key-homomorphic
+ring PRF (`--khprf`: that leg alone).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -175,6 +176,68 @@ def kshint_leg(gen):
                rel * nL * 2 * PS.n * PS.T * 8)
 
 
+def khprf_node_bytes(tree, nL, n, x0, B):
+    """compulsory bytes of the k_khprf_node launches of one eval over [x0, x0 + B): per internal node its left values
+    [U_l][L][n] and right digits [L][U_r][L][n] read once, its [U_v][L][n] written once (int64)"""
+    tot = 0
+
+    def U(c, s, leaf):
+        return 2 if leaf else min(2 ** c, ((x0 + B - 1) >> s) - (x0 >> s) + 1)
+
+    def rec(pos, s):                    # -> (next pos, leaves)
+        c = tree[pos]
+        if c == 1:
+            return pos + 1, 1
+        nonlocal tot
+        lpos = pos + 1
+        cr = c - tree[lpos]             # the left child's leaf count is the next entry
+        nxt, _ = rec(lpos, s + cr)
+        nxt2, _ = rec(nxt, s)
+        ul = U(tree[lpos], s + cr, tree[lpos] == 1)
+        ur = U(cr, s, tree[nxt] == 1)
+        uv = B if pos == 0 else U(c, s, False)
+        tot += (ul * nL * n + nL * ur * nL * n + uv * nL * n) * 8
+        return nxt2, c
+
+    if len(tree) > 1:
+        rec(0, 0)
+    return tot
+
+
+def khprf_leg(gen):
+    """The key-homomorphic ring PRF (lolhip_khprf_eval_batch, lolhip_khprf_batch).  The reference's benchmark shape
+    (KHPRFBenches.hs: 5 leaves, left / balanced / right trees, all 32 inputs, BaseBGad 2) at m = 128 with q = 257, p = 32
+    of Examples/KHPRF.hs, and one throughput shape: m = 2^11, q ~ 2^30, BaseBGad 2 (L = 30), a balanced 12-leaf tree,
+    B = 4096.  alg_bytes: what the node kernels must move (khprf_node_bytes) for eval, plus the [nkeys][B][L][n]
+    output written and read once more for batch.  The split between digit crt, k_khprf_node and the final passes is
+    read from a kernel trace of this leg."""
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    q30 = lol_amd.good_q(2 ** 11, 2 ** 29)
+    for label, m, q, p, base, trees, B in (
+            ("m=128 q=257 p=32 k=5", 128, 257, 32, 2,
+             (("left", lol_amd.left_spine_tree(5)), ("balanced", lol_amd.balanced_tree(5)),
+              ("right", lol_amd.right_spine_tree(5))), 32),
+            (f"m=2^11 q={q30} p=2^10 k=12", 2 ** 11, q30, 2 ** 10, 2, (("balanced", lol_amd.balanced_tree(12)),), 4096)):
+        P = lol_amd.Plan.for_index(m, [q])
+        nL = P.decomposeLen(base)
+        g = np.random.default_rng(0)
+        a0, a1 = (g.integers(0, q, size=(nL, P.n), dtype=np.int64) for _ in range(2))
+        s = torch.randint(0, q, (1, P.n), dtype=torch.int64, device="cuda", generator=gen)
+        for tname, tree in trees:
+            f = lol_amd.KHPRF(P, base, tree, a0, a1)
+            work = torch.empty((max(f.workLen(0, B), 1),), dtype=torch.int64, device="cuda")
+            out = torch.empty((B, nL, P.n), dtype=torch.int64, device="cuda")
+            nb = khprf_node_bytes(tree, nL, P.n, 0, B)
+            cfg = f"{label} {tname} base={base} L={nL} B={B}"
+            ms = timeit(lambda: L.lolhip_khprf_eval_batch(f._h, st, 0, B, ptr(out), ptr(work)))
+            report("khprf_eval", cfg, ms, B, nb, note="items = inputs; alg = node kernels' compulsory bytes")
+            ms = timeit(lambda: L.lolhip_khprf_batch(f._h, st, ptr(s), 1, p, 0, B, ptr(out), ptr(work)))
+            report("khprf_prf", cfg + " nkeys=1", ms, B, nb + B * nL * P.n * 8 * 2)
+            del work, out, f
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
     if "--decrypt" in sys.argv:          # the decrypt leg alone
@@ -185,6 +248,9 @@ def main():
         return
     if "--kshint" in sys.argv:           # the key-switch / tunnel hint leg alone
         kshint_leg(gen)
+        return
+    if "--khprf" in sys.argv:            # the key-homomorphic PRF leg alone
+        khprf_leg(gen)
         return
     L = lol_amd.lib()
     st = torch.cuda.current_stream().cuda_stream
