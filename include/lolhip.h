@@ -364,7 +364,8 @@ LOLHIP_API int lolhip_tunnel_hint_batch(const lolhip_ext *x_er, const lolhip_ext
  *   a device plan it uploads a0, a1 and crt(G^-1(a0)), crt(G^-1(a1)) [L][L][n] each (allocates and synchronises; the
  *   family belongs to the plan's device and must be destroyed before the plan).  A host-only plan makes a family that
  *   only answers work_len.  LOLHIP_ERR_INVALID for a malformed tree, T != 1, an invalid base, NULL pointers;
- *   LOLHIP_ERR_NO_CRT when q has no CRT basis for m — which is the case of the reference's own toy shapes over Zq 8.
+ *   LOLHIP_ERR_NO_CRT when q has no CRT basis for m — which is the case of the reference's own toy shapes over Zq 8:
+ *   those take lolhip_khprf_create_lifted below.
  * lolhip_khprf_work_len: the int64 scratch of both calls below over inputs [x0, x0 + B) (negative status on error).
  *   Node v with c_v leaves and s_v leaves to its right sees (x >> s_v) & (2^c_v - 1), which takes
  *   U_v = min(2^c_v, ((x0 + B - 1) >> s_v) - (x0 >> s_v) + 1) values over the range; each is computed once per call.  The
@@ -386,6 +387,29 @@ LOLHIP_API int lolhip_khprf_eval_batch(const lolhip_khprf *f, void *stream, int6
                                        int64_t *work);
 LOLHIP_API int lolhip_khprf_batch(const lolhip_khprf *f, void *stream, const int64_t *s_crt, int nkeys, int64_t p,
                                   int64_t x0, int64_t B, int64_t *out, int64_t *work);
+
+/* The lifted family: the same PRF over q = 2^k, which has no CRT basis (the reference's own Zq 8 -> Zq 2 over F128, and
+ * HomomPRF's ZP = Zq 8).  pq: a one-modulus plan mod q = 2^k (1 <= k); pQ: a one-modulus plan of the same index (the
+ * same prime powers in the same order) over an NTT-friendly prime Q (lolhip_good_q); a0_pow, a1_pow: HOST arrays [L][n]
+ * in the POWERFUL basis (any int64, taken mod q), L = lolhip_decompose_len(pq, base).
+ *   Every node product sum_i L_i digit_i is computed exactly over the integers in the CRT basis mod Q, then crtInv,
+ *   centred lift mod Q, reduced mod q, and lifted (centred, [-q/2, q/2)) and crt'd again where the next product needs
+ *   it; decompose and lInv run on pq.  Creation certifies exactness: with C_m = max_k sum_{i,j} |(b_i b_j)_k| over the
+ *   powerful basis b (n for m = 2^e, a product over the prime powers of m), L C_m (q/2) max|digit| < Q/2 and
+ *   C_m (q/2)^2 < Q/2 (the key product of ringPRF); max|digit| is q/2 under TrivGad, else the larger of b/2 and the
+ *   last centred digit's range.
+ * lolhip_khprf_create_lifted: LOLHIP_ERR_INVALID as for lolhip_khprf_create, and for plans of different indices;
+ *   LOLHIP_ERR_MODULUS when q is not a power of two or the bound above does not hold; LOLHIP_ERR_NO_CRT when Q has no
+ *   CRT basis.  Uploads as lolhip_khprf_create does (both plans must be device plans of the same device; either one
+ *   host-only makes a host-only family); the family must be destroyed before either plan.
+ * lolhip_khprf_work_len, lolhip_khprf_eval_batch and lolhip_khprf_batch take the lifted family unchanged, except:
+ *   eval_batch writes A_T(x) as residues in [0, q) in the POWERFUL basis (there is no CRT basis mod q);
+ *   batch takes s_crt [nkeys][n] as the centred lift of s in R_q, reduced mod Q, in the CRT basis mod Q (crt on pQ);
+ *   the rounding is y = ((p lift z + q/2) >> k) mod p, the same rescaleMod over q = 2^k.  The statuses are the same
+ *   (p >= q and p q >= 2^63 give LOLHIP_ERR_MODULUS); LOLHIP_ERR_NO_DEVICE when either plan is host-only. */
+LOLHIP_API int lolhip_khprf_create_lifted(const lolhip_plan *pq, const lolhip_plan *pQ, int64_t base,
+                                          const int32_t *tree, int ntree, const int64_t *a0_pow,
+                                          const int64_t *a1_pow, lolhip_khprf **out);
 
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */

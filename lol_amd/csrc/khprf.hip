@@ -6,6 +6,9 @@
 //                   from KhprfNode (by value)
 //   k_khprf_keymul  s_key * A for nkeys keys in one pass: [nkeys][B][ell][n], CRT basis
 //   k_khprf_round   rescaleDec to Z_p of decoding-basis residues, in place: fst (divModCent (p lift x) q) mod p
+//   k_khprf_lift    the lifted family (q = 2^k, products exact mod an NTT prime Q): Z_Q -> Z_q (centred lift, mod q),
+//                   Z_q -> Z_Q (centred lift) or both, and the 2-power rescaleMod to Z_p fused behind the first; two
+//                   words per thread, 16-byte accesses
 //
 // The slot scheme (include/lolhip.h, lolhip_khprf_eval_batch): node v sees w_v = x >> s_v; its slot is w_v & (2^c_v - 1)
 // when every one of the 2^c_v sub-inputs occurs in the window ("full") and w_v - (x0 >> s_v) otherwise.  Slot k of v
@@ -178,6 +181,79 @@ hipError_t launch_khprf_round(hipStream_t s, i64* y, i64 total, i64 p, const Mod
   if (!(mc.q & 1) || p < 2) return hipErrorInvalidValue;
   const u64 qinv = 0 - mc.nqinv;                                // q^-1 mod 2^64
   hipLaunchKernelGGL(k_khprf_round, dim3(grid_for(total)), dim3(TPB), 0, s, y, total, (u64)p, mc, qinv);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// The lifted family's pass over powerful-basis (or decoding-basis) words, two per thread:
+//   LIFT_FROM_Q  x in [0, Q) -> v = lift_Q x (centred) -> r = v mod q (q = 2^k: the low k bits), else r = x mod q
+//   LIFT_TO_Q    r -> lift_q r in [-q/2, q/2) -> mod Q
+//   LIFT_ROUND   r -> fst (divModCent (p lift_q r) q) mod p = ((p lift_q r + q/2) >> k) mod p (arithmetic shift:
+//                floor; |p lift r| <= p q / 2 < 2^62), in [-p/2, p/2] before the final + p
+// In place (src == dst) is allowed: every word is read and written by one thread.
+// ---------------------------------------------------------------------------------------
+template <int MODE>
+__device__ __forceinline__ i64 lift_one(i64 x, const KhprfLift& c) {
+  const u64 mask = ((u64)1 << c.qbits) - 1;
+  u64 r;
+  if constexpr ((MODE & LIFT_FROM_Q) != 0) {
+    const u64 xq = canon_in(x, c.Q);
+    const i64 v = 2 * xq < c.Q ? (i64)xq : (i64)xq - (i64)c.Q;
+    r = (u64)v & mask;
+  } else {
+    r = (u64)x & mask;
+  }
+  const i64 half = (i64)1 << (c.qbits - 1);
+  const i64 lr = (i64)r >= half ? (i64)r - 2 * half : (i64)r;     // lift_q: [-q/2, q/2)
+  if constexpr ((MODE & LIFT_TO_Q) != 0) {
+    return lr < 0 ? lr + (i64)c.Q : lr;
+  } else if constexpr ((MODE & LIFT_ROUND) != 0) {
+    const i64 y = ((i64)c.p * lr + half) >> c.qbits;
+    return y < 0 ? y + (i64)c.p : y;
+  } else {
+    return (i64)r;
+  }
+}
+
+template <int MODE, bool V2>
+__global__ void __launch_bounds__(TPB)
+k_khprf_lift(const i64* src, i64* dst, i64 total, KhprfLift c) {
+  if constexpr (V2) {
+    const i64 pairs = total >> 1;
+    for (i64 g = (i64)blockIdx.x * TPB + threadIdx.x; g < pairs; g += (i64)gridDim.x * TPB) {
+      const longlong2 a = reinterpret_cast<const longlong2*>(src)[g];
+      longlong2 b;
+      b.x = lift_one<MODE>(a.x, c);
+      b.y = lift_one<MODE>(a.y, c);
+      reinterpret_cast<longlong2*>(dst)[g] = b;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (total & 1)) dst[total - 1] = lift_one<MODE>(src[total - 1], c);
+  } else {                                                      // a slab not 16-byte aligned
+    for (i64 g = (i64)blockIdx.x * TPB + threadIdx.x; g < total; g += (i64)gridDim.x * TPB)
+      dst[g] = lift_one<MODE>(src[g], c);
+  }
+}
+
+hipError_t launch_khprf_lift(hipStream_t s, const i64* src, i64* dst, i64 total, int mode, const KhprfLift& c) {
+  if (total == 0) return hipSuccess;
+  if (c.qbits < 1 || c.qbits > 62) return hipErrorInvalidValue;
+  if ((mode & LIFT_ROUND) && ((mode & LIFT_TO_Q) || c.p < 2)) return hipErrorInvalidValue;
+  const bool v2 = ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0;
+  const unsigned grid = grid_for(v2 ? (total + 1) >> 1 : total);
+#define LOLHIP_LIFT(M)                                                                                      \
+  do {                                                                                                       \
+    if (v2) hipLaunchKernelGGL((k_khprf_lift<M, true>), dim3(grid), dim3(TPB), 0, s, src, dst, total, c);    \
+    else hipLaunchKernelGGL((k_khprf_lift<M, false>), dim3(grid), dim3(TPB), 0, s, src, dst, total, c);      \
+  } while (0)
+  switch (mode) {
+    case LIFT_FROM_Q: LOLHIP_LIFT(LIFT_FROM_Q); break;
+    case LIFT_TO_Q: LOLHIP_LIFT(LIFT_TO_Q); break;
+    case LIFT_FROM_Q | LIFT_TO_Q: LOLHIP_LIFT(LIFT_FROM_Q | LIFT_TO_Q); break;
+    case LIFT_ROUND: LOLHIP_LIFT(LIFT_ROUND); break;
+    case LIFT_FROM_Q | LIFT_ROUND: LOLHIP_LIFT(LIFT_FROM_Q | LIFT_ROUND); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef LOLHIP_LIFT
   return hipGetLastError();
 }
 

@@ -1,8 +1,14 @@
 // lol_amd/csrc/khprf_api.cpp — the C ABI of the key-homomorphic ring PRF (include/lolhip.h; lol-apps
 // KeyHomomorphicPRF.hs buildDecTree / ringPRF'): the tree, the slot planner over an input window and the launch plan
 // over the existing crt / crtInv / lInv / decompose and the kernels of khprf.hip.
+//
+// The lifted family (lolhip_khprf_create_lifted) runs over q = 2^k, which has no CRT basis: every node product is
+// computed exactly over the integers in the CRT basis mod an NTT prime Q (certified at creation) and brought back to
+// Z_q before it is used again.  The Q-side values sit where the one-modulus family keeps its CRT values; decompose and
+// lInv run on the plan mod q.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "capi_internal.h"
@@ -22,6 +28,8 @@ struct KNode {
 
 struct lolhip_khprf {
   const lolhip_plan* pq = nullptr;
+  const lolhip_plan* pQ = nullptr;  // the lifted family: products mod Q in its CRT basis; nullptr otherwise
+  KhprfLift lc{};                // the lifted family: Q, q = 2^qbits
   int64_t base = 0;
   int ell = 0;                   // gadget length L
   int k = 0;                     // leaves
@@ -31,6 +39,7 @@ struct lolhip_khprf {
   int fold = 1;                  // Q32 digits per 64-bit sum of k_khprf_node
   int64_t* d_leaf = nullptr;     // [2][L][n]: a0, a1 (CRT basis)
   int64_t* d_leafdig = nullptr;  // [L][2][L][n]: crt(G^-1(a0)), crt(G^-1(a1)) interleaved as decompose writes them
+  int64_t* d_leafpow = nullptr;  // the lifted family: [2][L][n] a0, a1 in the powerful basis mod q (a one-leaf A_T)
 };
 
 namespace {
@@ -117,25 +126,54 @@ bool range_ok(const lolhip_khprf* f, int64_t x0, int64_t B) {
 
 bool q_below31(const Plan& P) { return P.qs[0] < ((u64)1 << 31); }
 
+// LOLHIP_OK, or why the family cannot compute on the calling thread's current device (both plans of a lifted one)
+int need_device(const lolhip_khprf* f) {
+  const int rc = capi_need_device(f->pq);
+  return rc || !f->pQ ? rc : capi_need_device(f->pQ);
+}
+
+// Q32 digits per 64-bit sum of k_khprf_node for products mod q: (q-1) + fold (q-1)^2 < 2^64
+int fold_for(u64 q, int ell) {
+  if (q >= ((u64)1 << 32)) return 8;
+  const u64 q1 = q - 1, sq = q1 * q1;
+  const u64 F = (~(u64)0 - q1) / sq;
+  return (int)(F < (u64)ell ? F : (u64)ell);
+}
+
 // A_v for every slot of node i into dst ([U][L][n]), post-order
+// the lifted family: `rows` node values mod Q, CRT basis -> crtInv -> reduce mod q -> lift_q mod Q -> crt, in place
+int requantize(const lolhip_khprf& f, hipStream_t s, int64_t* y, int64_t rows) {
+  const Plan& PQ = f.pQ->P;
+  int rc = capi_do_crt(PQ, s, y, rows, true); if (rc) return rc;
+  if (launch_khprf_lift(s, y, y, rows * PQ.n, LIFT_FROM_Q | LIFT_TO_Q, f.lc) != hipSuccess) return LOLHIP_ERR_HIP;
+  return capi_do_crt(PQ, s, y, rows, false);
+}
+
 int eval_node(const lolhip_khprf& f, hipStream_t s, int i, int64_t x0, int64_t B, const Layout& lay, int64_t* work,
               int64_t* dst) {
   const Plan& P = f.pq->P;
+  const Plan& PC = f.pQ ? f.pQ->P : P;                     // where the products and their crt / crtInv live
   const KNode& v = f.nodes[i];
   const KNode& l = f.nodes[v.l];
   const KNode& r = f.nodes[v.r];
   const int64_t ln = (int64_t)f.ell * P.n;
-  if (!is_leaf(l)) { int rc = eval_node(f, s, v.l, x0, B, lay, work, work + lay.val[v.l]); if (rc) return rc; }
   const View vv = view(v, x0, B), vl = view(l, x0, B), vr = view(r, x0, B);
+  if (!is_leaf(l)) {
+    int rc = eval_node(f, s, v.l, x0, B, lay, work, work + lay.val[v.l]); if (rc) return rc;
+    if (f.pQ) { rc = requantize(f, s, work + lay.val[v.l], vl.U * f.ell); if (rc) return rc; }
+  }
   const int64_t* D = f.d_leafdig;
   if (!is_leaf(r)) {
     int64_t* rv = work + lay.val[v.r];
     int64_t* rd = work + lay.dig[v.r];
     int rc = eval_node(f, s, v.r, x0, B, lay, work, rv); if (rc) return rc;
     // G^-1: crtInv of the U_r L entries, their digits [L][U_r L][n], crt of the L U_r L digit polynomials
-    rc = capi_do_crt(P, s, rv, vr.U * f.ell, true); if (rc) return rc;
+    rc = capi_do_crt(PC, s, rv, vr.U * f.ell, true); if (rc) return rc;
+    if (f.pQ && launch_khprf_lift(s, rv, rv, vr.U * ln, LIFT_FROM_Q, f.lc) != hipSuccess) return LOLHIP_ERR_HIP;
     if (launch_decompose(s, rv, rd, vr.U * f.ell, P.n, f.dp, P.d_mod, q_below31(P)) != hipSuccess) return LOLHIP_ERR_HIP;
-    rc = capi_do_crt(P, s, rd, (int64_t)f.ell * vr.U * f.ell, false); if (rc) return rc;
+    const int64_t drows = (int64_t)f.ell * vr.U * f.ell;
+    if (f.pQ && launch_khprf_lift(s, rd, rd, drows * P.n, LIFT_TO_Q, f.lc) != hipSuccess) return LOLHIP_ERR_HIP;
+    rc = capi_do_crt(PC, s, rd, drows, false); if (rc) return rc;
     D = rd;
   }
   KhprfNode nd{};
@@ -152,20 +190,26 @@ int eval_node(const lolhip_khprf& f, hipStream_t s, int i, int64_t x0, int64_t B
   return launch_khprf_node(s, Lv, D, dst, nd, f.mc, f.fold) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
 }
 
-// A_T(x) for the window into dst [B][L][n] (B >= 1)
+// A_T(x) for the window into dst [B][L][n] (B >= 1): CRT basis, or powerful basis mod q for the lifted family
 int eval_root(const lolhip_khprf& f, hipStream_t s, int64_t x0, int64_t B, int64_t* work, int64_t* dst) {
   const int64_t ln = (int64_t)f.ell * f.pq->P.n;
-  if (is_leaf(f.nodes[0]))
-    return hipMemcpyAsync(dst, f.d_leaf + x0 * ln, sizeof(int64_t) * (size_t)(B * ln), hipMemcpyDeviceToDevice, s)
+  if (is_leaf(f.nodes[0])) {
+    const int64_t* src = (f.pQ ? f.d_leafpow : f.d_leaf) + x0 * ln;
+    return hipMemcpyAsync(dst, src, sizeof(int64_t) * (size_t)(B * ln), hipMemcpyDeviceToDevice, s)
                    == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  }
   const Layout lay = layout(f, x0, B);
-  return eval_node(f, s, 0, x0, B, lay, work, dst);
+  int rc = eval_node(f, s, 0, x0, B, lay, work, dst);
+  if (rc || !f.pQ) return rc;
+  rc = capi_do_crt(f.pQ->P, s, dst, B * f.ell, true); if (rc) return rc;
+  return launch_khprf_lift(s, dst, dst, B * ln, LIFT_FROM_Q, f.lc) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
 }
 
 void free_dev(lolhip_khprf* f) {
   if (f->d_leaf) (void)hipFree(f->d_leaf);
   if (f->d_leafdig) (void)hipFree(f->d_leafdig);
-  f->d_leaf = f->d_leafdig = nullptr;
+  if (f->d_leafpow) (void)hipFree(f->d_leafpow);
+  f->d_leaf = f->d_leafdig = f->d_leafpow = nullptr;
 }
 
 // a0 | a1 -> d_leaf; crtInv, decompose and crt into d_leafdig (on a private stream, synchronised)
@@ -192,6 +236,68 @@ int upload(lolhip_khprf* f, const std::vector<int64_t>& a) {
   return rc;
 }
 
+// the lifted family: a0 | a1 (powerful, [0, q)) -> d_leafpow; crt_Q (lift_q a) -> d_leaf; decompose mod q, lift_q and
+// crt_Q into d_leafdig (on a private stream, synchronised)
+int upload_lifted(lolhip_khprf* f, const std::vector<int64_t>& a) {
+  const Plan& P = f->pq->P;
+  const Plan& PQ = f->pQ->P;
+  const size_t words = a.size();                           // 2 L n
+  const int64_t dwords = (int64_t)f->ell * (int64_t)words;
+  if (hipMalloc(&f->d_leafpow, words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
+  if (hipMalloc(&f->d_leaf, words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
+  if (hipMalloc(&f->d_leafdig, (size_t)dwords * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
+  hipStream_t s;
+  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return LOLHIP_ERR_HIP;
+  int rc = LOLHIP_OK;
+  if (hipMemcpyAsync(f->d_leafpow, a.data(), words * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+      launch_khprf_lift(s, f->d_leafpow, f->d_leaf, (int64_t)words, LIFT_TO_Q, f->lc) != hipSuccess ||
+      launch_decompose(s, f->d_leafpow, f->d_leafdig, 2 * f->ell, P.n, f->dp, P.d_mod, q_below31(P)) != hipSuccess ||
+      launch_khprf_lift(s, f->d_leafdig, f->d_leafdig, dwords, LIFT_TO_Q, f->lc) != hipSuccess)
+    rc = LOLHIP_ERR_HIP;
+  if (!rc) rc = capi_do_crt(PQ, s, f->d_leaf, 2 * f->ell, false);
+  if (!rc) rc = capi_do_crt(PQ, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;
+  (void)hipStreamDestroy(s);
+  return rc;
+}
+
+// C_m = max_k sum_{i,j} |(b_i b_j)_k| over the powerful basis b: a product over the prime powers p^e of m.  The powerful
+// basis of p^e is {z^j : j < phi}, z^t = z^(t mod p^e), and z^(phi + r) = -sum_{l < p - 1} z^(l p^(e-1) + r) for
+// r < p^(e-1): each t = i + j (mult(t) = min(t, 2 phi - 2 - t) + 1 pairs) adds mult(t) to one or to p - 1 coefficients.
+// Saturates at 2^62.
+u64 growth(const std::vector<PP>& pps) {
+  const u64 cap = (u64)1 << 62;
+  u64 C = 1;
+  for (const PP& pe : pps) {
+    int64_t pk = 1;
+    for (int e = 0; e < pe.e; ++e) pk *= pe.p;
+    const int64_t pk1 = pk / pe.p, phi = pk - pk1;
+    std::vector<u64> acc((size_t)phi, 0);
+    for (int64_t t = 0; t <= 2 * phi - 2; ++t) {
+      const u64 mult = (u64)(std::min(t, 2 * phi - 2 - t) + 1);
+      const int64_t tt = t % pk;
+      if (tt < phi) { acc[(size_t)tt] += mult; continue; }
+      const int64_t r = tt - phi;
+      for (int64_t l = 0; l + 1 < pe.p; ++l) acc[(size_t)(l * pk1 + r)] += mult;
+    }
+    const u64 c = *std::max_element(acc.begin(), acc.end());
+    C = (unsigned __int128)C * c >= cap ? cap : C * c;
+  }
+  return C;
+}
+
+// the largest |digit| of decompose over lift_q: remainders in [-b/2, b/2), the last digit f^(k-1)(v) for v in
+// [-q/2, q/2) with f v = floor((v + b/2) / b) monotone; TrivGad: q/2
+u64 max_digit(u64 q, int64_t base, int k) {
+  if (base == 0) return q / 2;
+  auto fl = [&](int64_t a) { const int64_t d = a + base / 2; return d >= 0 ? d / base : -((-d + base - 1) / base); };
+  int64_t lo = -(int64_t)(q / 2), hi = (int64_t)(q / 2) - 1;
+  for (int i = 0; i + 1 < k; ++i) { lo = fl(lo); hi = fl(hi); }
+  u64 m = (u64)(base / 2);
+  m = std::max(m, (u64)(lo < 0 ? -lo : lo));
+  return std::max(m, (u64)(hi < 0 ? -hi : hi));
+}
+
 }  // namespace
 
 extern "C" {
@@ -212,13 +318,7 @@ int lolhip_khprf_create(const lolhip_plan* pq, int64_t base, const int32_t* tree
   f->k = f->nodes[0].c;
   const u64 q = P.qs[0];
   f->mc = make_modctx(q);
-  if (q < ((u64)1 << 32)) {                                // (q-1) + fold (q-1)^2 < 2^64
-    const u64 q1 = q - 1, sq = q1 * q1;
-    const u64 F = (~(u64)0 - q1) / sq;
-    f->fold = (int)(F < (u64)f->ell ? F : (u64)f->ell);
-  } else {
-    f->fold = 8;
-  }
+  f->fold = fold_for(q, f->ell);
   rc = capi_need_device(pq);
   if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f; return LOLHIP_OK; }      // host-only: validation and work lengths
   if (rc) { delete f; return rc; }
@@ -230,6 +330,51 @@ int lolhip_khprf_create(const lolhip_plan* pq, int64_t base, const int32_t* tree
     a[ln + i] = x1 < 0 ? x1 + (int64_t)q : x1;
   }
   rc = upload(f, a);
+  if (rc) { free_dev(f); delete f; return rc; }
+  *out = f;
+  return LOLHIP_OK;
+}
+
+int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int64_t base, const int32_t* tree,
+                               int ntree, const int64_t* a0_pow, const int64_t* a1_pow, lolhip_khprf** out) {
+  if (!pq || !pQ || !tree || !a0_pow || !a1_pow || !out || ntree < 1 || ntree > 123) return LOLHIP_ERR_INVALID;
+  const Plan& P = pq->P;
+  const Plan& PQ = pQ->P;
+  if (P.T != 1 || PQ.T != 1 || P.m != PQ.m || P.pps.size() != PQ.pps.size()) return LOLHIP_ERR_INVALID;
+  for (size_t i = 0; i < P.pps.size(); ++i)                 // the same index with the same tensor order
+    if (P.pps[i].p != PQ.pps[i].p || P.pps[i].e != PQ.pps[i].e) return LOLHIP_ERR_INVALID;
+  lolhip_khprf* f = new lolhip_khprf;
+  f->pq = pq;
+  f->pQ = pQ;
+  f->base = base;
+  int rc = capi_make_decomp(P, base, f->dp);
+  if (!rc && (parse(tree, ntree, 0, 0, f->nodes, 0) != ntree || f->nodes[0].c > 62)) rc = LOLHIP_ERR_INVALID;
+  const u64 q = P.qs[0], Q = PQ.qs[0];
+  if (!rc && (q < 2 || (q & (q - 1)) != 0)) rc = LOLHIP_ERR_MODULUS;
+  if (!rc && !PQ.has_crt) rc = LOLHIP_ERR_NO_CRT;
+  if (rc) { delete f; return rc; }
+  f->ell = f->dp.L;
+  f->k = f->nodes[0].c;
+  // exactness over Z: |sum_i L_i digit_i| <= L C_m (q/2) max|digit| and |s A| <= C_m (q/2)^2 below Q/2
+  auto sat = [](u128 a, u128 b) -> u128 { const u128 cap = (u128)1 << 100; return a >= cap || b >= cap || a * b >= cap ? cap : a * b; };
+  const u128 C = growth(P.pps), h = q / 2;
+  const u128 node = sat(sat(sat((u128)f->ell, C), h), max_digit(q, base, f->dp.k[0]));
+  const u128 key = sat(sat(C, h), h);
+  if (2 * std::max(node, key) >= (u128)Q) { delete f; return LOLHIP_ERR_MODULUS; }
+  f->lc.Q = Q;
+  f->lc.qbits = __builtin_ctzll(q);
+  f->mc = make_modctx(Q);
+  f->fold = fold_for(Q, f->ell);
+  rc = need_device(f);
+  if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f; return LOLHIP_OK; }      // host-only: validation and work lengths
+  if (rc) { delete f; return rc; }
+  const int64_t ln = (int64_t)f->ell * P.n;
+  std::vector<int64_t> a((size_t)(2 * ln));
+  for (int64_t i = 0; i < ln; ++i) {
+    a[i] = (int64_t)((u64)a0_pow[i] & (q - 1));
+    a[ln + i] = (int64_t)((u64)a1_pow[i] & (q - 1));
+  }
+  rc = upload_lifted(f, a);
   if (rc) { free_dev(f); delete f; return rc; }
   *out = f;
   return LOLHIP_OK;
@@ -248,7 +393,7 @@ int64_t lolhip_khprf_work_len(const lolhip_khprf* f, int64_t x0, int64_t B) {
 
 int lolhip_khprf_eval_batch(const lolhip_khprf* f, void* stream, int64_t x0, int64_t B, int64_t* out, int64_t* work) {
   if (!range_ok(f, x0, B)) return LOLHIP_ERR_INVALID;
-  int rc = capi_need_device(f->pq); if (rc) return rc;
+  int rc = need_device(f); if (rc) return rc;
   if (B > 0 && (!out || (!work && layout(*f, x0, B).total > 0))) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
   return eval_root(*f, (hipStream_t)stream, x0, B, work, out);
@@ -260,7 +405,7 @@ int lolhip_khprf_batch(const lolhip_khprf* f, void* stream, const int64_t* s_crt
   if (!range_ok(f, x0, B) || nkeys < 1) return LOLHIP_ERR_INVALID;
   const u64 q = f->pq->P.qs[0];
   if (p < 2 || (u64)p >= q || (unsigned __int128)(u64)p * q >= ((unsigned __int128)1 << 63)) return LOLHIP_ERR_MODULUS;
-  int rc = capi_need_device(f->pq); if (rc) return rc;
+  int rc = need_device(f); if (rc) return rc;
   const Layout lay = layout(*f, x0, B);
   if (B > 0 && (!s_crt || !out || (!work && lay.total > 0))) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
@@ -271,12 +416,26 @@ int lolhip_khprf_batch(const lolhip_khprf* f, void* stream, const int64_t* s_crt
   if (!is_leaf(f->nodes[0])) {
     int64_t* root = work + lay.val[0];
     rc = eval_node(*f, s, 0, x0, B, lay, work, root); if (rc) return rc;
+    if (f->pQ) { rc = requantize(*f, s, root, B * f->ell); if (rc) return rc; }
     A = root;
   }
   const int64_t rows = (int64_t)nkeys * B * f->ell;
   if (launch_khprf_keymul(s, A, s_crt, out, nkeys, B * f->ell, P.n, f->mc) != hipSuccess) return LOLHIP_ERR_HIP;
+  const bool linv = !P.prog_linv.stages.empty();
+  if (f->pQ) {
+    // exact s A mod Q -> Z_q (fused with the 2-power rounding when there is no lInv between them)
+    rc = capi_do_crt(f->pQ->P, s, out, rows, true); if (rc) return rc;
+    KhprfLift lc = f->lc;
+    lc.p = (u64)p;
+    if (linv) {
+      if (launch_khprf_lift(s, out, out, rows * P.n, LIFT_FROM_Q, lc) != hipSuccess) return LOLHIP_ERR_HIP;
+      rc = capi_run_prog(P, P.prog_linv, s, out, rows, nullptr); if (rc) return rc;
+    }
+    return launch_khprf_lift(s, out, out, rows * P.n, (linv ? 0 : LIFT_FROM_Q) | LIFT_ROUND, lc) == hipSuccess
+               ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  }
   rc = capi_do_crt(P, s, out, rows, true); if (rc) return rc;
-  if (!P.prog_linv.stages.empty()) { rc = capi_run_prog(P, P.prog_linv, s, out, rows, nullptr); if (rc) return rc; }
+  if (linv) { rc = capi_run_prog(P, P.prog_linv, s, out, rows, nullptr); if (rc) return rc; }
   return launch_khprf_round(s, out, rows * P.n, p, f->mc) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
 }
 

@@ -102,5 +102,15 @@ hipError_t launch_khprf_keymul(hipStream_t s, const i64* A, const i64* s_crt, i6
                                const ModCtx& mc);
 // y = fst (divModCent (p lift y) q) mod p in place (rescaleMod, q odd, p q < 2^63)
 hipError_t launch_khprf_round(hipStream_t s, i64* y, i64 total, i64 p, const ModCtx& mc);
+// the lifted family (q = 2^qbits, node products exact mod the NTT prime Q): dst = the pass `mode` of src, words in
+// [0, Q) / [0, q); src == dst allowed, both 16-byte aligned.  LIFT_FROM_Q: reduce lift_Q x mod q; LIFT_TO_Q: lift_q into
+// [0, Q); LIFT_ROUND: fst (divModCent (p lift_q r) q) mod p (needs p q < 2^63; not with LIFT_TO_Q)
+enum { LIFT_FROM_Q = 1, LIFT_TO_Q = 2, LIFT_ROUND = 4 };
+struct KhprfLift {
+  u64 Q;                       // the NTT prime
+  u64 p;                       // LIFT_ROUND: the target modulus
+  int qbits;                   // q = 2^qbits, 1 <= qbits <= 62
+};
+hipError_t launch_khprf_lift(hipStream_t s, const i64* src, i64* dst, i64 total, int mode, const KhprfLift& c);
 
 }  // namespace lolhip

@@ -16,6 +16,7 @@ Neither has a CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -118,6 +119,7 @@ def lib():
     L.lolhip_tunnel_hint_work_len.restype = i64
     L.lolhip_tunnel_hint_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, i64, C.c_char_p, C.c_uint64, vp, vp]
     L.lolhip_khprf_create.argtypes = [vp, i64, _i32p, ci, _i64p, _i64p, C.POINTER(vp)]
+    L.lolhip_khprf_create_lifted.argtypes = [vp, vp, i64, _i32p, ci, _i64p, _i64p, C.POINTER(vp)]
     L.lolhip_khprf_destroy.argtypes = [vp]
     L.lolhip_khprf_destroy.restype = None
     L.lolhip_khprf_work_len.argtypes = [vp, i64, i64]
@@ -975,11 +977,51 @@ class KHPRF:
                                          a1.ctypes.data_as(_i64p), C.byref(h)), f"khprf_create(tree={self.tree})")
         self._h = h
         self.k = self.tree[0]
+        self.plan_Q = None
+
+    @classmethod
+    def lifted(cls, plan_q: Plan, plan_Q: Plan, base, tree, a0_pow, a1_pow):
+        """The same PRF over q = 2^k, which has no CRT basis (lolhip_khprf_create_lifted): plan_q mod q, plan_Q of the
+        same index over an NTT-friendly prime Q in which every node product is exact (certified here), a0_pow, a1_pow
+        [L][n] in the powerful basis.  eval() then returns A_T(x) in the powerful basis mod q, and a key s passed to
+        __call__ is in the powerful basis of R_q."""
+        self = cls.__new__(cls)
+        self.plan, self.plan_Q, self.base = plan_q, plan_Q, int(base)
+        self.tree = [int(c) for c in tree]
+        self.L = plan_q.decomposeLen(base) if plan_q.T == 1 else 0
+        a0 = np.ascontiguousarray(np.asarray(a0_pow, dtype=np.int64).reshape(-1))
+        a1 = np.ascontiguousarray(np.asarray(a1_pow, dtype=np.int64).reshape(-1))
+        if a0.size != self.L * plan_q.n or a1.size != self.L * plan_q.n:
+            raise ValueError("a0 and a1 must be [L][n]")
+        tr = (C.c_int32 * max(1, len(self.tree)))(*self.tree)
+        h = C.c_void_p()
+        _check(lib().lolhip_khprf_create_lifted(plan_q._h, plan_Q._h, self.base, tr, len(self.tree),
+                                                a0.ctypes.data_as(_i64p), a1.ctypes.data_as(_i64p), C.byref(h)),
+               f"khprf_create_lifted(tree={self.tree})")
+        self._h = h
+        self.k = self.tree[0]
+        return self
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:
             _lib.lolhip_khprf_destroy(h)
+
+    def _key_crt(self, s, nkeys, stream=None):
+        """the lifted family's keys: powerful basis of R_q -> centred lift mod Q -> crt on plan_Q.  A CUDA key stays on
+        the device (torch ops ordered on the call's stream); a numpy key is lifted before its upload."""
+        import torch
+        q, Q = self.plan.qs[0], self.plan_Q.qs[0]
+        ctx = torch.cuda.stream(torch.cuda.ExternalStream(int(stream))) if stream else contextlib.nullcontext()
+        with ctx:
+            if isinstance(s, np.ndarray):
+                r = np.asarray(s, dtype=np.int64).reshape(nkeys, self.plan.n) & (q - 1)
+                d = torch.from_numpy(np.ascontiguousarray(np.where(2 * r < q, r, r - q + Q))).cuda()
+            else:
+                r = s.to(torch.int64).reshape(nkeys, self.plan.n) & (q - 1)
+                d = torch.where(2 * r < q, r, r - q + Q).contiguous()
+        self.plan_Q.crt(d.view(nkeys, self.plan.n, 1), stream)
+        return d
 
     def workLen(self, x0, B):
         w = lib().lolhip_khprf_work_len(self._h, int(x0), int(B))
@@ -987,7 +1029,8 @@ class KHPRF:
         return w
 
     def eval(self, x0, B, stream=None):
-        """A_T(x) for x = x0 .. x0 + B - 1: a CUDA tensor [B][L][n] in the CRT basis (lolhip_khprf_eval_batch)."""
+        """A_T(x) for x = x0 .. x0 + B - 1: a CUDA tensor [B][L][n] in the CRT basis (lolhip_khprf_eval_batch); the
+        lifted family: in the powerful basis, residues in [0, q)."""
         import torch
         L = lib()
         _check(L.lolhip_khprf_eval_batch(self._h, None, int(x0), 0, None, None))      # the host statuses first
@@ -1000,7 +1043,8 @@ class KHPRF:
 
     def __call__(self, s, p, x0, B, stream=None):
         """ringPRF s x for x = x0 .. x0 + B - 1 (lolhip_khprf_batch): s [n] or [nkeys][n] in the CRT basis (numpy or a
-        CUDA tensor) -> [nkeys][B][L][n] int64 in [0, p), decoding basis of R_p ([B][L][n] for a single key s [n])."""
+        CUDA tensor; the lifted family: in the powerful basis of R_q) -> [nkeys][B][L][n] int64 in [0, p), decoding
+        basis of R_p ([B][L][n] for a single key s [n])."""
         import torch
         L = lib()
         single = len(s.shape) == 1
@@ -1008,7 +1052,9 @@ class KHPRF:
         _check(L.lolhip_khprf_batch(self._h, None, None, nkeys, int(p), int(x0), 0, None, None))
         if int(x0) + int(B) > (1 << self.k) or int(B) < 0:
             _check(ERR_INVALID, "x0 + B > 2^k")
-        if isinstance(s, np.ndarray):
+        if self.plan_Q is not None:
+            s = self._key_crt(s, nkeys, stream)
+        elif isinstance(s, np.ndarray):
             s = torch.from_numpy(np.ascontiguousarray(s, dtype=np.int64)).cuda()
         s = s.reshape(nkeys, self.plan.n).contiguous()
         work = torch.empty((max(self.workLen(x0, B), 1),), dtype=torch.int64, device=s.device)

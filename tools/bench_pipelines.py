@@ -2,7 +2,7 @@
 """tools/bench_pipelines.py — throughput of the SymmSHE pipeline kernels on one MI355X
 (BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone), of encrypt / errorRounded
 (`--encrypt`: that leg alone), of the key-switch / tunnel hints (`--kshint`: that leg alone) and of the key-homomorphic
-ring PRF (`--khprf`: that leg alone).  Operands resident in HBM, HIP events on
+ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q = 2^k alone).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -238,8 +238,40 @@ def khprf_leg(gen):
             del work, out, f
 
 
+def khprf_lifted_leg(gen):
+    """The lifted family (lolhip_khprf_create_lifted) at the reference's own benchmark shape: F128, Zq 8 -> Zq 2,
+    BaseBGad 2 (L = 4), 5 leaves (left / balanced / right), all 32 inputs, products at a 30-bit NTT prime Q; and a
+    balanced 10-leaf tree over all 1024 inputs.  alg_bytes as for the one-modulus leg (node kernels only)."""
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    m, q, p, base = 128, 8, 2, 2
+    Q = lol_amd.good_q(m, 2 ** 29)
+    Pq, PQ = lol_amd.Plan.for_index(m, [q]), lol_amd.Plan.for_index(m, [Q])
+    nL = Pq.decomposeLen(base)
+    g = np.random.default_rng(0)
+    a0, a1 = (g.integers(0, q, size=(nL, Pq.n), dtype=np.int64) for _ in range(2))
+    for tname, tree in (("left", lol_amd.left_spine_tree(5)), ("balanced", lol_amd.balanced_tree(5)),
+                        ("right", lol_amd.right_spine_tree(5)), ("balanced", lol_amd.balanced_tree(10))):
+        B = 1 << tree[0]
+        f = lol_amd.KHPRF.lifted(Pq, PQ, base, tree, a0, a1)
+        s = f._key_crt(g.integers(0, q, size=(1, Pq.n), dtype=np.int64), 1)
+        work = torch.empty((max(f.workLen(0, B), 1),), dtype=torch.int64, device="cuda")
+        out = torch.empty((B, nL, Pq.n), dtype=torch.int64, device="cuda")
+        nb = khprf_node_bytes(tree, nL, Pq.n, 0, B)
+        cfg = f"m=128 q=8 Q={Q} p=2 k={tree[0]} {tname} base={base} L={nL} B={B}"
+        ms = timeit(lambda: L.lolhip_khprf_eval_batch(f._h, st, 0, B, ptr(out), ptr(work)))
+        report("khprf_lifted_eval", cfg, ms, B, nb, note="items = inputs; alg = node kernels' compulsory bytes")
+        ms = timeit(lambda: L.lolhip_khprf_batch(f._h, st, ptr(s), 1, p, 0, B, ptr(out), ptr(work)))
+        report("khprf_lifted_prf", cfg + " nkeys=1", ms, B, nb + B * nL * Pq.n * 8 * 2)
+        del work, out, f
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--khprf-lifted" in sys.argv:     # the lifted key-homomorphic PRF leg alone
+        khprf_lifted_leg(gen)
+        return
     if "--decrypt" in sys.argv:          # the decrypt leg alone
         decrypt_leg(gen)
         return
