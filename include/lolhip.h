@@ -411,6 +411,48 @@ LOLHIP_API int lolhip_khprf_create_lifted(const lolhip_plan *pq, const lolhip_pl
                                           const int32_t *tree, int ntree, const int64_t *a0_pow,
                                           const int64_t *a1_pow, lolhip_khprf **out);
 
+/* SymmSHE public operations and ciphertext addition (lol-apps SymmSHE.hs:214-230, 381-436; ZqBasic.hs:92-94,132-137).
+ * A ciphertext is CT enc k l c over R'_q (pq: index m', moduli q_0..q_{T-1}, Q = prod q_t): components cs
+ * [ncs][B][n'][T].  Public values are elements of R_m (m | m') mod p in the powerful basis, [B][n_m] int64 of any value
+ * (taken mod p), item b at b * stride; stride 0 = one value for the whole batch, otherwise stride >= n_m (the lifted
+ * output [B][L][n] of lolhip_khprf_eval_batch passes with stride L n).  decode' lifts v in [0, p) to v for 2v < p, else
+ * v - p (p/2 lifts to -p/2).
+ * lolhip_encode_scales: the encoding factors of the product ring, on the host (host-only plans too):
+ *   to_msd = 1: lsdToMSD = (zp = -Q mod p, zq_t = p^-1 mod q_t);  to_msd = 0: msdToLSD = (zp = (-Q)^-1 mod p,
+ *   zq_t = p mod q_t).  toMSD / toLSD multiply every c_i by zq and l by zp.
+ * lolhip_ct_lincomb_batch: out_i = alpha_t a_i + beta_t b_i mod q_t for i < max(na, nb), a missing component counting
+ *   as zero; alpha, beta: HOST arrays [T] of any int64; b = NULL with nb = 0 for out = alpha a.  Either basis.  out may
+ *   alias a or b.  toMSD / toLSD / mulScalar (alpha = decode'(a) mod q_t) / negate (alpha = -1) / subtraction and the
+ *   componentwise (+) are this one pass.
+ * lolhip_add_public_batch: addPublic b (SymmSHE.hs:381-390): toLSD, then c_0 += embed (reduce (decode' v)) with
+ *   v = l^-1 g_m^k b in R_m mod p (mulGPow of index m, k times).  cs in the powerful basis (cs_crt = 0) or the CRT basis
+ *   (cs_crt = 1), out in the same basis; enc 0 = LSD, 1 = MSD; *l_out = l after toLSD; k is unchanged.  pp_m: the plan
+ *   of index m over p alone (read for k > 0 only; it runs lolhip_mulgpow_batch).
+ * lolhip_mul_public_batch: mulPublic a (SymmSHE.hs:405-411): every c_i times embed (reduce (decode' a)); cs and out in
+ *   the CRT basis; enc, k and l do not change.  absorbGFactors (:464-473) is lolhip_divgpow_batch k times on the plan
+ *   (m', p) applied to 1, then this call with stride 0 and x_q = NULL.
+ * Both: x_q is an ext from the plan of (m, q_0..q_{T-1}) to pq, or NULL for m = m'; cs_shared = 1: one ciphertext for
+ *   the whole batch ([ncs][1][n'][T]); out [ncs][B][n'][T] may alias cs unless cs is shared and B > 1.  The embedding
+ *   is a gather folded into the pass: baseIndicesCRT (CRT basis; the public value goes through a crt of index m) or
+ *   embedPow (powerful basis).  work: lolhip_public_work_len(pq, x_q, B) int64 of device scratch.
+ * Status: LOLHIP_ERR_INVALID for ncs < 1, B < 0, T > 16, x_q not ending in pq's ring and moduli, a bad stride, pp_m not
+ *   of index m over p alone (k > 0), out = a shared cs with B > 1, NULL pointers; LOLHIP_ERR_NO_CRT for a CRT-basis path
+ *   whose plans have no CRT basis; LOLHIP_ERR_MODULUS for p < 2 or p >= 2^62, l not invertible mod p, MSD input with
+ *   gcd(Q, p) != 1 (encode_scales: p not invertible mod some q_t for to_msd = 1); LOLHIP_ERR_NO_DEVICE on a host-only
+ *   plan or ext; LOLHIP_ERR_DEVICE as elsewhere.  Every one is decided on the host before any launch: the output (and
+ *   *l_out) is then not written.  No call synchronises or allocates. */
+LOLHIP_API int lolhip_encode_scales(const lolhip_plan *pq, int64_t p, int to_msd, int64_t *zq_scale, int64_t *zp_scale);
+LOLHIP_API int lolhip_ct_lincomb_batch(const lolhip_plan *pq, void *stream, const int64_t *a, int na, const int64_t *alpha,
+                                       const int64_t *b, int nb, const int64_t *beta, int64_t *out, int64_t B);
+LOLHIP_API int64_t lolhip_public_work_len(const lolhip_plan *pq, const lolhip_ext *x_q, int64_t B);
+LOLHIP_API int lolhip_add_public_batch(const lolhip_plan *pq, const lolhip_ext *x_q, const lolhip_plan *pp_m, void *stream,
+                                       const int64_t *b_pow, int64_t b_stride, const int64_t *cs, int ncs, int cs_shared,
+                                       int cs_crt, int enc, int64_t k, int64_t l, int64_t p, int64_t *out, int64_t *l_out,
+                                       int64_t *work, int64_t B);
+LOLHIP_API int lolhip_mul_public_batch(const lolhip_plan *pq, const lolhip_ext *x_q, void *stream, const int64_t *a_pow,
+                                       int64_t a_stride, int64_t p, const int64_t *cs, int ncs, int cs_shared,
+                                       int64_t *out, int64_t *work, int64_t B);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

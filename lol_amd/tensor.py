@@ -126,6 +126,12 @@ def lib():
     L.lolhip_khprf_work_len.restype = i64
     L.lolhip_khprf_eval_batch.argtypes = [vp, vp, i64, i64, vp, vp]
     L.lolhip_khprf_batch.argtypes = [vp, vp, vp, ci, i64, i64, i64, vp, vp]
+    L.lolhip_encode_scales.argtypes = [vp, i64, ci, _i64p, _i64p]
+    L.lolhip_ct_lincomb_batch.argtypes = [vp, vp, vp, ci, _i64p, vp, ci, _i64p, vp, i64]
+    L.lolhip_public_work_len.argtypes = [vp, vp, i64]
+    L.lolhip_public_work_len.restype = i64
+    L.lolhip_add_public_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp, ci, ci, ci, ci, i64, i64, i64, vp, _i64p, vp, i64]
+    L.lolhip_mul_public_batch.argtypes = [vp, vp, vp, vp, i64, i64, vp, ci, ci, vp, vp, i64]
     L.lolhip_chacha20_block.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.lolhip_chacha20_block.restype = None
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
@@ -803,6 +809,195 @@ class Plan:
         s2 = s_crt.clone().contiguous()
         self.mul(s2, s_crt, stream=stream)
         return self._unstage(host, self.ksHint(s_crt, s2, svar, base, key=key, ctr=ctr, stream=stream)[0])
+
+    # ---- SymmSHE public operations and ciphertext addition (lol-apps SymmSHE.hs:214-230, 381-436) ---------------
+    # A ciphertext is cs ([ncs][B][n][T], or a list of [B][n][T]) with its (enc, k, l); each call takes and returns the
+    # parts it changes.  numpy in -> numpy out (staged through HBM); CUDA tensors in -> CUDA tensors out.
+    def encodeScales(self, p, to_msd):
+        """The encoding factors of the product ring (ZqBasic.hs:132-137, Prelude.hs:310-315): to_msd -> lsdToMSD =
+        ([p^-1 mod q_t], -Q mod p), else msdToLSD = ([p mod q_t], (-Q)^-1 mod p).  Host only."""
+        zq = np.zeros(self.T, dtype=np.int64)
+        zp = C.c_int64(0)
+        _check(lib().lolhip_encode_scales(self._h, int(p), int(bool(to_msd)), zq.ctypes.data_as(_i64p), C.byref(zp)))
+        return [int(v) for v in zq], int(zp.value)
+
+    def _cs(self, cs):
+        """(host?, cs as one [ncs][B][n][T] array or tensor, ncs, B)"""
+        import torch
+        if isinstance(cs, (list, tuple)):
+            host = isinstance(cs[0], np.ndarray)
+            cs = np.stack([np.asarray(c, dtype=np.int64) for c in cs]) if host else torch.stack(list(cs))
+        host = isinstance(cs, np.ndarray)
+        size = cs.size if host else cs.numel()
+        ncs = int(cs.shape[0])
+        B = size // max(ncs * self.n * self.T, 1)
+        if ncs * B * self.n * self.T != size:
+            raise ValueError("cs is not [ncs][B][n][T]")
+        return host, cs, ncs, B
+
+    def _per_mod(self, v):
+        v = [int(v)] * self.T if np.ndim(v) == 0 else [int(x) for x in v]
+        if len(v) != self.T:
+            raise ValueError("expected one scalar per modulus")
+        return (C.c_int64 * self.T)(*v)
+
+    def ctLinComb(self, a, alpha, b=None, beta=None, out=None, stream=None):
+        """out_i = alpha_t a_i + beta_t b_i mod q_t, i < max(na, nb), a missing component counting as zero
+        (lolhip_ct_lincomb_batch); alpha, beta: an int or one int per modulus.  Either basis; out may be a or b."""
+        import torch
+        host, a, na, B = self._cs(a)
+        nb = 0
+        if b is not None:
+            _, b, nb, Bb = self._cs(b)
+            if Bb != B:
+                raise ValueError("batch sizes differ")
+        al = self._per_mod(alpha)
+        be = self._per_mod(0 if beta is None else beta) if b is not None else None
+        L = lib()
+        _check(L.lolhip_ct_lincomb_batch(self._h, None, None, na, al, None if b is None else 1, nb, be, None, 0))
+        host, (a, b) = self._stage(a, b) if host else (False, (a, b))
+        if out is None:
+            out = torch.empty((max(na, nb), B, self.n, self.T), dtype=torch.int64, device=a.device)
+        _check(L.lolhip_ct_lincomb_batch(self._h, _stream(stream), _devptr(a), na, al, None if b is None else _devptr(b), nb,
+                                         be, _devptr(out), B))
+        return self._unstage(host, out)
+
+    @staticmethod
+    def _decode(v, p):
+        """decode' (ZqBasic.hs:92-94): v mod p lifted to [-p/2, p/2)"""
+        v = int(v) % int(p)
+        return v - p if 2 * v >= p else v
+
+    def toMSD(self, cs, p, enc="LSD", l=1, stream=None):
+        """toMSD (SymmSHE.hs:214-222) -> (cs, "MSD", l)"""
+        if self._enc(enc) == 1:
+            return cs, "MSD", int(l) % p
+        zq, zp = self.encodeScales(p, True)
+        return self.ctLinComb(cs, zq, stream=stream), "MSD", int(l) * zp % p
+
+    def toLSD(self, cs, p, enc="MSD", l=1, stream=None):
+        """toLSD (SymmSHE.hs:224-230) -> (cs, "LSD", l)"""
+        if self._enc(enc) == 0:
+            return cs, "LSD", int(l) % p
+        zq, zp = self.encodeScales(p, False)
+        return self.ctLinComb(cs, zq, stream=stream), "LSD", int(l) * zp % p
+
+    def mulScalar(self, cs, a, p, stream=None):
+        """mulScalar a (SymmSHE.hs:392-399): every c_i times decode'(a mod p) mod q_t"""
+        return self.ctLinComb(cs, self._decode(a, p), stream=stream)
+
+    def ctNegate(self, cs, stream=None):
+        """negate (SymmSHE.hs:420-436): every c_i times -1"""
+        return self.ctLinComb(cs, -1, stream=stream)
+
+    def mulGCT(self, cs, k, cs_crt=False, stream=None):
+        """mulGCT (SymmSHE.hs:413-416): mulG on every c_i (mulGCRT or mulGPow) -> (cs, k + 1)"""
+        host, cs, _, _ = self._cs(cs)
+        host, (cs,) = self._stage(cs) if host else (False, (cs,))
+        y = cs.clone()
+        self._dev("mulgcrt" if cs_crt else "mulgpow", y, stream)
+        return self._unstage(host, y), int(k) + 1
+
+    def ctAdd(self, ct1, ct2, p, cs_crt=False, stream=None):
+        """(+) (SymmSHE.hs:420-436) of ct = (cs, enc, k, l), aligned as the reference does, in order: l1 != l2 ->
+        mulScalar (l1 / l2) on ct1; unequal k -> mulGCT on the smaller; unequal encodings -> toMSD of the LSD one; then
+        the componentwise sum (the shorter one padded with zeros).  Returns (cs, enc, k, l)."""
+        (c1, e1, k1, l1), (c2, e2, k2, l2) = ct1, ct2
+        e1, e2, l1, l2 = self._enc(e1), self._enc(e2), int(l1) % p, int(l2) % p
+        while True:
+            if l1 != l2:
+                c1, l1 = self.mulScalar(c1, l1 * pow(l2, -1, p) % p, p, stream=stream), l2
+            elif k1 != k2:
+                if k1 < k2:
+                    c1, k1 = self.mulGCT(c1, k1, cs_crt, stream=stream)
+                else:
+                    c2, k2 = self.mulGCT(c2, k2, cs_crt, stream=stream)
+            elif e1 != e2:
+                if e1 == 0:
+                    c1, _, l1 = self.toMSD(c1, p, 0, l1, stream=stream)
+                    e1 = 1
+                else:
+                    c2, _, l2 = self.toMSD(c2, p, 0, l2, stream=stream)
+                    e2 = 1
+            else:
+                break
+        return self.ctLinComb(c1, 1, c2, 1, stream=stream), ("LSD", "MSD")[e1], k1, l1
+
+    def _public(self, v, n_m, B, stride):
+        """public values -> (array or tensor, stride): stride None infers 0 for one value ([n_m] or [1][n_m])"""
+        size = v.size if isinstance(v, np.ndarray) else v.numel()
+        if stride is None:
+            stride = 0 if size == n_m else n_m
+        if B > 0 and size < (stride * (B - 1) if stride else 0) + n_m:
+            raise ValueError("public values too short for the batch")
+        return v, int(stride)
+
+    def addPublic(self, b, cs, p, pp_m=None, ext=None, enc="LSD", k=0, l=1, cs_crt=False, cs_shared=False, stride=None,
+                  B=None, stream=None):
+        """addPublic b (SymmSHE.hs:381-390): toLSD, then c_0 + embed (decode' (l^-1 g^k b)) -> (cs, "LSD", l).  b [B][n_m]
+        (or one [n_m] for the whole batch) in the powerful basis of R_m, any int64; ext: an Ext from the Plan of (m, qs)
+        to this one, or None for m = m'; pp_m: the Plan of index m over p alone (k > 0).  cs_shared: one ciphertext
+        ([ncs][1][n][T]) for all B items."""
+        import torch
+        host, cs, ncs, Bc = self._cs(cs)
+        B = Bc if B is None else int(B)
+        n_m = self.n if ext is None else ext.lo.n
+        b, stride = self._public(b, n_m, B, stride)
+        L, xh, pph = lib(), (None if ext is None else ext._h), (None if pp_m is None else pp_m._h)
+        lo = C.c_int64(0)
+        args = (int(cs_shared), int(cs_crt), self._enc(enc), int(k), int(l), int(p))
+        _check(L.lolhip_add_public_batch(self._h, xh, pph, None, None, stride, None, ncs, *args, None, C.byref(lo), None, 0))
+        if host:
+            _, (b, cs) = self._stage(np.ascontiguousarray(b, dtype=np.int64), cs)
+        work = torch.empty((max(L.lolhip_public_work_len(self._h, xh, B), 1),), dtype=torch.int64, device=cs.device)
+        out = torch.empty((ncs, B, self.n, self.T), dtype=torch.int64, device=cs.device)
+        _check(L.lolhip_add_public_batch(self._h, xh, pph, _stream(stream), _devptr(b), stride, _devptr(cs), ncs, *args,
+                                         _devptr(out), C.byref(lo), _devptr(work), B))
+        return self._unstage(host, out), "LSD", int(lo.value)
+
+    def mulPublic(self, a, cs, p, ext=None, cs_shared=False, stride=None, B=None, out=None, stream=None):
+        """mulPublic a (SymmSHE.hs:405-411): every c_i times embed (reduce (decode' a)), cs and the result in the CRT
+        basis; enc, k and l do not change.  a [B][n_m] (or one [n_m]), any int64, powerful basis of R_m; stride: the
+        item stride of a (e.g. L n for KHPRF.eval's [B][L][n]); out may be cs unless cs is shared and B > 1."""
+        import torch
+        host, cs, ncs, Bc = self._cs(cs)
+        B = Bc if B is None else int(B)
+        n_m = self.n if ext is None else ext.lo.n
+        a, stride = self._public(a, n_m, B, stride)
+        L, xh = lib(), (None if ext is None else ext._h)
+        _check(L.lolhip_mul_public_batch(self._h, xh, None, None, stride, int(p), None, ncs, int(cs_shared), None, None, 0))
+        if host:
+            _, (a, cs) = self._stage(np.ascontiguousarray(a, dtype=np.int64), cs)
+        work = torch.empty((max(L.lolhip_public_work_len(self._h, xh, B), 1),), dtype=torch.int64, device=cs.device)
+        if out is None:
+            out = torch.empty((ncs, B, self.n, self.T), dtype=torch.int64, device=cs.device)
+        _check(L.lolhip_mul_public_batch(self._h, xh, _stream(stream), _devptr(a), stride, int(p), _devptr(cs), ncs,
+                                         int(cs_shared), _devptr(out), _devptr(work), B))
+        return self._unstage(host, out)
+
+    def modSwitchPT(self, cs, p, p2, enc="LSD", l=1, stream=None):
+        """modSwitchPT from p to p2 | p (SymmSHE.hs:255-261): toMSD, then l' = decode'_p(l) mod p2 -> (cs, "MSD", l')"""
+        if int(p) % int(p2):
+            raise ValueError("p2 must divide p")
+        cs, _, l = self.toMSD(cs, p, enc, l, stream=stream)
+        return cs, "MSD", self._decode(l, p) % int(p2)
+
+    def absorbGFactors(self, cs, k, pp, stream=None):
+        """absorbGFactors (SymmSHE.hs:464-473) of a CRT-basis ciphertext: every c_i times decode'(divG^k 1), divG over
+        pp (the Plan of this index over p alone) -> (cs, 0)"""
+        if int(k) == 0:
+            return cs, 0
+        d = np.zeros((1, pp.n, 1), dtype=np.int64)
+        d[0, 0, 0] = 1
+        for _ in range(int(k)):
+            d = pp.divGPow(d)
+            if d is None:
+                raise LolHipError(ERR_NOT_DIVISIBLE, "absorbGFactors: divG mod p")
+        if not isinstance(cs, np.ndarray) and not isinstance(cs, (list, tuple)):
+            import torch
+            d = torch.from_numpy(d).to(cs.device)
+        return self.mulPublic(d.reshape(-1) if isinstance(d, np.ndarray) else d.reshape(-1), cs, pp.qs[0], stride=0,
+                              stream=stream), 0
 
 
 def chacha20_block(key, counter, nonce):

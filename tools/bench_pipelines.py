@@ -267,8 +267,80 @@ def khprf_lifted_leg(gen):
         del work, out, f
 
 
+def public_leg(gen):
+    """The SymmSHE public operations and ciphertext addition (lolhip_mul_public_batch, lolhip_add_public_batch,
+    lolhip_ct_lincomb_batch).
+      1. HomomPRF's first step: mulPublic of B = 4096 public values of R_128 (stride L n, as lolhip_khprf_eval_batch
+         writes them) on one shared 2-component ciphertext over ZQ4 at m' = 128*7*13, p = 8; and on the same box the
+         direct composition: embedPow, crt at m', a copy and two lolhip_mul_batch against pre-broadcast components.
+         alg_bytes: the 2 output slabs written once (the public values and the shared ciphertext are L2-resident).
+      2. addPublic at config 3 (m' = 2^15, T = 4, 59-bit, B = 256, MSD in, k = 1), powerful and CRT basis.
+         alg_bytes: 2 component slabs read and written once, the [B][n] public values read once.
+      3. ct + ct at config 3: 2 + 2 component slabs read, 2 written."""
+    import ctypes
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    zq4 = [25159681, 19918081, 19393921, 18869761]
+    # ---- 1. HomomPRF mulPublic --------------------------------------------------------------
+    m, m2, p, B, nL = 128, 128 * 7 * 13, 8, 4096, 3
+    hi, lo = lol_amd.Plan.for_index(m2, zq4), lol_amd.Plan.for_index(m, zq4)
+    x = lol_amd.Ext(lo, hi)
+    T, n, n_m = hi.T, hi.n, lo.n
+    a = torch.randint(0, p, (B, nL, n_m), dtype=torch.int64, device="cuda", generator=gen)
+    cs = rnd(gen, zq4, 2, 1, n)
+    out = torch.empty((2, B, n, T), dtype=torch.int64, device="cuda")
+    work = torch.empty((L.lolhip_public_work_len(hi._h, x._h, B),), dtype=torch.int64, device="cuda")
+    cfg = f"m=128 in m'={m2} ZQ4 p=8 B={B} stride=L*n shared 2-comp ct"
+    wbytes = 2 * B * n * T * 8
+    ms = timeit(lambda: L.lolhip_mul_public_batch(hi._h, x._h, st, ptr(a), nL * n_m, p, ptr(cs), 2, 1, ptr(out),
+                                                   ptr(work), B))
+    report("mul_public", cfg, ms, B, wbytes, note="gather route: lift, crt at m, k_pub_apply")
+    # the direct composition; the lift (the same first step in both routes) is done once outside the timing
+    v = a[:, 0, :] % p
+    v = torch.where(2 * v < p, v, v - p)
+    lifted = torch.stack([v % q for q in zq4], dim=-1).contiguous()
+    emb = torch.empty((B, n, T), dtype=torch.int64, device="cuda")
+    emb1 = torch.empty_like(emb)
+    c0, c1 = (cs[i].expand(B, n, T).contiguous() for i in range(2))
+
+    def direct():
+        L.lolhip_embed_pow_batch(x._h, st, ptr(emb), ptr(lifted), B)
+        L.lolhip_crt_batch(hi._h, st, ptr(emb), B)
+        emb1.copy_(emb)
+        L.lolhip_mul_batch(hi._h, st, ptr(emb), ptr(c0), B)
+        L.lolhip_mul_batch(hi._h, st, ptr(emb1), ptr(c1), B)
+    ms_d = timeit(direct)
+    report("mul_public_direct", cfg, ms_d, B, wbytes, note="embedPow, crt at m', copy, 2 mul_batch (lift not timed)")
+    del a, cs, out, work, emb, emb1, c0, c1, lifted
+    # ---- 2. addPublic at config 3 -------------------------------------------------------------
+    qs = good_qs(2 ** 15, 2 ** 59, 4)
+    P = lol_amd.Plan([(2, 15)], qs)
+    pp = lol_amd.Plan([(2, 15)], [65537])
+    B = 256
+    slab = B * P.n * P.T * 8
+    cs = rnd(gen, qs, 2, B, P.n)
+    b = torch.randint(-2 ** 40, 2 ** 40, (B, P.n), dtype=torch.int64, device="cuda", generator=gen)
+    out = torch.empty_like(cs)
+    work = torch.empty((L.lolhip_public_work_len(P._h, None, B),), dtype=torch.int64, device="cuda")
+    lo_out = ctypes.c_int64(0)
+    for crt in (0, 1):
+        ms = timeit(lambda: L.lolhip_add_public_batch(P._h, None, pp._h, st, ptr(b), P.n, ptr(cs), 2, 0, crt, 1, 1, 3,
+                                                      65537, ptr(out), ctypes.byref(lo_out), ptr(work), B))
+        report("add_public", f"m'=2^15 T=4 59-bit B={B} MSD k=1 {'CRT' if crt else 'powerful'} basis", ms, B,
+               4 * slab + B * P.n * 8)
+    # ---- 3. ct + ct at config 3 ---------------------------------------------------------------
+    d = rnd(gen, qs, 2, B, P.n)
+    one = (ctypes.c_int64 * P.T)(*([1] * P.T))
+    ms = timeit(lambda: L.lolhip_ct_lincomb_batch(P._h, st, ptr(cs), 2, one, ptr(d), 2, one, ptr(out), B))
+    report("ct_add", f"m'=2^15 T=4 59-bit B={B} 2+2 comps", ms, B, 6 * slab)
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--public" in sys.argv:           # the public operations / ciphertext addition leg alone
+        public_leg(gen)
+        return
     if "--khprf-lifted" in sys.argv:     # the lifted key-homomorphic PRF leg alone
         khprf_lifted_leg(gen)
         return
