@@ -155,19 +155,36 @@ constexpr int lpad(int x) { return x + (x >> 4); }
 template <int AR> using VT = std::conditional_t<AR >= 2, u32, u64>;
 
 // Per-modulus constants of the lazy butterflies (wave-uniform, live in SGPRs).
-struct QK {
+// UNIFORM: the modulus is the same for every lane of the wave (SGPRs), else per lane (VGPRs: several short
+// polynomials of different components in one wave).  Part of the type: the trims below are chosen on it.
+// LAUNDER: -q, -2q, -4q are made opaque, so that x + (-4q) stays ONE v_lshl_add_u64.  Off only in the register-tight
+// per-lane kernels (k_pow2's TIGHT): hipcc then keeps q, 2q, 4q alone and subtracts them with a borrow pair.
+template <bool UNIFORM, bool LAUNDER = true>
+struct QKx {
+  static constexpr bool uniform = UNIFORM;
   u64 q, nq, q2, nq2, q4, nq4;
-  // UNIFORM: the modulus is the same for every lane of the wave (SGPRs), else per lane (VGPRs)
-  template <bool UNIFORM>
-  __device__ __forceinline__ QK(const ModCtx& mc, std::bool_constant<UNIFORM> u) : QK(mc.q, u) {}
-  template <bool UNIFORM>
-  __device__ __forceinline__ QK(u64 q_, std::bool_constant<UNIFORM>) : q(q_), nq(0 - q_), q2(2 * q_), nq2(0 - 2 * q_), q4(4 * q_), nq4(0 - 4 * q_) {
+  __device__ __forceinline__ QKx(const ModCtx& mc, std::bool_constant<UNIFORM> u) : QKx(mc.q, u) {}
+  __device__ __forceinline__ QKx(u64 q_, std::bool_constant<UNIFORM>) : q(q_), nq(0 - q_), q2(2 * q_), nq2(0 - 2 * q_), q4(4 * q_), nq4(0 - 4 * q_) {
     // opaque to the optimiser: x + nq4 must stay ONE v_lshl_add_u64, not be rewritten as the
     // two-instruction borrow chain x - q4
+    static_assert(LAUNDER || !UNIFORM, "only the per-lane constants may be left visible");
     if constexpr (UNIFORM) asm volatile("" : "+s"(nq), "+s"(nq2), "+s"(nq4));
-    else asm volatile("" : "+v"(nq), "+v"(nq2), "+v"(nq4));
+    else if constexpr (LAUNDER) asm volatile("" : "+v"(nq), "+v"(nq2), "+v"(nq4));
   }
 };
+typedef QKx<true> QK;
+// The 64-bit class's lazy-range trims, v in [0,2m) -> [0,m).  Wave-uniform modulus: predicated on EXEC (csubx,
+// zq_dev.h; 2 VALU); per-lane modulus (several short polynomials per wave, T > 1): the select form (4 VALU).
+template <class K> inline constexpr bool trim_exec = LOLHIP_CSUB_EXEC && std::remove_cvref_t<K>::uniform;
+template <bool U, bool LD> __device__ __forceinline__ u64 trim2(u64 v, const QKx<U, LD>& k) {
+  if constexpr (trim_exec<QKx<U, LD>>) return csubx(v, k.q2, k.nq2); else return csubn(v, k.nq2);
+}
+template <bool U, bool LD> __device__ __forceinline__ u64 trim42(u64 v, const QKx<U, LD>& k) {       // [0,8q) -> [0,2q)
+  if constexpr (trim_exec<QKx<U, LD>>) return csubx2(v, k.q4, k.nq4, k.q2, k.nq2); else return csubn(csubn(v, k.nq4), k.nq2);
+}
+template <bool U, bool LD> __device__ __forceinline__ u64 trim21(u64 v, const QKx<U, LD>& k) {       // [0,4q) -> [0,q)
+  if constexpr (trim_exec<QKx<U, LD>>) return csubx2(v, k.q2, k.nq2, k.q, k.nq); else return csubn(csubn(v, k.nq2), k.nq);
+}
 struct QK32 {
   u32 q, q2, mu;       // mu = floor(2^32 / q): one-step Barrett of the wide lazy range of AR = 4
   u32 r, rp, nqinv;    // Shoup pair of 2^32 mod q and -q^-1 mod 2^32: the fused poly-mul's Montgomery pointwise product
@@ -175,7 +192,7 @@ struct QK32 {
   __device__ __forceinline__ QK32(const ModCtx& mc, std::bool_constant<UNIFORM>)
       : q((u32)mc.q), q2(2 * (u32)mc.q), mu((u32)(mc.mu >> 32)), r(mc.r32), rp(mc.r32p), nqinv((u32)mc.nqinv) {}
 };
-template <int AR> using QKT = std::conditional_t<AR >= 2, QK32, QK>;
+template <int AR, bool UNIFORM = true, bool LAUNDER = true> using QKT = std::conditional_t<AR >= 2, QK32, QKx<UNIFORM, LAUNDER>>;
 
 __device__ __forceinline__ u32 csub32(u32 x, u32 m) { return min(x, x - m); }        // x < 2m
 // w*y mod q in [0,2q) for any 32-bit y
@@ -228,7 +245,7 @@ __device__ __forceinline__ u32 shoup_pair(u32 d, u32 w, u32 wp, u32 q) {
 // WS: the twiddle is wave-uniform (SGPR operands in the 64-bit class's multiply chains, zq_dev.h)
 // L1: level 1 of the 64-bit class, whose X arrives in (0,2q) from from_i64_fwd: no conditional subtraction
 template <int AR, bool WS = false, bool L1 = false>
-__device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, const QKT<AR>& k) {
+__device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, const auto& k) {
   if constexpr (AR == 3) {
     const u32 x = csub32(X, k.q);                     // [0,2q) -> [0,q)
     const u32 t = csub32(shoup32(Y, w, wp, k.q), k.q);
@@ -255,10 +272,13 @@ __device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
   } else if constexpr (AR == 1) {
 #ifdef LH_ABL_NO_FWD_CSUB
     const u64 x = X;                                  // timing-only ablation: results are garbage
+    const u64 xn = shoup_acc<WS>(Y, w, wp, k.nq, x);
 #else
-    const u64 x = L1 ? X : csubn(X, k.nq4);           // [0,8q) -> [0,4q)
+    u64 x = X, xn;
+    if constexpr (L1) xn = shoup_acc<WS>(Y, w, wp, k.nq, x);    // x + t, t in [0,4q)
+    else if constexpr (trim_exec<decltype(k)>) xn = shoup_acc_csubx<WS, true>(Y, w, wp, k.nq, x, k.q4, k.nq4);   // the trim rides in the product's first block
+    else { x = csubn(X, k.nq4); xn = shoup_acc<WS>(Y, w, wp, k.nq, x); }                     // [0,8q) -> [0,4q)
 #endif
-    const u64 xn = shoup_acc<WS>(Y, w, wp, k.nq, x);  // x + t, t in [0,4q)
     const u64 z = shl1_add64u(x, k.q4);                // 2x + 4q
     X = xn;
     Y = z - xn;                                       // x - t + 4q
@@ -271,7 +291,7 @@ __device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
 }
 // inverse (Gentleman-Sande) butterfly:  X' = X + Y,  Y' = (X - Y) * w
 template <int AR, bool WS = false>
-__device__ __forceinline__ void bfly_inv(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, const QKT<AR>& k) {
+__device__ __forceinline__ void bfly_inv(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, const auto& k) {
   if constexpr (AR == 3) {                            // canonical in, canonical out
     const u32 s = X + Y;
     const u32 d = X - Y + k.q;
@@ -289,8 +309,8 @@ __device__ __forceinline__ void bfly_inv(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
   } else if constexpr (AR == 1) {
     const u64 s = add64(X, Y);                        // [0,8q)
     const u64 d = add64u(X, k.q4) - Y;                 // (0,8q)
-    X = csubn(s, k.nq4);
-    Y = shoup_acc<WS>(d, w, wp, k.nq, 0);
+    if constexpr (trim_exec<decltype(k)>) { X = s; Y = shoup_acc_csubx<WS, false>(d, w, wp, k.nq, X, k.q4, k.nq4); }
+    else { X = csubn(s, k.nq4); Y = shoup_acc<WS>(d, w, wp, k.nq, 0); }
   } else {
     const u64 s = X + Y;
     const u64 d = X - Y + k.q2;
@@ -301,7 +321,7 @@ __device__ __forceinline__ void bfly_inv(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
 // last inverse level: both outputs additionally scaled by mhat^-1 (crt.cpp:573-579).
 // (s0,s1) = Shoup pair of mhat^-1; (w, wp) = Shoup pair of psi_2^-1 * mhat^-1.
 template <int AR, bool WS = false>
-__device__ __forceinline__ void bfly_inv_last(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, VT<AR> s0, VT<AR> s1, const QKT<AR>& k) {
+__device__ __forceinline__ void bfly_inv_last(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> wp, VT<AR> s0, VT<AR> s1, const auto& k) {
   if constexpr (AR == 3) {
     const u32 s = X + Y;
     const u32 d = X - Y + k.q;
@@ -324,7 +344,7 @@ __device__ __forceinline__ void bfly_inv_last(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT
     Y = shoup_lazy(d, w, wp, k.q);
   }
 }
-template <int AR> __device__ __forceinline__ VT<AR> canon_fwd(VT<AR> v, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> canon_fwd(VT<AR> v, const auto& k) {
   if constexpr (AR == 3) return csub32(v, k.q);
   else if constexpr (AR == 2) return csub32(csub32(v, k.q2), k.q);
   else if constexpr (AR == 4) return csub32(v - __umulhi(v, k.mu) * k.q, k.q);     // any 32-bit v: v - floor(v mu / 2^32) q in [0,2q)
@@ -333,16 +353,16 @@ template <int AR> __device__ __forceinline__ VT<AR> canon_fwd(VT<AR> v, const QK
     return csubn(csubn(v, k.nq2), k.nq);
   }
 }
-template <int AR> __device__ __forceinline__ VT<AR> canon_inv(VT<AR> v, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> canon_inv(VT<AR> v, const auto& k) {
   if constexpr (AR == 3) return v;
   else if constexpr (AR == 2 || AR == 4) return csub32(v, k.q);
   else {
-    if constexpr (AR == 1) v = csubn(v, k.nq2);
-    return csubn(v, k.nq);
+    if constexpr (AR == 1) return trim21(v, k);
+    else return csubn(v, k.nq);
   }
 }
 // reference-style input in (-q, q) -> [0, q)
-template <int AR> __device__ __forceinline__ VT<AR> from_i64(i64 x, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> from_i64(i64 x, const auto& k) {
   if constexpr (AR >= 2) return (u32)x + (k.q & (u32)(x >> 63));
   else return canon_in(x, k.q);
 }
@@ -350,14 +370,14 @@ template <int AR> __device__ __forceinline__ VT<AR> from_i64(i64 x, const QKT<AR
 // 64-bit class: x + q is in (0,2q) for every x in (-q,q) (one v_lshl_add_u64 instead of a sign test and a masked
 // add), inside the [0,4q) a butterfly's X is trimmed to, so level 1 skips that trim (bfly_fwd L1).  32-bit classes: x + q is in (0,2q), inside [0,2q) (class 3), [0,4q) (class 2)
 // and the wide range of class 4 (inputs below 2q: 2q + 14 * 2q = 30q < 2^32 for q < 2^27).
-template <int AR> __device__ __forceinline__ VT<AR> from_i64_fwd(i64 x, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> from_i64_fwd(i64 x, const auto& k) {
   if constexpr (AR == 1) return add64u((u64)x, k.q);
   else if constexpr (AR >= 2) return (u32)x + k.q;
   else return from_i64<AR>(x, k);
 }
 // and into an inverse transform: 64-bit class range [0,4q): x + 2q is in (q,3q); classes 2 and 4 [0,2q): x + q;
 // class 3's inverse works on canonical values
-template <int AR> __device__ __forceinline__ VT<AR> from_i64_inv(i64 x, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> from_i64_inv(i64 x, const auto& k) {
   if constexpr (AR == 1) return add64u((u64)x, k.q2);
   else if constexpr (AR == 2 || AR == 4) return (u32)x + k.q;
   else return from_i64<AR>(x, k);
@@ -365,14 +385,14 @@ template <int AR> __device__ __forceinline__ VT<AR> from_i64_inv(i64 x, const QK
 // the operand of the fused poly-mul that waits in registers: canonical in the 64-bit classes; in the
 // 32-bit ones canonical AND multiplied by 2^32 (one Shoup product, valid for any lazy 32-bit value),
 // so that the pointwise product below is a bare Montgomery reduction
-template <int AR> __device__ __forceinline__ VT<AR> park_fwd(VT<AR> v, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> park_fwd(VT<AR> v, const auto& k) {
   if constexpr (AR >= 2) return csub32(shoup32(v, k.r, k.rp, k.q), k.q);
-  else if constexpr (AR == 1) return csubn(csubn(v, k.nq4), k.nq2);      // [0,8q) -> [0,2q): all the Montgomery product needs
+  else if constexpr (AR == 1) return trim42(v, k);      // [0,8q) -> [0,2q): all the Montgomery product needs
   else return canon_fwd<AR>(v, k);
 }
 // pointwise product of a parked a-hat and a lazy b-hat (forward range), any range the
 // inverse transform accepts
-template <int AR> __device__ __forceinline__ VT<AR> pmul(VT<AR> a, VT<AR> b, const ModCtx& mc, const QKT<AR>& k) {
+template <int AR> __device__ __forceinline__ VT<AR> pmul(VT<AR> a, VT<AR> b, const ModCtx& mc, const auto& k) {
   if constexpr (AR >= 2) {
     // a = a-hat 2^32 mod q < q; b < 4q (AR = 2), 2q (AR = 3), 29q (AR = 4): x = a b < q 2^32.
     // REDC: m = x (-q^-1) mod 2^32; (x + m q) / 2^32 = a-hat b-hat mod q, below 2q; 4 instructions
@@ -596,7 +616,7 @@ __device__ __forceinline__ void tw_fill_lds(V* dst, rsrc_t src, u32 comp, int n,
 #define LOLHIP_WS 1      // wave-uniform twiddles as SGPR operands (A/B switch)
 #endif
 template <int AR, bool INV, Lay A, int K, int HALF = -1>
-__device__ __forceinline__ void level(VT<AR> (&v)[E], const LevelTwT<VT<AR>>& t, const TwCtxT<VT<AR>>& tw, const QKT<AR>& qk) {
+__device__ __forceinline__ void level(VT<AR> (&v)[E], const LevelTwT<VT<AR>>& t, const TwCtxT<VT<AR>>& tw, const auto& qk) {
   constexpr int beta = A.reg[K];
 #ifdef LOLHIP_ABL_NO_BFLY     // ablation: keep the twiddles live, skip the arithmetic
 #pragma unroll
@@ -753,7 +773,7 @@ __device__ __forceinline__ void fetch4(LevelTwT<VT<AR>> (&t)[R], const TwCtxT<VT
 }
 // register-lean variant: fetch each level's twiddles right before the level (<= 32 VGPRs live)
 template <int AR, bool INV, Lay A, int K>
-__device__ __forceinline__ void level_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& tw, int xt, const QKT<AR>& qk) {
+__device__ __forceinline__ void level_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& tw, int xt, const auto& qk) {
   using LevelTw = LevelTwT<VT<AR>>;
   if constexpr (tw_distinct(A, K) == 8 && sizeof(VT<AR>) == 8) {
     // all eight twiddles distinct (32 VGPRs): LOLHIP_LEVEL_PARTS parts keep the live set small
@@ -765,14 +785,14 @@ __device__ __forceinline__ void level_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& 
   }
 }
 template <int AR, Lay A, int K0, int K1 = R>
-__device__ __forceinline__ void levels4_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& tw, int xt, const QKT<AR>& qk) {
+__device__ __forceinline__ void levels4_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& tw, int xt, const auto& qk) {
   if constexpr (K0 <= 0 && K1 > 0) level_jit<AR, false, A, 0>(v, tw, xt, qk);
   if constexpr (K0 <= 1 && K1 > 1) level_jit<AR, false, A, 1>(v, tw, xt, qk);
   if constexpr (K0 <= 2 && K1 > 2) level_jit<AR, false, A, 2>(v, tw, xt, qk);
   if constexpr (K0 <= 3 && K1 > 3) level_jit<AR, false, A, 3>(v, tw, xt, qk);
 }
 template <int AR, bool INV, Lay A, int K0, int K1 = R>
-__device__ __forceinline__ void levels4(VT<AR> (&v)[E], const LevelTwT<VT<AR>> (&t)[R], const TwCtxT<VT<AR>>& tw, const QKT<AR>& qk) {
+__device__ __forceinline__ void levels4(VT<AR> (&v)[E], const LevelTwT<VT<AR>> (&t)[R], const TwCtxT<VT<AR>>& tw, const auto& qk) {
   if constexpr (!INV) {
     if constexpr (K0 <= 0 && K1 > 0) level<AR, false, A, 0>(v, t[0], tw, qk);
     if constexpr (K0 <= 1 && K1 > 1) level<AR, false, A, 1>(v, t[1], tw, qk);
@@ -807,7 +827,7 @@ __device__ __forceinline__ int fresh(int x) {
 // issues the DMA, or the first such twiddle waits for the whole DMA to land.
 struct NoTop {};
 template <int AR, int L, Lay PREV, int SB = 0, bool LEAN = false, bool W16 = false, typename TOP = NoTop, bool TRUNC = false>
-__device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const QKT<AR>& qk,
+__device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const auto& qk,
                                               TOP* pre = nullptr) {
   constexpr bool PRE = !std::is_same_v<TOP, NoTop>;
   using LevelTw = LevelTwT<VT<AR>>;
@@ -897,7 +917,7 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
 // inverse transform; data arrives in Sched<L>::final_layout(), leaves in layout NEXT.
 // TRUNC: start at level L - 2 (the mirror of the truncated forward transform)
 template <int AR, int L, Lay NEXT, bool W16 = false, bool TRUNC = false>
-__device__ __forceinline__ void inv_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const QKT<AR>& qk) {
+__device__ __forceinline__ void inv_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const auto& qk) {
   using LevelTw = LevelTwT<VT<AR>>;
   using S = Sched<L, W16>;
   static_assert(!TRUNC || L >= 11, "the truncated inverse transform needs the G layout");
@@ -1010,7 +1030,7 @@ __device__ __forceinline__ void pow2_base4(u64 (&v)[E], const u64 (&va)[E], cons
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       a[k] = va[g | EK[k]];
-      y[k] = csubn(csubn(v[g | EK[k]], qk.nq4), qk.nq2);           // b_k: [0,8q) -> [0,2q)
+      y[k] = trim42(v[g | EK[k]], qk);                             // b_k: [0,8q) -> [0,2q)
     }
 #pragma unroll
     for (int k = 3; k >= 0; --k) {
@@ -1021,7 +1041,7 @@ __device__ __forceinline__ void pow2_base4(u64 (&v)[E], const u64 (&va)[E], cons
       // materialised here: left to hipcc, the reductions sink past the LDS twiddle refill loop to their first use in
       // the inverse and hold four 64-bit columns per output instead of one result (spills)
       asm volatile("" : "+v"(v[g | EK[k]]));
-      if (k) y[k] = csubn(shoup_acc<false>(y[k], zw, zwp, qk.nq, 0), qk.nq2);   // zeta b_k in [0,2q)
+      if (k) y[k] = trim2(shoup_acc<false>(y[k], zw, zwp, qk.nq, 0), qk);   // zeta b_k in [0,2q)
     }
   }
 }
@@ -1069,7 +1089,13 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
     b = (i64)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)b));
   }
   b0 = (i64)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(b0 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)b0));
-  const QKT<AR> qk(mod[t], std::bool_constant<(NT >= 64 || T1)>{});
+  // TIGHT: the 61-bit fused poly-mul with a per-lane modulus (32 <= n < 1024, T > 1: several components in one wave).  Its
+  // per-modulus constants, table pointers and scale pairs are VGPRs, and at the 128-VGPR budget it spilled 4 to 12 of them
+  // to scratch.  For it alone: a's transform fetches its twiddles level by level like b's (LEAN), whatever only the
+  // inverse reads (its table pointer, the four scale pairs) is set up after the pointwise product from an opaque copy
+  // of t, and -q, -2q, -4q are not laundered (QKx).  n = 16 fits as it is (114 VGPRs).
+  constexpr bool TIGHT = (AR == 1 && MODE == 2 && !(NT >= 64 || T1) && L >= 5);
+  const QKT<AR, (NT >= 64 || T1), !TIGHT> qk(mod[t], std::bool_constant<(NT >= 64 || T1)>{});
   // Buffer descriptors (wave-uniform): data windows start at the workgroup's first polynomial
   // and end at the end of the batch, so tail lanes of a packed launch read zeros and their
   // stores are dropped by the hardware range check.
@@ -1084,7 +1110,7 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
   tw.inv = __builtin_amdgcn_make_buffer_rsrc((void*)tw_inv, 0, (u32)T * n * TWB, 0x00020000);
   tw.comp = (u32)t * (u32)n * TWB;
   tw.pf = tw_fwd + (size_t)t * n * 2;
-  tw.pi = tw_inv + (size_t)t * n * 2;
+  if constexpr (!TIGHT) tw.pi = tw_inv + (size_t)t * n * 2;
   tw.lds_tw = lds_tw;
   // levels 5..9 read their twiddles from LDS; (re)filled before the transform direction changes.
   // Visibility: for L > 10 a workgroup barrier follows before first use; for L <= 10 the
@@ -1093,10 +1119,12 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
   constexpr int SC = (MODE == 2 && AR == 1) ? 4 : 0;       // the 2^64-scaled pairs: see pmul
   // the truncated route's (n/4)^-1 2^64 pairs follow the [T][8] block as [T][4] (plan.cpp)
   const V* scp = TR ? scale + (size_t)T * 8 + (size_t)t * 4 : scale + (size_t)t * 8 + SC;
-  tw.sc0 = scp[0];
-  tw.sc1 = scp[1];
-  tw.l1w = scp[2];
-  tw.l1wp = scp[3];
+  if constexpr (!TIGHT) {
+    tw.sc0 = scp[0];
+    tw.sc1 = scp[1];
+    tw.l1w = scp[2];
+    tw.l1wp = scp[3];
+  }
 
   constexpr Lay LIO = S::io();              // global I/O of powerful-basis data
   constexpr Lay LFIN = S::final_layout();   // where the forward transform leaves the CRT coefficients
@@ -1119,7 +1147,7 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
     const rsrc_t src = (MODE == 2) ? ra : ry;
     load_poly<LIO, T1>(src, off_io, uT8, [&](int e, u64 x) { v[e] = from_i64_fwd<AR>((i64)x, qk); });
     LH_STAMP(1);
-    fwd_transform<AR, L, LIO, 0, false, T1, NoTop, TR>(v, lds, tw, tau, qk);
+    fwd_transform<AR, L, LIO, 0, TIGHT, T1, NoTop, TR>(v, lds, tw, tau, qk);
     if constexpr (MODE == 0) LH_STAMP(20);
   }
   if constexpr (MODE == 2) {
@@ -1150,7 +1178,9 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
       fwd_transform<AR, L, LIO, 10, true, T1, NoTop, TR>(v, lds, tw, tau, qk);
     }
     LH_STAMP(19);
-    const ModCtx mc = mod[t];     // re-read here: keeping it live across the transforms costs registers
+    // TIGHT: from an opaque copy of t, so that no per-lane address is formed (and held) above this point
+    const int tl = TIGHT ? fresh(t) : t;
+    const ModCtx mc = mod[tl];    // re-read here: keeping it live across the transforms costs registers
     if constexpr (TR) {
       pow2_base4<LFIN>(v, va, tw, xthr<LFIN>(fresh(tau)), mc, qk);   // squaring: v still holds a-hat (lazy)
     } else {
@@ -1173,6 +1203,15 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
     LH_STAMP(21);
   } else {
     LH_STAMP(23);
+    if constexpr (TIGHT) {
+      const int tl = fresh(t);      // as above: the addresses are formed here
+      tw.pi = tw_inv + (size_t)tl * n * 2;
+      const V* sc = scale + (size_t)tl * 8 + SC;
+      tw.sc0 = sc[0];
+      tw.sc1 = sc[1];
+      tw.l1w = sc[2];
+      tw.l1wp = sc[3];
+    }
     inv_transform<AR, L, LIO, T1, TR>(v, lds, tw, tau, qk);
     LH_STAMP(24);
     store_poly<LIO, T1>(ry, off_io, uT8, [&](int e) { return (u64)canon_inv<AR>(v[e], qk); });

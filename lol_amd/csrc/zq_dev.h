@@ -128,6 +128,64 @@ LH_D u64 csubn(u64 x, u64 negm) {
   return ((int)hi32(t) < 0) ? x : t;
 }
 
+// ---- the same trim predicated on EXEC (LOLHIP_CSUB_EXEC) ---------------------------------------
+// x - m where x >= m (unsigned, any 64-bit x) else x: the compare narrows the wave's lane mask to the lanes that
+// subtract, the add runs in place under that mask, and the mask is put back from the pair saved in the same block.
+// Two VALU instructions instead of the select form's four (add, compare, two v_cndmask) and no second candidate
+// register.  ONLY for wave-uniform m / negm = -m (SGPR operands, one per instruction: the constant-bus rule); the
+// compiler never sees a modified EXEC.  LH_CSUBX_TAIL pads a block that ENDS in a trim: gfx940-class parts want 4
+// wait states between a VALU write of EXEC and v_readlane / v_writelane (hipcc's SGPR spill lanes) and 2 between a
+// VALU write of a VGPR and a v_permlane*_swap of it, and the hazard recogniser does not look into asm blocks.
+#ifndef LOLHIP_CSUB_EXEC
+#define LOLHIP_CSUB_EXEC 1      // 0: the select form everywhere (A/B switch)
+#endif
+#ifndef LOLHIP_CSUBX_PAD
+#define LOLHIP_CSUBX_PAD 1      // 0: timing-only A/B of the unpadded tail
+#endif
+#if LOLHIP_CSUBX_PAD
+#define LH_CSUBX_TAIL "\n\ts_nop 1"
+#else
+#define LH_CSUBX_TAIL ""
+#endif
+// %[x] "+v", %[sv] "=&s" scratch pair, %[m] / %[nm] "s"
+#define LH_CSUBX(x, sv, m, nm)                                                                       \
+  "s_mov_b64 %[" sv "], exec\n\t"                                                                     \
+  "v_cmpx_ge_u64 vcc, %[" x "], %[" m "]\n\t"                                                         \
+  "v_lshl_add_u64 %[" x "], %[" x "], 0, %[" nm "]\n\t"                                                \
+  "s_mov_b64 exec, %[" sv "]"
+// the same with EXEC saved by the caller (exec_save below): %[sv] "s" input
+#define LH_CSUBX_SAVED(x, sv, m, nm)                                                                 \
+  "v_cmpx_ge_u64 vcc, %[" x "], %[" m "]\n\t"                                                         \
+  "v_lshl_add_u64 %[" x "], %[" x "], 0, %[" nm "]\n\t"                                                \
+  "s_mov_b64 exec, %[" sv "]"
+LH_D u64 csubx(u64 x, u64 m, u64 negm) {
+  u64 sv;
+  asm(LH_CSUBX("x", "sv", "m", "nm") LH_CSUBX_TAIL
+      : [x] "+v"(x), [sv] "=&s"(sv) : [m] "s"(m), [nm] "s"(negm) : "vcc");
+  return x;
+}
+// The wave's lane mask, for a group of trims that share one save.  The trims must sit in the same control-flow
+// region as the save (volatile: it is not moved across a branch that changes EXEC).
+LH_D u64 exec_save() {
+  u64 sv;
+  asm volatile("s_mov_b64 %0, exec" : "=s"(sv));
+  return sv;
+}
+LH_D u64 csubx(u64 x, u64 m, u64 negm, u64 saved_exec) {
+  asm(LH_CSUBX_SAVED("x", "sv", "m", "nm") LH_CSUBX_TAIL
+      : [x] "+v"(x) : [sv] "s"(saved_exec), [m] "s"(m), [nm] "s"(negm) : "vcc");
+  return x;
+}
+// two trims back to back (m1 then m2, e.g. 4q then 2q): EXEC is restored between them, because the second compare
+// has to see every lane
+LH_D u64 csubx2(u64 x, u64 m1, u64 negm1, u64 m2, u64 negm2) {
+  u64 sv;
+  asm(LH_CSUBX("x", "sv", "m1", "nm1") "\n\t"
+      LH_CSUBX_SAVED("x", "sv", "m2", "nm2") LH_CSUBX_TAIL
+      : [x] "+v"(x), [sv] "=&s"(sv) : [m1] "s"(m1), [nm1] "s"(negm1), [m2] "s"(m2), [nm2] "s"(negm2) : "vcc");
+  return x;
+}
+
 // init + w*y - Q*q (mod 2^64) with an APPROXIMATE quotient
 //   Q = wp.hi*y.hi + hi32(wp.hi*y.lo) + hi32(wp.lo*y.hi)  in {floor(wp*y/2^64) - 2 .. same}
 // so (result - init) = w*y mod q + {0..3}*q  in [0, 4q) for any 64-bit y.  7 mads + 2
@@ -221,6 +279,46 @@ LH_D u64 shoup_acc(u64 y, u64 w, u64 wp, u64 nq, u64 init) {
   u32 th = hi32(t) + lo32(h);
   asm("" : "+v"(th));          // keeps it ONE v_add_u32 (else: t + (h << 32) as v_mov + v_lshl_add_u64)
   return ((u64)th << 32) | lo32(t);
+#endif
+}
+
+// shoup_acc with a trim of x (csubx(x, m, negm), wave-uniform m) at the head of its first asm statement: the trim
+// does not depend on the quotient, and inside the block it costs no asm-block boundary and needs no tail padding
+// (five multiplies follow it).  INIT_X: the trimmed x is also the product's addend (forward butterfly), else 0.
+template <bool WS, bool INIT_X>
+LH_D u64 shoup_acc_csubx(u64 y, u64 w, u64 wp, u64 nq, u64& x, u64 m, u64 negm) {
+#if LOLHIP_ASM_MAD == 3
+  u64 Q, t, h, sv;
+  u32 ah, bh;
+#define LH_SHOUP_BLOCKS_X(WC)                                                                        \
+  asm(LH_CSUBX("x", "sv", "m", "nm") "\n\t"                                                          \
+      "v_mul_hi_u32 %[ah], %[wph], %[yl]\n\t"                                                        \
+      "v_mul_hi_u32 %[bh], %[wpl], %[yh]\n\t"                                                        \
+      "v_mad_u64_u32 %[Q], vcc, %[wph], %[yh], 0\n\t"                                                \
+      "v_mad_u64_u32 %[Q], vcc, %[ah], 1, %[Q]\n\t"                                                  \
+      "v_mad_u64_u32 %[Q], vcc, %[bh], 1, %[Q]"                                                      \
+      : [Q] "=&v"(Q), [ah] "=&v"(ah), [bh] "=&v"(bh), [x] "+v"(x), [sv] "=&s"(sv)                    \
+      : [wph] WC(hi32(wp)), [wpl] WC(lo32(wp)), [yl] "v"(lo32(y)), [yh] "v"(hi32(y)),                \
+        [m] "s"(m), [nm] "s"(negm)                                                                   \
+      : "vcc");                                                                                      \
+  asm("v_mad_u64_u32 %0, vcc, %2, %4, %10\n\t"                                                       \
+      "v_mad_u64_u32 %1, vcc, %2, %5, 0\n\t"                                                         \
+      "v_mad_u64_u32 %0, vcc, %6, %8, %0\n\t"                                                        \
+      "v_mad_u64_u32 %1, vcc, %3, %4, %1\n\t"                                                        \
+      "v_mad_u64_u32 %1, vcc, %6, %9, %1\n\t"                                                        \
+      "v_mad_u64_u32 %1, vcc, %7, %8, %1"                                                            \
+      : "=&v"(t), "=&v"(h)                                                                           \
+      : WC(lo32(w)), WC(hi32(w)), "v"(lo32(y)), "v"(hi32(y)), "v"(lo32(Q)), "v"(hi32(Q)),            \
+        "s"(lo32(nq)), "s"(hi32(nq)), "v"(INIT_X ? x : (u64)0)                                       \
+      : "vcc")
+  if constexpr (WS) { LH_SHOUP_BLOCKS_X("s"); } else { LH_SHOUP_BLOCKS_X("v"); }
+#undef LH_SHOUP_BLOCKS_X
+  u32 th = hi32(t) + lo32(h);
+  asm("" : "+v"(th));
+  return ((u64)th << 32) | lo32(t);
+#else
+  x = csubx(x, m, negm);
+  return shoup_acc<WS>(y, w, wp, nq, INIT_X ? x : (u64)0);
 #endif
 }
 
