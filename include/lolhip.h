@@ -453,6 +453,67 @@ LOLHIP_API int lolhip_mul_public_batch(const lolhip_plan *pq, const lolhip_ext *
                                        int64_t a_stride, int64_t p, const int64_t *cs, int ncs, int cs_shared,
                                        int64_t *out, int64_t *work, int64_t B);
 
+/* Ciphertext modSwitch and multi-hop tunnelling (lol-apps SymmSHE.hs:236-246, HomomPRF.hs:153-155, 427-431;
+ * lol Prelude.hs:227-232, 274-308).
+ * lolhip_modswitch_batch: modSwitch of CT enc k l c from the moduli of `from` to those of `to`.  Both plans have the
+ *   same index (same prime powers, same order); to's moduli are a suffix of from's (down: the first d = T - T' moduli
+ *   are dropped, 1 <= d <= 5), from's are a suffix of to's (up: u = T' - T moduli are added in front, 1 <= u <= 5), or
+ *   the lists are equal (toMSD alone).  cs [ncs][B][n][T] in the powerful basis (cs_crt = 0) or the CRT basis
+ *   (cs_crt = 1), residues in (-q_t, q_t); it is only read.  out [ncs][B][n][T'] canonical, powerful basis
+ *   (out_crt = 0) or CRT basis (out_crt = 1); it must not overlap cs or work.  enc 0 = LSD, 1 = MSD; the result is
+ *   always MSD with *l_out = l mod p for MSD input and (-Q_from mod p) l mod p for LSD input (lolhip_encode_scales);
+ *   k is unchanged.  c_0 is rescaled in the decoding basis, the other components in the powerful basis (modSwitchMSD).
+ *   Down iterates the reference's one-step rule, which is not one rounding by q_0 ... q_{d-1}: for i = 0 .. d-1,
+ *   z = lift c_i (a for 2a < q_i, else a - q_i) and c_s <- q_i^-1 (c_s - z) mod q_s for every s > i.  Up puts 0 into
+ *   the new leading components and multiplies every old one by the product of the new moduli.
+ *   Launch plan: crtInv on from (cs_crt) -> lInv on from over c_0 -> k_modswitch (toMSD scale, down / up, one pass)
+ *   -> l on to over c_0 -> crt on to (out_crt).  With equal lists (the scale alone, which commutes with l / lInv) the
+ *   two passes over c_0 are left out.
+ *   work: lolhip_modswitch_work_len(from, to, ncs, B) = ncs B n T int64 of device scratch (0 for B = 0; a negative
+ *   status for bad arguments): the copy of cs that crtInv / lInv transform.
+ * Status: LOLHIP_ERR_INVALID for NULL pointers, ncs < 1, B < 0, enc not 0 / 1, plans of different indices, moduli lists
+ *   that are not suffix-related, more than 5 moduli dropped or added, T or T' > 16; LOLHIP_ERR_MODULUS for p < 2 (or
+ *   p >= 2^62), LSD input with p not invertible mod some q_t, a dropped modulus not invertible mod a kept one;
+ *   LOLHIP_ERR_NO_CRT for a CRT-basis side whose plan has no CRT basis; LOLHIP_ERR_NO_DEVICE on a host-only plan;
+ *   LOLHIP_ERR_DEVICE as elsewhere.  Every one is decided on the host before any launch: out and *l_out are then not
+ *   written.  A failing launch (LOLHIP_ERR_HIP) leaves out undefined and *l_out unwritten.  The call does not allocate
+ *   or synchronise. */
+LOLHIP_API int64_t lolhip_modswitch_work_len(const lolhip_plan *from, const lolhip_plan *to, int ncs, int64_t B);
+LOLHIP_API int lolhip_modswitch_batch(const lolhip_plan *from, const lolhip_plan *to, void *stream, const int64_t *cs,
+                                      int ncs, int cs_crt, int enc, int64_t l, int64_t p, int64_t *out, int out_crt,
+                                      int64_t *l_out, int64_t *work, int64_t B);
+/* tunnelH (HomomPRF.hs:427-431) = roundCTDown . roundCTDown . tunnelInternal hints . roundCTUp as one call.
+ * lolhip_tunnel_chain_create: hop i is lolhip_tunnel_batch(x_er[i], x_es[i], ys_crt[i], hints[i], base) from R'_i (the
+ *   high plan of x_er[i]) to S'_i (the high plan of x_es[i]); ys_crt[i] and hints[i] are DEVICE pointers the chain
+ *   borrows (layouts of lolhip_tunnel_batch; they must outlive the chain's calls), the exts and plans are borrowed too.
+ *   All hops share one moduli list, the up list; S'_i and R'_{i+1} have the same index and moduli.  p_in: a plan of
+ *   R'_0's index whose moduli are a suffix of the up list (u = 0..5 moduli are added on entry); p_out: a plan of the
+ *   last S' index whose moduli are a suffix of the up list (d = 0..5 are dropped on exit).  nhops = 0: p_in and p_out
+ *   have the same index and the call is lolhip_modswitch_batch(p_in, p_out).  Create validates and copies host
+ *   metadata only.
+ * lolhip_tunnel_chain_batch: cs [2][B][n_R'][T_in], a linear ciphertext with k = 0 (absorbGFactors stays the caller's
+ *   job: lolhip_divgpow_batch on 1 and lolhip_mul_public_batch, as above), bases and enc / l / p as for
+ *   lolhip_modswitch_batch; out [2][B][n_S'][T_out], MSD, *l_out as there.  Steps: modSwitch up from p_in (this is also
+ *   toMSD) -> per hop the tunnel, and between hops one crtInv over both components and lInv over c_0 -> ONE modSwitch
+ *   down by d after the last hop (successive roundCTDowns are one d-step pass: both act coefficient-wise in the same
+ *   bases).  work: lolhip_tunnel_chain_work_len(c, B) int64 = 4 B n_max T_up (two ciphertext buffers, n_max over R'_0
+ *   and every S'_i) + the largest of lolhip_modswitch_work_len(p_in, R'_0, 2, B) and the hops'
+ *   lolhip_tunnel_work_len; for nhops = 0 it is lolhip_modswitch_work_len(p_in, p_out, 2, B).
+ * Status: as for the pieces; LOLHIP_ERR_INVALID also for nhops < 0, mismatched neighbouring hops, hops over other
+ *   moduli than the first, plans not of the end rings.  Nothing allocates or synchronises after create.  Every status
+ *   but a failing launch is decided on the host before the first launch: out and *l_out are then not written.  A
+ *   launch that fails mid-chain (LOLHIP_ERR_HIP, a transform's ring allocation included) leaves out undefined and *l_out
+ *   unwritten. */
+typedef struct lolhip_tunnel_chain lolhip_tunnel_chain;
+LOLHIP_API int lolhip_tunnel_chain_create(int nhops, const lolhip_ext *const *x_er, const lolhip_ext *const *x_es,
+                                          const int64_t *const *ys_crt, const int64_t *const *hints, int64_t base,
+                                          const lolhip_plan *p_in, const lolhip_plan *p_out, lolhip_tunnel_chain **out);
+LOLHIP_API void lolhip_tunnel_chain_destroy(lolhip_tunnel_chain *c);
+LOLHIP_API int64_t lolhip_tunnel_chain_work_len(const lolhip_tunnel_chain *c, int64_t B);
+LOLHIP_API int lolhip_tunnel_chain_batch(const lolhip_tunnel_chain *c, void *stream, const int64_t *cs, int cs_crt, int enc,
+                                         int64_t l, int64_t p, int64_t *out, int out_crt, int64_t *l_out, int64_t *work,
+                                         int64_t B);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

@@ -132,6 +132,16 @@ def lib():
     L.lolhip_public_work_len.restype = i64
     L.lolhip_add_public_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp, ci, ci, ci, ci, i64, i64, i64, vp, _i64p, vp, i64]
     L.lolhip_mul_public_batch.argtypes = [vp, vp, vp, vp, i64, i64, vp, ci, ci, vp, vp, i64]
+    L.lolhip_modswitch_work_len.argtypes = [vp, vp, ci, i64]
+    L.lolhip_modswitch_work_len.restype = i64
+    L.lolhip_modswitch_batch.argtypes = [vp, vp, vp, vp, ci, ci, ci, i64, i64, vp, ci, _i64p, vp, i64]
+    L.lolhip_tunnel_chain_create.argtypes = [ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64, vp, vp,
+                                             C.POINTER(vp)]
+    L.lolhip_tunnel_chain_destroy.argtypes = [vp]
+    L.lolhip_tunnel_chain_destroy.restype = None
+    L.lolhip_tunnel_chain_work_len.argtypes = [vp, i64]
+    L.lolhip_tunnel_chain_work_len.restype = i64
+    L.lolhip_tunnel_chain_batch.argtypes = [vp, vp, vp, ci, ci, i64, i64, vp, ci, _i64p, vp, i64]
     L.lolhip_chacha20_block.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.lolhip_chacha20_block.restype = None
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
@@ -982,6 +992,25 @@ class Plan:
         cs, _, l = self.toMSD(cs, p, enc, l, stream=stream)
         return cs, "MSD", self._decode(l, p) % int(p2)
 
+    def modSwitch(self, to, cs, p, enc="LSD", l=1, cs_crt=False, out_crt=False, stream=None):
+        """modSwitch (SymmSHE.hs:236-246) from this plan's moduli to those of `to`, a Plan of the same index whose moduli
+        are a suffix of these (up to 5 dropped), of which these are a suffix (up to 5 added), or the same (toMSD):
+        lolhip_modswitch_batch, one pass for the encoding scale and the whole rescale.  cs [ncs][B][n][T] in the powerful
+        basis (or the CRT basis with cs_crt) -> (out [ncs][B][n][T'] in the basis out_crt asks for, "MSD", l')."""
+        import torch
+        host, cs, ncs, B = self._cs(cs)
+        L, lo = lib(), C.c_int64(0)
+        args = (ncs, int(cs_crt), self._enc(enc), int(l), int(p))
+        _check(L.lolhip_modswitch_batch(self._h, to._h, None, None, *args, None, int(out_crt), C.byref(lo), None, 0))
+        host, (cs,) = self._stage(cs) if host else (False, (cs,))
+        wl = L.lolhip_modswitch_work_len(self._h, to._h, ncs, B)
+        _check(min(wl, 0))
+        work = torch.empty((max(wl, 1),), dtype=torch.int64, device=cs.device)
+        out = torch.empty((ncs, B, to.n, to.T), dtype=torch.int64, device=cs.device)
+        _check(L.lolhip_modswitch_batch(self._h, to._h, _stream(stream), _devptr(cs), *args, _devptr(out), int(out_crt),
+                                        C.byref(lo), _devptr(work), B))
+        return self._unstage(host, out), "MSD", int(lo.value)
+
     def absorbGFactors(self, cs, k, pp, stream=None):
         """absorbGFactors (SymmSHE.hs:464-473) of a CRT-basis ciphertext: every c_i times decode'(divG^k 1), divG over
         pp (the Plan of this index over p alone) -> (cs, 0)"""
@@ -1120,6 +1149,87 @@ class Ext:
     def embedPow(self, x, out=None, stream=None): return self._run(EXT_EMBED_POW, "embed_pow", x, True, out, stream)
     def embedDec(self, x, out=None, stream=None): return self._run(EXT_EMBED_DEC, "embed_dec", x, True, out, stream)
     def embedCRT(self, x, out=None, stream=None): return self._run(EXT_EMBED_CRT, "embed_crt", x, True, out, stream)
+
+
+class TunnelChain:
+    """tunnelH (HomomPRF.hs:427-431): roundCTUp, the tunnel hops and the roundCTDowns as one call
+    (lolhip_tunnel_chain_batch).  exts_er[i] / exts_es[i]: the Exts E'_i in R'_i / E'_i in S'_i of hop i, all over one
+    moduli list (the up list); ys[i] [rel_i][n_S][T] and hints[i] [rel_i][L][2][n_S][T]: CUDA tensors as Ext.tunnel
+    takes them (kept alive here); p_in / p_out: Plans of the first R' / last S' index over a suffix of the up list."""
+
+    def __init__(self, exts_er, exts_es, ys, hints, base, p_in: Plan, p_out: Plan):
+        self.exts_er, self.exts_es, self.ys, self.hint_slabs = list(exts_er), list(exts_es), list(ys), list(hints)
+        self.base, self.p_in, self.p_out = int(base), p_in, p_out
+        n = len(self.exts_er)
+        if not (len(self.exts_es) == len(self.ys) == len(self.hint_slabs) == n):
+            raise ValueError("one ext pair, one ys table and one hint slab per hop")
+        arr = lambda vals: (C.c_void_p * max(n, 1))(*vals)
+        h = C.c_void_p()
+        _check(lib().lolhip_tunnel_chain_create(n, arr([x._h for x in self.exts_er]), arr([x._h for x in self.exts_es]),
+                                                arr([_devptr(y) for y in self.ys]), arr([_devptr(x) for x in self.hint_slabs]),
+                                                self.base, p_in._h, p_out._h, C.byref(h)), "tunnel_chain_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.lolhip_tunnel_chain_destroy(h)
+
+    def workLen(self, B):
+        w = lib().lolhip_tunnel_chain_work_len(self._h, int(B))
+        _check(min(w, 0))
+        return w
+
+    def __call__(self, cs, p, enc="LSD", l=1, cs_crt=False, out_crt=False, stream=None):
+        """cs [2][B][n_R'][T_in], a linear ciphertext with k = 0 (Plan.absorbGFactors first otherwise), powerful basis or
+        CRT basis (cs_crt) -> (out [2][B][n_S'][T_out], "MSD", l')."""
+        import torch
+        host, cs, ncs, B = self.p_in._cs(cs)
+        if ncs != 2:
+            raise LolHipError(ERR_INVALID, "tunnelH takes a linear ciphertext")
+        L, lo = lib(), C.c_int64(0)
+        args = (int(cs_crt), Plan._enc(enc), int(l), int(p))
+        _check(L.lolhip_tunnel_chain_batch(self._h, None, None, *args, None, int(out_crt), C.byref(lo), None, 0))
+        host, (cs,) = Plan._stage(cs) if host else (False, (cs,))
+        work = torch.empty((max(self.workLen(B), 1),), dtype=torch.int64, device=cs.device)
+        out = torch.empty((2, B, self.p_out.n, self.p_out.T), dtype=torch.int64, device=cs.device)
+        _check(L.lolhip_tunnel_chain_batch(self._h, _stream(stream), _devptr(cs), *args, _devptr(out), int(out_crt),
+                                           C.byref(lo), _devptr(work), B))
+        return Plan._unstage(host, out), "MSD", int(lo.value)
+
+    @staticmethod
+    def hints(exts_er, exts_es, exts_f, funcs, s_in_crt, p, svar, base, key=None, ctr=0, stream=None):
+        """tunnelHintChain (HomomPRF.hs:400-411) on the device.  Per hop i: a fresh key of S'_i by errorRounded svar
+        (genSKWithVar), ys_i = crt (reduce (embed (liftPow f_i))) (extendLin, Linear.hs:113-119) and Ext.tunnelHint.
+        exts_er / exts_es as for the chain; exts_f[i]: the Ext from (S_i, up list) to S'_i (None for S = S');
+        funcs[i] [rel_i][n_S_i]: the values of the linear function f_i on the relative decoding basis, residues mod p
+        in the powerful basis of S_i; s_in_crt [n_R'][T]: the key of R'_0 in the CRT basis.  Stream items: the key of
+        hop i is errorRounded's item ctr (domain 2), its hint rows are items ctr .. ctr + rel_i L - 1 of the hint domains
+        (3 / 4), and ctr then advances by rel_i L, as include/lolhip.h prescribes.
+        Returns (hints, ys, last key [n_S'][T] in the CRT basis, the next free ctr)."""
+        import torch
+        kb = Plan._key(key)
+        s_in = torch.from_numpy(np.ascontiguousarray(s_in_crt, dtype=np.int64)).cuda() if isinstance(s_in_crt, np.ndarray) else s_in_crt
+        out_h, out_y = [], []
+        for er, es, xf, f in zip(exts_er, exts_es, exts_f, funcs):
+            S = es.hi
+            qs = torch.tensor(S.qs, dtype=torch.int64, device=s_in.device)
+            rel = er.hi.n // er.lo.n
+            sk = S.errorRounded(svar, 1, key=kb, ctr=ctr, stream=stream)                      # [1][n_S] decoding basis
+            s_out = torch.remainder(sk.reshape(1, S.n, 1), qs).contiguous()
+            S.crt(S.l(s_out, stream), stream)
+            f = torch.from_numpy(np.ascontiguousarray(f, dtype=np.int64)).to(s_in.device) if isinstance(f, np.ndarray) else f
+            f = torch.remainder(f.reshape(rel, -1), int(p))
+            f = torch.where(2 * f >= int(p), f - int(p), f)                                     # liftPow: centred
+            y = torch.remainder(f.reshape(rel, -1, 1), qs).contiguous()                         # reduce
+            y = S.crt(y if xf is None else xf.embedPow(y, stream=stream), stream)
+            L = S.decomposeLen(base)
+            out_h.append(er.tunnelHint(es, y, s_in.reshape(-1), s_out.reshape(-1), svar, base, key=kb, ctr=ctr,
+                                       stream=stream))
+            out_y.append(y)
+            ctr += rel * L
+            s_in = s_out.reshape(S.n, S.T)
+        return out_h, out_y, s_in, ctr
 
 
 # ---- key-homomorphic ring PRF (lol-apps KeyHomomorphicPRF.hs) -------------------------------

@@ -2,7 +2,8 @@
 """tools/bench_pipelines.py — throughput of the SymmSHE pipeline kernels on one MI355X
 (BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone), of encrypt / errorRounded
 (`--encrypt`: that leg alone), of the key-switch / tunnel hints (`--kshint`: that leg alone) and of the key-homomorphic
-ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q = 2^k alone).  Operands resident in HBM, HIP events on
+ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q = 2^k alone), of ciphertext modSwitch
+(`--modswitch`: that leg alone) and of multi-hop tunnelling (`--tunnel-chain`: that leg alone).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -336,8 +337,135 @@ def public_leg(gen):
     report("ct_add", f"m'=2^15 T=4 59-bit B={B} 2+2 comps", ms, B, 6 * slab)
 
 
+ZQ5 = [2149056001, 25159681, 19918081, 19393921, 18869761]      # HomomPRFParams.hs ZQ5; ZQ4 and ZQ3 are its suffixes
+
+
+def modswitch_leg(gen):
+    """Ciphertext modSwitch (lolhip_modswitch_batch) against the composition callers used before: lolhip_ct_lincomb_batch
+    for toMSD, then one lolhip_rescale_drop_batch per component per dropped modulus on successive plans (with the same
+    crtInv / lInv / l / crt around it where the shape asks for them: no l / lInv at m' = 2^k, whose programs are empty
+    and which the one call skips too).  The two routes alternate in one process; the median of three rounds is reported.  alg_bytes: (T + T') 8 bytes per coefficient per component."""
+    import ctypes
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    lo_out = ctypes.c_int64(0)
+    q59 = good_qs(2 ** 15, 2 ** 59, 4)
+    # (label, index, moduli, moduli kept, B, CRT basis in and out, p)
+    for label, m, qs, keep, B, crt, p in (("m'=2^15 59-bit", 2 ** 15, q59, 3, 256, 0, 65537),
+                                           ("m'=2^15 59-bit", 2 ** 15, q59, 2, 256, 0, 65537),
+                                           ("m'=9*5*7*13 ZQ5->ZQ3", 9 * 5 * 7 * 13, ZQ5, 3, 4096, 1, 8)):
+        T = len(qs)
+        plans = [lol_amd.Plan.for_index(m, qs[i:]) for i in range(T - keep + 1)]
+        F, G = plans[0], plans[-1]
+        n, ncs = F.n, 2
+        cs = rnd(gen, qs, ncs, B, n)
+        out = torch.empty((ncs, B, n, keep), dtype=torch.int64, device="cuda")
+        work = torch.empty((max(L.lolhip_modswitch_work_len(F._h, G._h, ncs, B), 1),), dtype=torch.int64, device="cuda")
+        tmp = [torch.empty((ncs, B, n, T - i), dtype=torch.int64, device="cuda") for i in range(T - keep + 1)]
+        zq = (ctypes.c_int64 * T)(*F.encodeScales(p, True)[0])
+        dec = m & (m - 1) != 0                  # the decoding basis differs from the powerful one
+
+        def fused():
+            rc = L.lolhip_modswitch_batch(F._h, G._h, st, ptr(cs), ncs, crt, 0, 1, p, ptr(out), crt, ctypes.byref(lo_out),
+                                          ptr(work), B)
+            assert rc == 0, rc
+
+        def composed():
+            L.lolhip_ct_lincomb_batch(F._h, st, ptr(cs), ncs, zq, None, 0, None, ptr(tmp[0]), B)
+            if crt:
+                L.lolhip_crtinv_batch(F._h, st, ptr(tmp[0]), ncs * B)
+            if dec:
+                L.lolhip_linv_batch(F._h, st, ptr(tmp[0]), B)
+            for i in range(T - keep):
+                for c in range(ncs):
+                    L.lolhip_rescale_drop_batch(plans[i]._h, st, ptr(tmp[i][c]), ptr(tmp[i + 1][c]), B)
+            if dec:
+                L.lolhip_l_batch(G._h, st, ptr(tmp[-1]), B)
+            if crt:
+                L.lolhip_crt_batch(G._h, st, ptr(tmp[-1]), ncs * B)
+
+        fused(); composed()
+        torch.cuda.synchronize()
+        assert torch.equal(out, tmp[-1]), "the two routes differ"
+        t_f, t_c = [], []
+        for _ in range(3):
+            t_f.append(timeit(fused))
+            t_c.append(timeit(composed))
+        alg = (T + keep) * 8 * ncs * B * n
+        cfg = f"{label} T={T}->{keep} B={B} ncs={ncs} {'CRT in/out' if crt else 'powerful basis'} LSD p={p}"
+        report("modswitch", cfg, statistics.median(t_f), B, alg, note="one lolhip_modswitch_batch call")
+        report("modswitch_composed", cfg, statistics.median(t_c), B, alg,
+               note="ct_lincomb + one rescale_drop per component per dropped modulus (+ the same transforms)")
+        del cs, out, work, tmp
+    c = rnd(gen, q59, 256, 2 ** 14)
+    o = torch.empty((256, 2 ** 14, 3), dtype=torch.int64, device="cuda")
+    P = lol_amd.Plan.for_index(2 ** 15, q59)
+    ms = timeit(lambda: L.lolhip_rescale_drop_batch(P._h, st, ptr(c), ptr(o), 256))
+    report("rescale_drop", "m=2^15 T=4->3 B=256", ms, 256, 256 * 2 ** 14 * 7 * 8)
+
+
+def tunnel_chain_leg(gen):
+    """tunnelH (lolhip_tunnel_chain_batch) over the reference's five hops (HomomPRFParams.hs RngList, primed rings), up
+    list ZQ5, in ZQ4, out ZQ3, base 2, B = 64, random hints (timing only), against the same steps through the Python
+    methods one call at a time.  alg_bytes: the input and output ciphertexts (the hops' traffic is not modelled)."""
+    st = torch.cuda.current_stream().cuda_stream
+    base, B, p = 2, 64, 8
+    rs = [128, 64 * 7, 32 * 7 * 13, 8 * 5 * 7 * 13, 4 * 3 * 5 * 7 * 13, 9 * 5 * 7 * 13]
+    rps = [128 * 7 * 13, 64 * 7 * 13] + rs[2:]
+    import math
+    Rp = [lol_amd.Plan.for_index(m, ZQ5) for m in rps]
+    exts_er, exts_es, ys, hints = [], [], [], []
+    for i in range(5):
+        E = lol_amd.Plan.for_index(math.gcd(rs[i], rs[i + 1]) * (rps[i] // rs[i]), ZQ5)
+        exts_er.append(lol_amd.Ext(E, Rp[i])); exts_es.append(lol_amd.Ext(E, Rp[i + 1]))
+        rel, S = Rp[i].n // E.n, Rp[i + 1]
+        ys.append(rnd(gen, ZQ5, rel, S.n))
+        hints.append(rnd(gen, ZQ5, rel, S.decomposeLen(base), 2, S.n))
+    p_in, p_mid, p_out = lol_amd.Plan.for_index(rps[0], ZQ5[1:]), lol_amd.Plan.for_index(rps[-1], ZQ5[1:]), lol_amd.Plan.for_index(rps[-1], ZQ5[2:])
+    chain = lol_amd.TunnelChain(exts_er, exts_es, ys, hints, base, p_in, p_out)
+    cs = rnd(gen, ZQ5[1:], 2, B, p_in.n)
+    L = lol_amd.lib()
+    import ctypes
+    work = torch.empty((chain.workLen(B),), dtype=torch.int64, device="cuda")
+    out = torch.empty((2, B, p_out.n, p_out.T), dtype=torch.int64, device="cuda")
+    lo_out = ctypes.c_int64(0)
+
+    def one_call():
+        rc = L.lolhip_tunnel_chain_batch(chain._h, st, cs.data_ptr(), 0, 0, 1, p, out.data_ptr(), 0, ctypes.byref(lo_out),
+                                         work.data_ptr(), B)
+        assert rc == 0, rc
+
+    res = []
+
+    def hop_by_hop():
+        cur, _, l = p_in.modSwitch(Rp[0], cs, p, "LSD", 1)
+        for xr, xs, R, S, y, h in zip(exts_er, exts_es, Rp[:-1], Rp[1:], ys, hints):
+            c0 = R.lInv(cur[0])
+            cur = S.crtInv(xr.tunnel(xs, c0, cur[1], y, h, base))
+        cur, _, l = Rp[-1].modSwitch(p_mid, cur, p, "MSD", l)
+        cur, _, l = p_mid.modSwitch(p_out, cur, p, "MSD", l)
+        res[:] = [cur]
+
+    one_call(); hop_by_hop()
+    torch.cuda.synchronize()
+    assert torch.equal(out, res[0]), "the two routes differ"
+    alg = 8 * 2 * B * (p_in.n * p_in.T + p_out.n * p_out.T)
+    cfg = f"RngList 5 hops {rps[0]}->{rps[-1]} ZQ4 -> ZQ5 -> ZQ3 base={base} B={B}"
+    report("tunnel_chain", cfg, timeit(one_call, iters=5), B, alg, note="one lolhip_tunnel_chain_batch call")
+    report("tunnel_chain_hop_by_hop", cfg, timeit(hop_by_hop, iters=5), B, alg,
+           note="Plan.modSwitch up, per hop lInv / Ext.tunnel / crtInv, two Plan.modSwitch down")
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--modswitch" in sys.argv:        # the ciphertext modSwitch leg alone
+        modswitch_leg(gen)
+        return
+    if "--tunnel-chain" in sys.argv:     # the multi-hop tunnelling leg alone
+        tunnel_chain_leg(gen)
+        return
     if "--public" in sys.argv:           # the public operations / ciphertext addition leg alone
         public_leg(gen)
         return
