@@ -14,11 +14,8 @@
 #include <string>
 #include <vector>
 
-#include "capi_internal.h"
 #include "kernels.h"
-#include "pipeline.h"
-#include "lolhip.h"
-#include "plan.h"
+#include "she_host.h"
 
 using namespace lolhip;
 
@@ -81,15 +78,6 @@ int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const in
   return LOLHIP_OK;
 }
 
-int need_device(const lolhip_plan* p) {
-  if (!p) return LOLHIP_ERR_INVALID;
-  if (!p->P.device) return LOLHIP_ERR_NO_DEVICE;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (dev != p->P.device_id) return LOLHIP_ERR_DEVICE;     // the plan's tables live on another GPU
-  return LOLHIP_OK;
-}
-
 // stream-ordered workspace: allocated and released on the caller's stream, so concurrent calls on
 // one plan (other host threads, other streams) never share it and nothing synchronises the device
 struct StreamBuf {
@@ -130,14 +118,42 @@ bool use_fused2(const Plan& P) {
   return !sw(SW_NO_FUSED2) && P.fused2 && use_mixed(P, P.prog_crt_fused) && use_mixed(P, P.prog_crtinv_fused);
 }
 
-// y = program(src or y) over B polynomials
-int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src = nullptr) {
+int run_pow2(const Plan& P, int mode, hipStream_t s, int64_t* y, const int64_t* a, const int64_t* b, int64_t B) {
+  Pow2Launch l;
+  l.stream = s; l.y = y; l.a = a; l.b = b; l.B = B; l.T = P.T; l.L = P.pow2.L;
+  l.mod = P.d_mod;
+  if (P.pow2.arith32) {             // every modulus < 2^27 (class 4), < 2^30 (2) or < 2^31 (3): 32-bit arithmetic
+    l.arith = P.pow2.arith32; l.tw_fwd = P.pow2.d_tw_fwd32; l.tw_inv = P.pow2.d_tw_inv32; l.scale = P.pow2.d_scale32;
+  } else {
+    l.arith = 1;
+    for (u64 q : P.qs) if (q >= (1ull << 61) || !(q & 1)) l.arith = 0;      // class 1's pointwise product is a Montgomery step: odd q
+    l.tw_fwd = P.pow2.d_tw_fwd; l.tw_inv = P.pow2.d_tw_inv; l.scale = P.pow2.d_scale;
+    l.trunc = (l.arith == 1 && mode == 2 && !sw(SW_NO_TRUNC)) ? 1 : 0;
+  }
+  return hip_status(launch_pow2(l, mode));
+}
+
+}  // namespace
+
+// ---- what the other host translation units call too (she_host.h) --------------------------------------------------
+namespace lolhip {
+
+int need_device(const lolhip_plan* p) {
+  if (!p) return LOLHIP_ERR_INVALID;
+  if (!p->P.device) return LOLHIP_ERR_NO_DEVICE;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LOLHIP_ERR_HIP;
+  if (dev != p->P.device_id) return LOLHIP_ERR_DEVICE;     // the plan's tables live on another GPU
+  return LOLHIP_OK;
+}
+
+int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
   if (use_mixed(P, sp)) {
     MixedLaunch m;
     m.stream = s; m.y = y; m.a = src ? src : y; m.b = nullptr; m.B = B; m.T = P.T; m.n = P.n;
     m.st_a = sp.d_stages; m.n_a = sp.nstages; m.st_b = nullptr; m.n_b = 0;
     m.consts = P.d_consts_mont ? P.d_consts_mont : P.d_consts; m.consts32 = P.d_consts32; m.cpc = P.consts_per_comp; m.mod = P.d_mod; m.cls = P.mixed_cls; m.fused = false; m.big = sp.big;
-    return launch_mixed(m) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    return hip_status(launch_mixed(m));
   }
   GenericLaunch a;
   a.stream = s; a.y = y; a.B = B; a.T = P.T; a.n = P.n;
@@ -156,22 +172,7 @@ int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, i
   if (src && src != y) {                // the scalar interpreter works in place
     if (hipMemcpyAsync(y, src, sizeof(int64_t) * (size_t)(B * P.n * P.T), hipMemcpyDeviceToDevice, s) != hipSuccess) return LOLHIP_ERR_HIP;
   }
-  return launch_generic(a) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
-}
-
-int run_pow2(const Plan& P, int mode, hipStream_t s, int64_t* y, const int64_t* a, const int64_t* b, int64_t B) {
-  Pow2Launch l;
-  l.stream = s; l.y = y; l.a = a; l.b = b; l.B = B; l.T = P.T; l.L = P.pow2.L;
-  l.mod = P.d_mod;
-  if (P.pow2.arith32) {             // every modulus < 2^27 (class 4), < 2^30 (2) or < 2^31 (3): 32-bit arithmetic
-    l.arith = P.pow2.arith32; l.tw_fwd = P.pow2.d_tw_fwd32; l.tw_inv = P.pow2.d_tw_inv32; l.scale = P.pow2.d_scale32;
-  } else {
-    l.arith = 1;
-    for (u64 q : P.qs) if (q >= (1ull << 61) || !(q & 1)) l.arith = 0;      // class 1's pointwise product is a Montgomery step: odd q
-    l.tw_fwd = P.pow2.d_tw_fwd; l.tw_inv = P.pow2.d_tw_inv; l.scale = P.pow2.d_scale;
-    l.trunc = (l.arith == 1 && mode == 2 && !sw(SW_NO_TRUNC)) ? 1 : 0;
-  }
-  return launch_pow2(l, mode) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_generic(a));
 }
 
 // crt / crtInv of B polynomials through whichever path the plan has: the m = 2^k kernels,
@@ -202,7 +203,35 @@ int divg_ok(const Plan& P) {
   return 1;
 }
 
-}  // namespace
+static int gadlen(u64 b, u64 q) {   // ZqBasic.hs:238-240: base-b digits of q
+  int k = 0;
+  while (q != 0) { ++k; q /= b; }
+  return k;
+}
+
+// digit counts and the invariant-divisor constants for `base` over the plan's moduli
+int make_decomp(const Plan& P, int64_t base, DecompParams& d) {
+  if (P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
+  if (base != 0 && base < 2) return LOLHIP_ERR_INVALID;
+  d.T = P.T;
+  d.base = base;
+  d.L = 0;
+  for (int t = 0; t < P.T; ++t) {
+    d.k[t] = base == 0 ? 1 : gadlen((u64)base, P.qs[t]);
+    d.L += d.k[t];
+  }
+  d.magic = 1; d.sh1 = 0; d.sh2 = 0;
+  if (base >= 2) {
+    int l = 0;
+    while (((u128)1 << l) < (u128)base) ++l;                       // ceil(log2 base)
+    d.magic = (u64)((((u128)1 << 64) * (((u128)1 << l) - (u128)base)) / (u128)base) + 1;
+    d.sh1 = l < 1 ? l : 1;
+    d.sh2 = l > 1 ? l - 1 : 0;
+  }
+  return LOLHIP_OK;
+}
+
+}  // namespace lolhip
 
 extern "C" {
 
@@ -316,7 +345,7 @@ int lolhip_polymul_batch(const lolhip_plan* p, void* stream, int64_t* c, const i
     m.st_a = pf.d_stages; m.n_a = pf.nstages;
     m.st_b = pi.d_stages; m.n_b = pi.nstages;
     m.consts = P.d_consts_mont ? P.d_consts_mont : P.d_consts; m.consts32 = P.d_consts32; m.cpc = P.consts_per_comp; m.mod = P.d_mod; m.cls = P.mixed_cls; m.fused = true; m.big = pf.big || pi.big;
-    return launch_mixed(m) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    return hip_status(launch_mixed(m));
   }
   // otherwise: crt(a) -> c, crt(b) -> temp, multiply, crtInv.  c may alias a or b.  The temp is a
   // stream-ordered allocation of this call (the pool recycles it: no device synchronisation).
@@ -369,8 +398,7 @@ int lolhip_mulgcrt_batch(const lolhip_plan* p, void* stream, int64_t* y, int64_t
   if (!p->P.has_crt) return LOLHIP_ERR_NO_CRT;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const i64 per = p->P.n * p->P.T;
-  return launch_pointwise_mul((hipStream_t)stream, y, p->P.d_gcrt, B * per, per, p->P.T, p->P.d_mod) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_pointwise_mul((hipStream_t)stream, y, p->P.d_gcrt, B * per, per, p->P.T, p->P.d_mod));
 }
 int lolhip_divgcrt_batch(const lolhip_plan* p, void* stream, int64_t* y, int64_t B) {
   int rc = need_device(p); if (rc) return rc;
@@ -378,8 +406,7 @@ int lolhip_divgcrt_batch(const lolhip_plan* p, void* stream, int64_t* y, int64_t
   if (!p->P.has_ginvcrt) return LOLHIP_ERR_NOT_DIVISIBLE;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const i64 per = p->P.n * p->P.T;
-  return launch_pointwise_mul((hipStream_t)stream, y, p->P.d_ginvcrt, B * per, per, p->P.T, p->P.d_mod) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_pointwise_mul((hipStream_t)stream, y, p->P.d_ginvcrt, B * per, per, p->P.T, p->P.d_mod));
 }
 
 // ---- floating-point members of the class ---------------------------------
@@ -392,57 +419,24 @@ int lolhip_crtc_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) 
   int rc = float_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
-  return launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crt.d_stages, P.prog_crt.nstages, P.d_cconsts) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crt.d_stages, P.prog_crt.nstages, P.d_cconsts));
 }
 int lolhip_crtinvc_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
   int rc = float_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
-  return launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crtinv.d_stages, P.prog_crtinv.nstages, P.d_cconsts) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crtinv.d_stages, P.prog_crtinv.nstages,
+                                P.d_cconsts));
 }
 int lolhip_gaussian_dec_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
   int rc = float_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
-  return launch_gauss((hipStream_t)stream, y, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_gauss((hipStream_t)stream, y, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages,
+                                 P.d_rconsts));
 }
 
 // ---- ring-level pipelines ---------------------------------------------
-
-namespace {
-
-int gadlen(u64 b, u64 q) {   // ZqBasic.hs:238-240: base-b digits of q
-  int k = 0;
-  while (q != 0) { ++k; q /= b; }
-  return k;
-}
-
-// digit counts and the invariant-divisor constants for `base` over the plan's moduli
-int make_decomp(const Plan& P, int64_t base, DecompParams& d) {
-  if (P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
-  if (base != 0 && base < 2) return LOLHIP_ERR_INVALID;
-  d.T = P.T;
-  d.base = base;
-  d.L = 0;
-  for (int t = 0; t < P.T; ++t) {
-    d.k[t] = base == 0 ? 1 : gadlen((u64)base, P.qs[t]);
-    d.L += d.k[t];
-  }
-  d.magic = 1; d.sh1 = 0; d.sh2 = 0;
-  if (base >= 2) {
-    int l = 0;
-    while (((u128)1 << l) < (u128)base) ++l;                       // ceil(log2 base)
-    d.magic = (u64)((((u128)1 << 64) * (((u128)1 << l) - (u128)base)) / (u128)base) + 1;
-    d.sh1 = l < 1 ? l : 1;
-    d.sh2 = l > 1 ? l - 1 : 0;
-  }
-  return LOLHIP_OK;
-}
-
-}  // namespace
 
 int lolhip_ctmul_crt_batch(const lolhip_plan* p, void* stream, const int64_t* c0, const int64_t* c1,
                            const int64_t* d0, const int64_t* d1, int64_t* e0, int64_t* e1, int64_t* e2, int64_t B) {
@@ -450,8 +444,8 @@ int lolhip_ctmul_crt_batch(const lolhip_plan* p, void* stream, const int64_t* c0
   if (!p->P.has_crt) return LOLHIP_ERR_NO_CRT;
   if (p->P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (B < 0 || (B > 0 && (!c0 || !c1 || !d0 || !d1 || !e0 || !e1 || !e2))) return LOLHIP_ERR_INVALID;
-  return launch_ctmul((hipStream_t)stream, c0, c1, d0, d1, e0, e1, e2, p->P.d_gcrt, B, p->P.n, p->P.T, p->P.d_mod)
-                 == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_ctmul((hipStream_t)stream, c0, c1, d0, d1, e0, e1, e2, p->P.d_gcrt, B, p->P.n, p->P.T,
+                                 p->P.d_mod));
 }
 
 int lolhip_decompose_len(const lolhip_plan* p, int64_t base) {
@@ -481,8 +475,7 @@ int lolhip_decompose_batch(const lolhip_plan* p, void* stream, const int64_t* c_
   DecompParams d;
   rc = make_decomp(p->P, base, d); if (rc) return rc;
   if (B < 0 || (B > 0 && (!c_pow || !digits))) return LOLHIP_ERR_INVALID;
-  return launch_decompose((hipStream_t)stream, c_pow, digits, B, p->P.n, d, p->P.d_mod, q_below(p->P, 31)) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_decompose((hipStream_t)stream, c_pow, digits, B, p->P.n, d, p->P.d_mod, q_below(p->P, 31)));
 }
 
 int lolhip_knapsack_batch(const lolhip_plan* p, void* stream, const int64_t* xs_crt, int L, const int64_t* hint,
@@ -490,8 +483,8 @@ int lolhip_knapsack_batch(const lolhip_plan* p, void* stream, const int64_t* xs_
   int rc = need_device(p); if (rc) return rc;
   if (L < 0 || K < 1 || K > 3 || B < 0 || p->P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (B > 0 && (!out || (L > 0 && (!xs_crt || !hint)))) return LOLHIP_ERR_INVALID;
-  return launch_knapsack((hipStream_t)stream, xs_crt, L, hint, K, addend, out, B, p->P.n, p->P.T, p->P.d_mod, q_below(p->P, 29))
-                 == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_knapsack((hipStream_t)stream, xs_crt, L, hint, K, addend, out, B, p->P.n, p->P.T,
+                                    p->P.d_mod, q_below(p->P, 29)));
 }
 
 }  // extern "C"
@@ -511,13 +504,8 @@ int keyswitch_impl(const Plan& P, hipStream_t stream, const int64_t* c2_pow, int
     KeySwitchLaunch l;
     l.stream = stream; l.c2 = c2_pow; l.hint = hint; l.addend = addend; l.out = out; l.B = B;
     l.T = P.T; l.L = P.pow2.L; l.tw_fwd32 = P.pow2.d_tw_fwd32; l.mod = P.d_mod; l.dp = d; l.arith = P.pow2.arith32;
-    l.magic32 = 1;
-    if (base >= 2) {
-      int lg = 0;
-      while (((u64)1 << lg) < (u64)base) ++lg;
-      l.magic32 = (uint32_t)((((u64)1 << 32) * (((u64)1 << lg) - (u64)base)) / (u64)base) + 1;
-    }
-    return launch_keyswitch_fused(l) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    l.magic32 = magic32(base);
+    return hip_status(launch_keyswitch_fused(l));
   }
   // ... and for every other index the vector interpreter takes, in its 32-bit Montgomery class (mixed_ks.hip)
   if (!P.is_pow2 && (P.mixed_cls == 2 || P.mixed_cls == 4) && P.d_consts32 && K == 2 && (base == 0 || base < ((int64_t)1 << 31)) &&
@@ -531,19 +519,14 @@ int keyswitch_impl(const Plan& P, hipStream_t stream, const int64_t* c2_pow, int
       MixedKeySwitchLaunch l;
       l.stream = stream; l.c2 = c2_pow; l.hint = hint; l.addend = addend; l.out = out; l.B = B; l.T = P.T; l.n = P.n;
       l.st_crt = pf.d_stages; l.n_crt = pf.nstages; l.big = pf.big; l.consts32 = P.d_consts32; l.cpc = P.consts_per_comp; l.mod = P.d_mod; l.dp = d;
-      l.magic32 = 1;
-      if (base >= 2) {
-        int lg = 0;
-        while (((u64)1 << lg) < (u64)base) ++lg;
-        l.magic32 = (uint32_t)((((u64)1 << 32) * (((u64)1 << lg) - (u64)base)) / (u64)base) + 1;
-      }
-      return launch_mixed_keyswitch(l) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+      l.magic32 = magic32(base);
+      return hip_status(launch_mixed_keyswitch(l));
     }
   }
   if (launch_decompose(stream, c2_pow, work, B, P.n, d, P.d_mod, q_below(P, 31)) != hipSuccess) return LOLHIP_ERR_HIP;
   rc = do_crt(P, stream, work, (int64_t)d.L * B, false);                 // all L*B digit polynomials in one launch
   if (rc) return rc;
-  return launch_knapsack(stream, work, d.L, hint, K, addend, out, B, P.n, P.T, P.d_mod, q_below(P, 29)) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_knapsack(stream, work, d.L, hint, K, addend, out, B, P.n, P.T, P.d_mod, q_below(P, 29)));
 }
 }  // namespace
 
@@ -567,7 +550,7 @@ int lolhip_rescale_drop_batch(const lolhip_plan* p, void* stream, const int64_t*
     r.qa_inv[s] = invmod(P.qs[0] % P.qs[s], P.qs[s]);
     if (r.qa_inv[s] == 0) return LOLHIP_ERR_MODULUS;
   }
-  return launch_rescale((hipStream_t)stream, c, out, B, P.n, r, P.d_mod) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_rescale((hipStream_t)stream, c, out, B, P.n, r, P.d_mod));
 }
 
 // ---- ring extensions -----------------------------------------------------------------
@@ -641,8 +624,8 @@ static int ext_gather(const lolhip_ext* x, void* stream, int64_t* out, const int
   if (B < 0 || (B > 0 && (!out || !in))) return LOLHIP_ERR_INVALID;
   const ExtPlan& X = x->X;
   const i64 n_out = to_hi ? X.host.phi2 : X.host.phi, n_in = to_hi ? X.host.phi : X.host.phi2;
-  return launch_gather((hipStream_t)stream, out, in, idx, B, n_out, n_in, X.lo->T, X.lo->d_mod, replicating) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_gather((hipStream_t)stream, out, in, idx, B, n_out, n_in, X.lo->T, X.lo->d_mod,
+                                  replicating));
 }
 int lolhip_twace_powdec_batch(const lolhip_ext* x, void* s, int64_t* lo_out, const int64_t* hi_in, int64_t B) {
   return ext_gather(x, s, lo_out, hi_in, B, x ? x->X.d_twace_powdec : nullptr, false);
@@ -652,8 +635,8 @@ int lolhip_coeffs_batch(const lolhip_ext* x, void* s, int64_t* lo_out, const int
   if (!x->X.d_coeffs) return LOLHIP_ERR_NO_DEVICE;
   if (B < 0 || (B > 0 && (!lo_out || !hi_in))) return LOLHIP_ERR_INVALID;
   const ExtPlan& X = x->X;
-  return launch_coeffs((hipStream_t)s, lo_out, hi_in, X.d_coeffs, B, X.host.phi, X.host.phi2, X.lo->T, X.lo->d_mod)
-                 == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_coeffs((hipStream_t)s, lo_out, hi_in, X.d_coeffs, B, X.host.phi, X.host.phi2, X.lo->T,
+                                  X.lo->d_mod));
 }
 int lolhip_evallin_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* s, const int64_t* r_dec,
                          const int64_t* ys_crt, int64_t* out, int64_t* work, int64_t B) {
@@ -676,8 +659,8 @@ int lolhip_evallin_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* s
   if (!rc) rc = run_prog(*PS, PS->prog_l, (hipStream_t)s, tmp_s, rel * B);                 // Dec -> Pow
   if (!rc) rc = do_crt(*PS, (hipStream_t)s, tmp_s, rel * B, false);
   if (rc) return rc;
-  return launch_knapsack((hipStream_t)s, tmp_s, (int)rel, ys_crt, 1, nullptr, out, B, PS->n, PS->T, PS->d_mod, q_below(*PS, 29))
-                 == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_knapsack((hipStream_t)s, tmp_s, (int)rel, ys_crt, 1, nullptr, out, B, PS->n, PS->T,
+                                    PS->d_mod, q_below(*PS, 29)));
 }
 int64_t lolhip_tunnel_work_len(const lolhip_ext* x_er, const lolhip_ext* x_es, int64_t base, int64_t B) {
   if (!x_er || !x_es || B < 0) return LOLHIP_ERR_INVALID;
@@ -747,8 +730,8 @@ int lolhip_twace_crt_batch(const lolhip_ext* x, void* s, int64_t* lo_out, const 
   if (X.tweak.empty()) return LOLHIP_ERR_NO_CRT;
   if (!X.d_tweak) return LOLHIP_ERR_NO_DEVICE;
   if (B < 0 || (B > 0 && (!lo_out || !hi_in))) return LOLHIP_ERR_INVALID;
-  return launch_twace_crt((hipStream_t)s, lo_out, hi_in, X.d_ext_crt, X.d_tweak, B, X.host.phi, X.host.phi2,
-                          X.lo->T, X.lo->d_mod) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_twace_crt((hipStream_t)s, lo_out, hi_in, X.d_ext_crt, X.d_tweak, B, X.host.phi,
+                                     X.host.phi2, X.lo->T, X.lo->d_mod));
 }
 
 // ---- host-pointer convenience ----------------------------------------------------------
@@ -1024,14 +1007,3 @@ int16_t tensorGInvDecRq(int16_t T, int64_t* y, int64_t totm, lolhip_pp* pe, int1
 }
 
 }  // extern "C"
-
-// ---- for the other host translation units of the C ABI (capi_internal.h) -----------------
-namespace lolhip {
-int capi_need_device(const lolhip_plan* p) { return need_device(p); }
-int capi_run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
-  return run_prog(P, sp, s, y, B, src);
-}
-int capi_do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse) { return do_crt(P, s, y, B, inverse); }
-int capi_divg_ok(const Plan& P) { return divg_ok(P); }
-int capi_make_decomp(const Plan& P, int64_t base, DecompParams& d) { return make_decomp(P, base, d); }
-}  // namespace lolhip

@@ -16,8 +16,8 @@
 // lift_consts); the p-dependent ones travel by value in LiftParams.
 #include <hip/hip_runtime.h>
 
+#include "elementwise_dev.h"
 #include "pipeline.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
@@ -26,12 +26,6 @@ typedef unsigned __int128 u128;
 namespace {
 constexpr int EPT = 2;                       // elements per thread (k_sk_eval, k_addmod)
 constexpr i64 TILE = 256 * EPT;
-bool tiles_for(i64 total, i64 tile, unsigned* blocks) {
-  const i64 b = (total + tile - 1) / tile;
-  if (b > 0x7fffffff) return false;
-  *blocks = (unsigned)(b < 1 ? 1 : b);
-  return true;
-}
 }  // namespace
 
 // ---------------------------------------------------------------------------------------

@@ -3,30 +3,19 @@
 // decrypt.hip and the existing transforms.
 #include <hip/hip_runtime_api.h>
 
-#include "capi_internal.h"
-#include "hostmath.h"
-#include "pipeline.h"
+#include "she_host.h"
 
 using namespace lolhip;
 
 // ---- errorTerm / decrypt (lol-apps SymmSHE.hs:153-178) ---------------------------------------
 namespace {
 
-// y = program(src or y), or a copy when the program is empty (L and L^-1 of m = 2^k: the powerful and decoding
-// bases coincide)
-int run_prog_or_copy(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
-  if (!sp.stages.empty()) return capi_run_prog(P, sp, s, y, B, src);
-  if (!src || src == y || B == 0) return LOLHIP_OK;
-  return hipMemcpyAsync(y, src, sizeof(int64_t) * (size_t)(B * P.n * P.T), hipMemcpyDeviceToDevice, s) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
-}
-
 // host checks shared by both entries and the lift's p-dependent constants.  enc: 0 LSD, 1 MSD; p: the plaintext
 // modulus; l: the ciphertext's scalar (decrypt only; l' = l, or l (-Q)^-1 mod p for MSD: msdToLSD, Prelude.hs:311-315)
 int decrypt_setup(const Plan& P, int ncs, int enc, int64_t p, int64_t l, LiftParams& lp) {
   if (ncs < 1 || (enc != 0 && enc != 1) || P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (!P.has_crt) return LOLHIP_ERR_NO_CRT;
-  if (p < 2 || p >= ((int64_t)1 << 62) || !P.lift_ok) return LOLHIP_ERR_MODULUS;
+  if (!p_ok(p) || !P.lift_ok) return LOLHIP_ERR_MODULUS;
   const u64 up = (u64)p;
   lp = LiftParams();
   lp.T = P.T;
@@ -34,18 +23,15 @@ int decrypt_setup(const Plan& P, int ncs, int enc, int64_t p, int64_t l, LiftPar
   lp.mp = make_modctx(up);
   u64 prefix = 1 % up;
   for (int t = 0; t < P.T; ++t) {
-    lp.scale[t] = up % P.qs[(size_t)t];
     lp.pw[t] = prefix;
     prefix = mulmod(prefix, P.qs[(size_t)t] % up, up);
   }
   lp.qp = prefix;
-  const u64 lmod = (u64)(((l % p) + p) % p);
-  lp.lp = lmod;
-  if (enc == 1) {
-    const u64 inv = invmod((up - lp.qp) % up, up);           // (-Q)^-1 mod p
-    if (inv == 0 && up > 1) return LOLHIP_ERR_MODULUS;
-    lp.lp = mulmod(lmod, inv, up);
+  u64 zp = 1;
+  if (enc == 1) {                                              // msdToLSD: p mod q_t on the residues, (-Q)^-1 mod p on l
+    const int rc = encode_scales(P, p, false, lp.scale, &zp); if (rc) return rc;
   }
+  lp.lp = encode_l(l, zp, up);
   return LOLHIP_OK;
 }
 
@@ -65,23 +51,23 @@ int eval_dec(const Plan& P, hipStream_t s, const int64_t* cs, int ncs, bool cs_c
   int rc = LOLHIP_OK;
   if (cs_crt) {
     if (launch_sk_eval(s, cs, ncs, false, s_crt, work, B, P.n, P.T, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
-    rc = capi_do_crt(P, s, work, B, true);
+    rc = do_crt(P, s, work, B, true);
     return rc ? rc : run_prog_or_copy(P, P.prog_linv, s, work, B, nullptr);
   }
   if (ncs == 1) {
     if (l_id) { *v = cs; return LOLHIP_OK; }
-    return capi_run_prog(P, P.prog_linv, s, work, B, cs);
+    return run_prog(P, P.prog_linv, s, work, B, cs);
   }
   if (hipMemcpyAsync(work, cs + slab, sizeof(int64_t) * slab * (size_t)(ncs - 1), hipMemcpyDeviceToDevice, s) != hipSuccess)
     return LOLHIP_ERR_HIP;
-  rc = capi_do_crt(P, s, work, B * (ncs - 1), false);
+  rc = do_crt(P, s, work, B * (ncs - 1), false);
   if (rc) return rc;
   if (launch_sk_eval(s, work, ncs - 1, true, s_crt, work, B, P.n, P.T, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
-  rc = capi_do_crt(P, s, work, B, true);
+  rc = do_crt(P, s, work, B, true);
   if (rc) return rc;
   if (l_id) { *add = cs; return LOLHIP_OK; }
   if (launch_addmod(s, work, cs, B, P.n, P.T, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
-  return capi_run_prog(P, P.prog_linv, s, work, B, nullptr);
+  return run_prog(P, P.prog_linv, s, work, B, nullptr);
 }
 
 int64_t qside_len(const Plan& P, int ncs, int64_t B) { return (int64_t)(ncs > 2 ? ncs - 1 : 1) * B * P.n * P.T; }
@@ -97,7 +83,7 @@ int64_t lolhip_decrypt_work_len(const lolhip_plan* pq, int ncs, int64_t B) {
 
 int lolhip_error_term_batch(const lolhip_plan* pq, void* stream, const int64_t* cs, int ncs, int cs_crt,
                             const int64_t* s_crt, int enc, int64_t p, int64_t* e_dec, int64_t* work, int64_t B) {
-  int rc = capi_need_device(pq); if (rc) return rc;
+  int rc = need_device(pq); if (rc) return rc;
   const Plan& P = pq->P;
   LiftParams lp;
   rc = decrypt_setup(P, ncs, enc, p, 1, lp); if (rc) return rc;
@@ -106,7 +92,7 @@ int lolhip_error_term_batch(const lolhip_plan* pq, void* stream, const int64_t* 
   hipStream_t s = (hipStream_t)stream;
   const int64_t *v, *add;
   rc = eval_dec(P, s, cs, ncs, cs_crt != 0, s_crt, work, B, &v, &add); if (rc) return rc;
-  return launch_lift(s, v, add, e_dec, B * P.n, lp, false, P.d_lift, P.d_mod) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_lift(s, v, add, e_dec, B * P.n, lp, false, P.d_lift, P.d_mod));
 }
 
 // decrypt = l' * twace (divG^k (reduce_p e)): the lift writes l' * reduce_p e (decoding basis of R'_p, l' folded in:
@@ -114,9 +100,9 @@ int lolhip_error_term_batch(const lolhip_plan* pq, void* stream, const int64_t* 
 int lolhip_decrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lolhip_ext* x_p, void* stream,
                          const int64_t* cs, int ncs, int cs_crt, const int64_t* s_crt, int enc, int64_t k, int64_t l,
                          int64_t* pt_pow, int64_t* work, int64_t B) {
-  int rc = capi_need_device(pq); if (rc) return rc;
+  int rc = need_device(pq); if (rc) return rc;
   if (!pp) return LOLHIP_ERR_INVALID;
-  rc = capi_need_device(pp); if (rc) return rc;
+  rc = need_device(pp); if (rc) return rc;
   const Plan &P = pq->P, &PP = pp->P;
   if (PP.T != 1 || PP.m != P.m || k < 0) return LOLHIP_ERR_INVALID;
   const Plan* PM = &PP;                                       // the plan of the output ring R_m over p
@@ -128,7 +114,7 @@ int lolhip_decrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
   }
   LiftParams lp;
   rc = decrypt_setup(P, ncs, enc, (int64_t)PP.qs[0], l, lp); if (rc) return rc;
-  if (k > 0 && !capi_divg_ok(PP)) return LOLHIP_ERR_NOT_DIVISIBLE;
+  if (k > 0 && !divg_ok(PP)) return LOLHIP_ERR_NOT_DIVISIBLE;
   if (B < 0 || (B > 0 && (!cs || !s_crt || !pt_pow || !work))) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -137,7 +123,7 @@ int lolhip_decrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
   int64_t* e = work + qside_len(P, ncs, B);                   // [B][n'] residues mod p
   if (launch_lift(s, v, add, e, B * P.n, lp, true, P.d_lift, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
   for (int64_t i = 0; i < k; ++i) {
-    rc = capi_run_prog(PP, PP.prog_ginvdec, s, e, B, nullptr); if (rc) return rc;
+    rc = run_prog(PP, PP.prog_ginvdec, s, e, B, nullptr); if (rc) return rc;
   }
   if (x_p) {
     rc = lolhip_twace_powdec_batch(x_p, stream, pt_pow, e, B); if (rc) return rc;

@@ -14,9 +14,9 @@
 // run over the grid's y dimension; the key and the stream offset travel by value.
 #include <hip/hip_runtime.h>
 
+#include "elementwise_dev.h"
 #include "pipeline.h"
 #include "rng_dev.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
@@ -25,9 +25,9 @@ constexpr int TPB = 256;
 constexpr unsigned MAX_GRID_Y = 65535;
 
 bool grid_for(i64 nblk, i64 B, dim3* grid) {
-  const i64 x = (nblk + TPB - 1) / TPB;
-  if (x > 0x7fffffff) return false;
-  *grid = dim3((unsigned)(x < 1 ? 1 : x), (unsigned)(B < (i64)MAX_GRID_Y ? B : MAX_GRID_Y));
+  unsigned x;
+  if (!tiles_for(nblk, TPB, &x)) return false;
+  *grid = dim3(x, (unsigned)(B < (i64)MAX_GRID_Y ? B : MAX_GRID_Y));
   return true;
 }
 
@@ -56,13 +56,6 @@ __device__ __forceinline__ void gauss8(const ChaChaKey& key, u64 ctr, int domain
   stream_block(key, ctr, domain, b, k, w);
 #pragma unroll
   for (int i = 0; i < 4; ++i) box_muller(w + 4 * i, sigma, &g[2 * i], &g[2 * i + 1]);
-}
-
-// x mod q for any int64 x
-__device__ __forceinline__ u64 smod(i64 x, const ModCtx& mc) {
-  const u64 ax = x < 0 ? (u64)0 - (u64)x : (u64)x;
-  const u64 r = rem128(0, ax, mc);
-  return x < 0 && r ? mc.q - r : r;
 }
 }  // namespace
 
@@ -149,7 +142,7 @@ k_enc_error(const double* d, const i64* __restrict__ rep, i64 p, i64* out, i64 B
       for (u32 w = threadIdx.x; w < words; w += TPB) {
         const u32 c = w / (u32)T, t = w - c * (u32)T;
         const ModCtx mc = mod[t];
-        const u64 v = smod(se[c], mc);
+        const u64 v = mod_any(se[c], mc);
         ob[w] = (i64)(MODE == ENC_ADD ? addmod(canon_in(ob[w], mc.q), v, mc.q) : v);
       }
     }

@@ -27,9 +27,9 @@ int64_t lolhip_encrypt_work_len(const lolhip_plan* pq, int64_t B) {
 int lolhip_encrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lolhip_ext* x_p, void* stream,
                          const int64_t* pt_pow, const int64_t* s_crt, double svar, const uint8_t key[32], uint64_t ctr,
                          int out_crt, int64_t* cs_out, int64_t* work, int64_t B) {
-  int rc = capi_need_device(pq); if (rc) return rc;
+  int rc = need_device(pq); if (rc) return rc;
   if (!pp) return LOLHIP_ERR_INVALID;
-  rc = capi_need_device(pp); if (rc) return rc;
+  rc = need_device(pp); if (rc) return rc;
   const Plan &P = pq->P, &PP = pp->P;
   if (!svar_ok(svar) || B < 0 || PP.T != 1 || PP.m != P.m || P.T > PIPE_MAX_T) return LOLHIP_ERR_INVALID;
   if (x_p) {
@@ -58,25 +58,25 @@ int lolhip_encrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
   const int64_t* rep_src = rep;
   if (x_p) {
     rc = lolhip_embed_pow_batch(x_p, stream, rep, pt_pow, B); if (rc) return rc;
-    if (!PP.prog_linv.stages.empty()) { rc = capi_run_prog(PP, PP.prog_linv, s, rep, B, nullptr); if (rc) return rc; }
+    rc = run_prog_or_copy(PP, PP.prog_linv, s, rep, B); if (rc) return rc;
   } else if (!PP.prog_linv.stages.empty()) {
-    rc = capi_run_prog(PP, PP.prog_linv, s, rep, B, pt_pow); if (rc) return rc;
+    rc = run_prog(PP, PP.prog_linv, s, rep, B, pt_pow); if (rc) return rc;
   } else {
     rep_src = pt_pow;
   }
 
   if (out_crt) {
     rc = sample_error(P, s, d, rep_src, p, c0, ENC_WRITE, k, ctr, CHACHA_DOM_ENC_GAUSS, sigma, B); if (rc) return rc;
-    if (!P.prog_l.stages.empty()) { rc = capi_run_prog(P, P.prog_l, s, c0, B, nullptr); if (rc) return rc; }
-    rc = capi_do_crt(P, s, c0, B, false); if (rc) return rc;
-    return launch_enc_c1(s, true, c0, c1, s_crt, B, n, P.T, P.d_mod, k, ctr) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    rc = run_prog_or_copy(P, P.prog_l, s, c0, B); if (rc) return rc;
+    rc = do_crt(P, s, c0, B, false); if (rc) return rc;
+    return hip_status(launch_enc_c1(s, true, c0, c1, s_crt, B, n, P.T, P.d_mod, k, ctr));
   }
   if (launch_enc_c1(s, false, c0, c1, s_crt, B, n, P.T, P.d_mod, k, ctr) != hipSuccess) return LOLHIP_ERR_HIP;
-  rc = capi_do_crt(P, s, cs_out, 2 * B, true); if (rc) return rc;
+  rc = do_crt(P, s, cs_out, 2 * B, true); if (rc) return rc;
   if (pow2) return sample_error(P, s, d, rep_src, p, c0, ENC_ADD, k, ctr, CHACHA_DOM_ENC_GAUSS, sigma, B);
   rc = sample_error(P, s, d, rep_src, p, e, ENC_WRITE, k, ctr, CHACHA_DOM_ENC_GAUSS, sigma, B); if (rc) return rc;
-  rc = capi_run_prog(P, P.prog_l, s, e, B, nullptr); if (rc) return rc;
-  return launch_addmod(s, c0, e, B, n, P.T, P.d_mod) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  rc = run_prog(P, P.prog_l, s, e, B, nullptr); if (rc) return rc;
+  return hip_status(launch_addmod(s, c0, e, B, n, P.T, P.d_mod));
 }
 
 // errorRounded svar = round (tGaussianDec svar), coefficient-wise (UCyc.hs:422-429): the sampler with p = 1, rep = 0,
@@ -84,7 +84,7 @@ int lolhip_encrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
 int lolhip_error_rounded_batch(const lolhip_plan* p, void* stream, double svar, const uint8_t key[32], uint64_t ctr,
                                int64_t* z_dec, int64_t* work, int64_t B) {
   (void)work;
-  int rc = capi_need_device(p); if (rc) return rc;
+  int rc = need_device(p); if (rc) return rc;
   const Plan& P = p->P;
   if (!svar_ok(svar) || B < 0) return LOLHIP_ERR_INVALID;
   rc = sampler_ok(P); if (rc) return rc;

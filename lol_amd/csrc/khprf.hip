@@ -19,8 +19,8 @@
 
 #include <type_traits>
 
+#include "elementwise_dev.h"
 #include "pipeline.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
@@ -85,8 +85,7 @@ k_khprf_node(const i64* __restrict__ Lv, const i64* __restrict__ D, i64* __restr
       for (int jj = 0; jj < JG; ++jj) acc[t][jj] = 0;
     auto red = [&](Acc a) -> u64 {
       if constexpr (Q32) {
-        const u64 r = a - __umul64hi(a, mc.mu) * mc.q;          // [0, 2q)
-        return r >= mc.q ? r - mc.q : r;
+        return trim(a - __umul64hi(a, mc.mu) * mc.q, mc.q);
       } else {
         return reduce128((u64)(a >> 64), (u64)a, mc);
       }

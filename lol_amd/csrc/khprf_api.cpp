@@ -11,8 +11,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "capi_internal.h"
-#include "pipeline.h"
+#include "she_host.h"
 
 using namespace lolhip;
 
@@ -128,8 +127,8 @@ bool q_below31(const Plan& P) { return P.qs[0] < ((u64)1 << 31); }
 
 // LOLHIP_OK, or why the family cannot compute on the calling thread's current device (both plans of a lifted one)
 int need_device(const lolhip_khprf* f) {
-  const int rc = capi_need_device(f->pq);
-  return rc || !f->pQ ? rc : capi_need_device(f->pQ);
+  const int rc = lolhip::need_device(f->pq);
+  return rc || !f->pQ ? rc : lolhip::need_device(f->pQ);
 }
 
 // Q32 digits per 64-bit sum of k_khprf_node for products mod q: (q-1) + fold (q-1)^2 < 2^64
@@ -144,9 +143,9 @@ int fold_for(u64 q, int ell) {
 // the lifted family: `rows` node values mod Q, CRT basis -> crtInv -> reduce mod q -> lift_q mod Q -> crt, in place
 int requantize(const lolhip_khprf& f, hipStream_t s, int64_t* y, int64_t rows) {
   const Plan& PQ = f.pQ->P;
-  int rc = capi_do_crt(PQ, s, y, rows, true); if (rc) return rc;
+  int rc = do_crt(PQ, s, y, rows, true); if (rc) return rc;
   if (launch_khprf_lift(s, y, y, rows * PQ.n, LIFT_FROM_Q | LIFT_TO_Q, f.lc) != hipSuccess) return LOLHIP_ERR_HIP;
-  return capi_do_crt(PQ, s, y, rows, false);
+  return do_crt(PQ, s, y, rows, false);
 }
 
 int eval_node(const lolhip_khprf& f, hipStream_t s, int i, int64_t x0, int64_t B, const Layout& lay, int64_t* work,
@@ -168,12 +167,12 @@ int eval_node(const lolhip_khprf& f, hipStream_t s, int i, int64_t x0, int64_t B
     int64_t* rd = work + lay.dig[v.r];
     int rc = eval_node(f, s, v.r, x0, B, lay, work, rv); if (rc) return rc;
     // G^-1: crtInv of the U_r L entries, their digits [L][U_r L][n], crt of the L U_r L digit polynomials
-    rc = capi_do_crt(PC, s, rv, vr.U * f.ell, true); if (rc) return rc;
+    rc = do_crt(PC, s, rv, vr.U * f.ell, true); if (rc) return rc;
     if (f.pQ && launch_khprf_lift(s, rv, rv, vr.U * ln, LIFT_FROM_Q, f.lc) != hipSuccess) return LOLHIP_ERR_HIP;
     if (launch_decompose(s, rv, rd, vr.U * f.ell, P.n, f.dp, P.d_mod, q_below31(P)) != hipSuccess) return LOLHIP_ERR_HIP;
     const int64_t drows = (int64_t)f.ell * vr.U * f.ell;
     if (f.pQ && launch_khprf_lift(s, rd, rd, drows * P.n, LIFT_TO_Q, f.lc) != hipSuccess) return LOLHIP_ERR_HIP;
-    rc = capi_do_crt(PC, s, rd, drows, false); if (rc) return rc;
+    rc = do_crt(PC, s, rd, drows, false); if (rc) return rc;
     D = rd;
   }
   KhprfNode nd{};
@@ -187,7 +186,7 @@ int eval_node(const lolhip_khprf& f, hipStream_t s, int i, int64_t x0, int64_t B
   nd.l = KhprfChild{vl.lo, ((int64_t)1 << l.c) - 1, vl.full ? 1 : 0, r.c};
   nd.r = KhprfChild{vr.lo, ((int64_t)1 << r.c) - 1, vr.full ? 1 : 0, 0};
   const int64_t* Lv = is_leaf(l) ? f.d_leaf : work + lay.val[v.l];
-  return launch_khprf_node(s, Lv, D, dst, nd, f.mc, f.fold) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_khprf_node(s, Lv, D, dst, nd, f.mc, f.fold));
 }
 
 // A_T(x) for the window into dst [B][L][n] (B >= 1): CRT basis, or powerful basis mod q for the lifted family
@@ -195,14 +194,13 @@ int eval_root(const lolhip_khprf& f, hipStream_t s, int64_t x0, int64_t B, int64
   const int64_t ln = (int64_t)f.ell * f.pq->P.n;
   if (is_leaf(f.nodes[0])) {
     const int64_t* src = (f.pQ ? f.d_leafpow : f.d_leaf) + x0 * ln;
-    return hipMemcpyAsync(dst, src, sizeof(int64_t) * (size_t)(B * ln), hipMemcpyDeviceToDevice, s)
-                   == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    return hip_status(hipMemcpyAsync(dst, src, sizeof(int64_t) * (size_t)(B * ln), hipMemcpyDeviceToDevice, s));
   }
   const Layout lay = layout(f, x0, B);
   int rc = eval_node(f, s, 0, x0, B, lay, work, dst);
   if (rc || !f.pQ) return rc;
-  rc = capi_do_crt(f.pQ->P, s, dst, B * f.ell, true); if (rc) return rc;
-  return launch_khprf_lift(s, dst, dst, B * ln, LIFT_FROM_Q, f.lc) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  rc = do_crt(f.pQ->P, s, dst, B * f.ell, true); if (rc) return rc;
+  return hip_status(launch_khprf_lift(s, dst, dst, B * ln, LIFT_FROM_Q, f.lc));
 }
 
 void free_dev(lolhip_khprf* f) {
@@ -226,10 +224,10 @@ int upload(lolhip_khprf* f, const std::vector<int64_t>& a) {
   if (hipMemcpyAsync(f->d_leaf, a.data(), words * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(tmp, f->d_leaf, words * sizeof(int64_t), hipMemcpyDeviceToDevice, s) != hipSuccess)
     rc = LOLHIP_ERR_HIP;
-  if (!rc) rc = capi_do_crt(P, s, tmp, 2 * f->ell, true);
+  if (!rc) rc = do_crt(P, s, tmp, 2 * f->ell, true);
   if (!rc && launch_decompose(s, tmp, f->d_leafdig, 2 * f->ell, P.n, f->dp, P.d_mod, q_below31(P)) != hipSuccess)
     rc = LOLHIP_ERR_HIP;
-  if (!rc) rc = capi_do_crt(P, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
+  if (!rc) rc = do_crt(P, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
   if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;
   (void)hipStreamDestroy(s);
   (void)hipFree(tmp);
@@ -254,8 +252,8 @@ int upload_lifted(lolhip_khprf* f, const std::vector<int64_t>& a) {
       launch_decompose(s, f->d_leafpow, f->d_leafdig, 2 * f->ell, P.n, f->dp, P.d_mod, q_below31(P)) != hipSuccess ||
       launch_khprf_lift(s, f->d_leafdig, f->d_leafdig, dwords, LIFT_TO_Q, f->lc) != hipSuccess)
     rc = LOLHIP_ERR_HIP;
-  if (!rc) rc = capi_do_crt(PQ, s, f->d_leaf, 2 * f->ell, false);
-  if (!rc) rc = capi_do_crt(PQ, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
+  if (!rc) rc = do_crt(PQ, s, f->d_leaf, 2 * f->ell, false);
+  if (!rc) rc = do_crt(PQ, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
   if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;
   (void)hipStreamDestroy(s);
   return rc;
@@ -310,7 +308,7 @@ int lolhip_khprf_create(const lolhip_plan* pq, int64_t base, const int32_t* tree
   lolhip_khprf* f = new lolhip_khprf;
   f->pq = pq;
   f->base = base;
-  int rc = capi_make_decomp(P, base, f->dp);
+  int rc = make_decomp(P, base, f->dp);
   if (!rc && (parse(tree, ntree, 0, 0, f->nodes, 0) != ntree || f->nodes[0].c > 62)) rc = LOLHIP_ERR_INVALID;
   if (!rc && !P.has_crt) rc = LOLHIP_ERR_NO_CRT;
   if (rc) { delete f; return rc; }
@@ -319,15 +317,14 @@ int lolhip_khprf_create(const lolhip_plan* pq, int64_t base, const int32_t* tree
   const u64 q = P.qs[0];
   f->mc = make_modctx(q);
   f->fold = fold_for(q, f->ell);
-  rc = capi_need_device(pq);
+  rc = need_device(pq);
   if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f; return LOLHIP_OK; }      // host-only: validation and work lengths
   if (rc) { delete f; return rc; }
   const int64_t ln = (int64_t)f->ell * P.n;
   std::vector<int64_t> a((size_t)(2 * ln));
   for (int64_t i = 0; i < ln; ++i) {
-    const int64_t x0 = a0_crt[i] % (int64_t)q, x1 = a1_crt[i] % (int64_t)q;
-    a[i] = x0 < 0 ? x0 + (int64_t)q : x0;
-    a[ln + i] = x1 < 0 ? x1 + (int64_t)q : x1;
+    a[i] = (int64_t)canon(a0_crt[i], q);
+    a[ln + i] = (int64_t)canon(a1_crt[i], q);
   }
   rc = upload(f, a);
   if (rc) { free_dev(f); delete f; return rc; }
@@ -340,14 +337,12 @@ int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int
   if (!pq || !pQ || !tree || !a0_pow || !a1_pow || !out || ntree < 1 || ntree > 123) return LOLHIP_ERR_INVALID;
   const Plan& P = pq->P;
   const Plan& PQ = pQ->P;
-  if (P.T != 1 || PQ.T != 1 || P.m != PQ.m || P.pps.size() != PQ.pps.size()) return LOLHIP_ERR_INVALID;
-  for (size_t i = 0; i < P.pps.size(); ++i)                 // the same index with the same tensor order
-    if (P.pps[i].p != PQ.pps[i].p || P.pps[i].e != PQ.pps[i].e) return LOLHIP_ERR_INVALID;
+  if (P.T != 1 || PQ.T != 1 || !same_index(P, PQ)) return LOLHIP_ERR_INVALID;
   lolhip_khprf* f = new lolhip_khprf;
   f->pq = pq;
   f->pQ = pQ;
   f->base = base;
-  int rc = capi_make_decomp(P, base, f->dp);
+  int rc = make_decomp(P, base, f->dp);
   if (!rc && (parse(tree, ntree, 0, 0, f->nodes, 0) != ntree || f->nodes[0].c > 62)) rc = LOLHIP_ERR_INVALID;
   const u64 q = P.qs[0], Q = PQ.qs[0];
   if (!rc && (q < 2 || (q & (q - 1)) != 0)) rc = LOLHIP_ERR_MODULUS;
@@ -424,19 +419,18 @@ int lolhip_khprf_batch(const lolhip_khprf* f, void* stream, const int64_t* s_crt
   const bool linv = !P.prog_linv.stages.empty();
   if (f->pQ) {
     // exact s A mod Q -> Z_q (fused with the 2-power rounding when there is no lInv between them)
-    rc = capi_do_crt(f->pQ->P, s, out, rows, true); if (rc) return rc;
+    rc = do_crt(f->pQ->P, s, out, rows, true); if (rc) return rc;
     KhprfLift lc = f->lc;
     lc.p = (u64)p;
     if (linv) {
       if (launch_khprf_lift(s, out, out, rows * P.n, LIFT_FROM_Q, lc) != hipSuccess) return LOLHIP_ERR_HIP;
-      rc = capi_run_prog(P, P.prog_linv, s, out, rows, nullptr); if (rc) return rc;
+      rc = run_prog(P, P.prog_linv, s, out, rows, nullptr); if (rc) return rc;
     }
-    return launch_khprf_lift(s, out, out, rows * P.n, (linv ? 0 : LIFT_FROM_Q) | LIFT_ROUND, lc) == hipSuccess
-               ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    return hip_status(launch_khprf_lift(s, out, out, rows * P.n, (linv ? 0 : LIFT_FROM_Q) | LIFT_ROUND, lc));
   }
-  rc = capi_do_crt(P, s, out, rows, true); if (rc) return rc;
-  if (linv) { rc = capi_run_prog(P, P.prog_linv, s, out, rows, nullptr); if (rc) return rc; }
-  return launch_khprf_round(s, out, rows * P.n, p, f->mc) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  rc = do_crt(P, s, out, rows, true); if (rc) return rc;
+  rc = run_prog_or_copy(P, P.prog_linv, s, out, rows); if (rc) return rc;
+  return hip_status(launch_khprf_round(s, out, rows * P.n, p, f->mc));
 }
 
 }  // extern "C"

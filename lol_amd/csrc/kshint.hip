@@ -11,9 +11,9 @@
 // — the values lolhip_gadget returns, with no per-call table to upload.
 #include <hip/hip_runtime.h>
 
+#include "elementwise_dev.h"
 #include "pipeline.h"
 #include "rng_dev.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
@@ -87,9 +87,9 @@ hipError_t launch_kshint_combine(hipStream_t s, const i64* e_crt, const i64* val
   const i64 nT = n * dp.T, rows = B * dp.L;
   if (rows == 0 || nT == 0) return hipSuccess;
   if (dp.T < 1 || dp.T > PIPE_MAX_T) return hipErrorInvalidValue;
-  const i64 x = ((nT + 3) / 4 + TPB - 1) / TPB;
-  if (x > 0x7fffffff) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)x, (unsigned)(rows < (i64)MAX_GRID_Y ? rows : MAX_GRID_Y));
+  unsigned x;
+  if (!tiles_for((nT + 3) / 4, TPB, &x)) return hipErrorInvalidValue;
+  const dim3 grid(x, (unsigned)(rows < (i64)MAX_GRID_Y ? rows : MAX_GRID_Y));
   hipLaunchKernelGGL(k_kshint_combine, grid, dim3(TPB), 0, s, e_crt, vals, s_crt, hints, B, nT, dp, mod, key, ctr);
   return hipGetLastError();
 }

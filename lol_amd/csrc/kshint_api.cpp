@@ -9,27 +9,11 @@ using namespace lolhip;
 
 namespace {
 
-// the digit counts of `base` over the plan's moduli: the part of the decomposition parameters the gadget needs
-// (make_decomp of the key switch, capi.cpp, decides the same statuses: T > 16, base neither 0 nor >= 2)
-int hint_decomp(const Plan& P, int64_t base, DecompParams& d) {
-  if (P.T > PIPE_MAX_T || (base != 0 && base < 2)) return LOLHIP_ERR_INVALID;
-  d = DecompParams{};
-  d.T = P.T;
-  d.base = base;
-  for (int t = 0; t < P.T; ++t) {
-    int k = 0;
-    if (base == 0) k = 1;
-    else for (u64 q = P.qs[t]; q != 0; q /= (u64)base) ++k;      // gadlen (ZqBasic.hs:238-240)
-    d.k[t] = k;
-    d.L += k;
-  }
-  return LOLHIP_OK;
-}
-
-// every status of a ksHint call over plan p (B rows of L samples each), decided on the host
+// every status of a ksHint call over plan p (B rows of L samples each), decided on the host; d: the decomposition
+// parameters of the key switch (launch_kshint_combine reads T, L, base and the digit counts)
 int hint_status(const Plan& P, double svar, int64_t base, int64_t B, DecompParams& d) {
   if (!svar_ok(svar) || B < 0) return LOLHIP_ERR_INVALID;
-  int rc = hint_decomp(P, base, d); if (rc) return rc;
+  int rc = make_decomp(P, base, d); if (rc) return rc;
   rc = sampler_ok(P); if (rc) return rc;
   if (!P.has_crt) return LOLHIP_ERR_NO_CRT;
   return LOLHIP_OK;
@@ -49,10 +33,9 @@ int kshint_launch(const Plan& P, hipStream_t s, const int64_t* s_crt, const int6
   double* dbl = two_power(P) ? nullptr : reinterpret_cast<double*>(work + BL * P.n * P.T);
   int rc = sample_error(P, s, dbl, nullptr, 1, e, ENC_WRITE, k, ctr, CHACHA_DOM_HINT_GAUSS, deviation(P, svar), BL);
   if (rc) return rc;
-  if (!P.prog_l.stages.empty()) { rc = capi_run_prog(P, P.prog_l, s, e, BL, nullptr); if (rc) return rc; }
-  rc = capi_do_crt(P, s, e, BL, false); if (rc) return rc;
-  return launch_kshint_combine(s, e, vals_crt, s_crt, hints, B, P.n, d, P.d_mod, k, ctr) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  rc = run_prog_or_copy(P, P.prog_l, s, e, BL); if (rc) return rc;
+  rc = do_crt(P, s, e, BL, false); if (rc) return rc;
+  return hip_status(launch_kshint_combine(s, e, vals_crt, s_crt, hints, B, P.n, d, P.d_mod, k, ctr));
 }
 
 }  // namespace
@@ -62,13 +45,13 @@ extern "C" {
 int64_t lolhip_kshint_work_len(const lolhip_plan* pq, int64_t base, int64_t B) {
   if (!pq || B < 0) return LOLHIP_ERR_INVALID;
   DecompParams d;
-  const int rc = hint_decomp(pq->P, base, d); if (rc) return rc;
+  const int rc = make_decomp(pq->P, base, d); if (rc) return rc;
   return hint_work_len(pq->P, d.L, B);
 }
 
 int lolhip_kshint_batch(const lolhip_plan* pq, void* stream, const int64_t* s_crt, const int64_t* vals_crt, double svar,
                         int64_t base, const uint8_t key[32], uint64_t ctr, int64_t* hints_out, int64_t* work, int64_t B) {
-  int rc = capi_need_device(pq); if (rc) return rc;
+  int rc = need_device(pq); if (rc) return rc;
   DecompParams d;
   rc = hint_status(pq->P, svar, base, B, d); if (rc) return rc;
   if (B > 0 && (!s_crt || !vals_crt || !key || !hints_out || !work)) return LOLHIP_ERR_INVALID;
@@ -82,7 +65,7 @@ int64_t lolhip_tunnel_hint_work_len(const lolhip_ext* x_er, const lolhip_ext* x_
   if (!x_er || !x_es) return LOLHIP_ERR_INVALID;
   const ExtPlan &ER = x_er->X, &ES = x_es->X;
   DecompParams d;
-  const int rc = hint_decomp(*ES.hi, base, d); if (rc) return rc;
+  const int rc = make_decomp(*ES.hi, base, d); if (rc) return rc;
   const int64_t rel = ER.host.phi2 / ER.host.phi, T = ER.lo->T, nE = ER.host.phi, nR = ER.host.phi2,
                 nS = ES.host.phi2;
   const int64_t lin = rel * nR * T + rel * rel * (nE + nS) * T, ks = hint_work_len(*ES.hi, d.L, rel);
@@ -113,10 +96,10 @@ int lolhip_tunnel_hint_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, voi
   int64_t* ev = sp + rel * nR * T;                                 // evalLin scratch
   int64_t* ks = sp;                                                // ksHint scratch, after evalLin
   if (launch_unit_rows(s, sp, ER.d_coeffs, rel, nR, (int)T, ER.host.phi) != hipSuccess) return LOLHIP_ERR_HIP;
-  rc = capi_do_crt(PR, s, sp, rel, false); if (rc) return rc;
+  rc = do_crt(PR, s, sp, rel, false); if (rc) return rc;
   if (launch_sk_eval(s, sp, 1, true, s_in_crt, sp, rel, nR, (int)T, PR.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
-  rc = capi_do_crt(PR, s, sp, rel, true); if (rc) return rc;
-  if (!PR.prog_linv.stages.empty()) { rc = capi_run_prog(PR, PR.prog_linv, s, sp, rel, nullptr); if (rc) return rc; }
+  rc = do_crt(PR, s, sp, rel, true); if (rc) return rc;
+  rc = run_prog_or_copy(PR, PR.prog_linv, s, sp, rel); if (rc) return rc;
   rc = lolhip_evallin_batch(x_er, x_es, stream, sp, ys_crt, comps, ev, rel); if (rc) return rc;
   return kshint_launch(PS, s, s_out_crt, comps, svar, d, key, ctr, hints_out, ks, rel);
 }

@@ -12,17 +12,13 @@
 // The constants travel by value in the kernel arguments (wave-uniform: they stay in SGPRs).  No LDS.
 #include <hip/hip_runtime.h>
 
+#include "elementwise_dev.h"
 #include "modswitch.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
 namespace {
 constexpr int TPB = 256;                     // one row per thread: a tile is TPB rows
-
-typedef u64 ms_u64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u64 trim(u64 r, u64 q) { return r >= q ? r - q : r; }   // [0, 2q) -> [0, q)
 }  // namespace
 
 // SH = d - u: D = SH leading components dropped or U = -SH zero components added.  VIN / VOUT: the rows of the input /
@@ -84,8 +80,8 @@ k_modswitch(const i64* __restrict__ in0, i64 rows0, const i64* __restrict__ in, 
 #pragma unroll
     for (int j = 0; j + 1 < PIPE_MAX_T - D + U && j < PIPE_MAX_T; j += 2)
       if (j < To) {
-        ms_u64x2 v; v.x = o(j); v.y = o(j + 1);
-        *reinterpret_cast<ms_u64x2*>(dst + j) = v;
+        u64x2 v; v.x = o(j); v.y = o(j + 1);
+        *reinterpret_cast<u64x2*>(dst + j) = v;
       }
   } else {
 #pragma unroll
@@ -101,11 +97,11 @@ hipError_t launch_modswitch(hipStream_t s, const i64* in0, i64 rows0, const i64*
   if (p.T < 1 || p.T > PIPE_MAX_T || p.d < 0 || p.d > MODSW_MAX_D || p.u < 0 || p.u > MODSW_MAX_D || (p.d && p.u) ||
       To < 1 || To > PIPE_MAX_T || rows0 < 0 || rows0 > rows)
     return hipErrorInvalidValue;
-  const i64 b = (rows + TPB - 1) / TPB;
-  if (b > 0x7fffffff) return hipErrorInvalidValue;
+  unsigned blocks;
+  if (!tiles_for(rows, TPB, &blocks)) return hipErrorInvalidValue;
   const bool vin = (p.T & 1) == 0 && ((((uintptr_t)in0) | ((uintptr_t)in)) & 15) == 0;
   const bool vout = (To & 1) == 0 && (((uintptr_t)out) & 15) == 0;
-  const dim3 grid((unsigned)b), block(TPB);
+  const dim3 grid(blocks), block(TPB);
 #define LOLHIP_MS(SS)                                                                                             \
   case SS:                                                                                                        \
     if (vin) { if (vout) hipLaunchKernelGGL((k_modswitch<SS, true, true>), grid, block, 0, s, in0, rows0, in, out, rows, p);   \

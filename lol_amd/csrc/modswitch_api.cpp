@@ -1,36 +1,22 @@
 // lol_amd/csrc/modswitch_api.cpp — the C ABI of ciphertext modSwitch and multi-hop tunnelling (include/lolhip.h;
-// lol-apps SymmSHE.hs:236-246, HomomPRF.hs:153-155, 427-431): host checks, the per-modulus constants and the launch
-// plans over k_modswitch (modswitch.hip), lolhip_tunnel_batch and the existing transforms.
+// lol-apps SymmSHE.hs:236-246, HomomPRF.hs:153-155, 427-431): host checks, the per-modulus constants (the encoding
+// factors are she_host.h's) and the launch plans over k_modswitch (modswitch.hip), lolhip_tunnel_batch and the existing
+// transforms.
 #include <hip/hip_runtime_api.h>
 
 #include <memory>
 #include <vector>
 
-#include "capi_internal.h"
-#include "hostmath.h"
 #include "modswitch.h"
+#include "she_host.h"
 
 using namespace lolhip;
 
 namespace {
 
-constexpr int64_t P_MAX = (int64_t)1 << 62;
-
 // the bases a side of the internal call may be in.  B_MIXED is what the rescale itself works in and what a tunnel
 // hop takes: c_0 in the decoding basis, the other components in the powerful basis
 enum Basis { B_POW = 0, B_CRT = 1, B_MIXED = 2 };
-
-u64 canon(int64_t x, u64 q) {
-  const int64_t r = (int64_t)((__int128)x % (__int128)q);
-  return r < 0 ? (u64)(r + (int64_t)q) : (u64)r;
-}
-
-bool same_index(const Plan& a, const Plan& b) {
-  if (a.m != b.m || a.pps.size() != b.pps.size()) return false;
-  for (size_t i = 0; i < a.pps.size(); ++i)
-    if (a.pps[i].p != b.pps[i].p || a.pps[i].e != b.pps[i].e) return false;
-  return true;
-}
 
 // tail's moduli are the last tail.T of all's
 bool is_suffix(const std::vector<u64>& all, const std::vector<u64>& tail) {
@@ -52,20 +38,15 @@ int relation(const Plan& F, const Plan& G, int* d, int* u) {
 
 // every constant of the pass and l' (the statuses of p and of the inverses)
 int make_params(const Plan& F, const Plan& G, int d, int u, int enc, int64_t l, int64_t p, ModSwitchParams& mp, u64* l2) {
-  if (p < 2 || p >= P_MAX) return LOLHIP_ERR_MODULUS;
-  const u64 up = (u64)p;
+  if (!p_ok(p)) return LOLHIP_ERR_MODULUS;
+  u64 zq[PIPE_MAX_T], zp = 1;
+  if (enc == 0) { const int rc = encode_scales(F, p, true, zq, &zp); if (rc) return rc; }      // lsdToMSD
   mp = ModSwitchParams();
   mp.T = F.T; mp.d = d; mp.u = u;
   mp.scaled = (enc == 0 || u > 0) ? 1 : 0;
-  u64 qmod = 1 % up;
   for (int t = 0; t < F.T; ++t) {
     const u64 q = F.qs[(size_t)t];
-    qmod = mulmod(qmod, q % up, up);
-    u64 sc = 1 % q;
-    if (enc == 0) {                                            // lsdToMSD: p^-1 mod q_t (ZqBasic.hs:132-137)
-      sc = invmod(up % q, q);
-      if (sc == 0) return LOLHIP_ERR_MODULUS;
-    }
+    u64 sc = enc == 0 ? zq[t] : 1 % q;
     for (int a = 0; a < u; ++a) sc = mulmod(sc, G.qs[(size_t)a] % q, q);
     mp.q[t] = q;
     mp.s[t] = sc;
@@ -79,7 +60,7 @@ int make_params(const Plan& F, const Plan& G, int d, int u, int enc, int64_t l, 
       mp.inv[i][t] = w;
       mp.invp[i][t] = make_shoup(w, q).wp;
     }
-  *l2 = enc == 0 ? mulmod(canon(l, up), (up - qmod) % up, up) : canon(l, up);
+  *l2 = encode_l(l, zp, (u64)p);
   return LOLHIP_OK;
 }
 
@@ -108,27 +89,27 @@ int run(const Switch1& w, hipStream_t s, const int64_t* cs, int ncs, int in_b, i
   const int64_t *in0 = cs, *in = cs;
   // the scale alone (d = u = 0) is per modulus and commutes with the Z_q-linear l / lInv: no trip through the decoding basis
   const bool dec_in = in_b != B_MIXED && !(w.mp.d == 0 && w.mp.u == 0 && out_b != B_MIXED) && !F.prog_linv.stages.empty();
-  const bool dec_out = out_b != B_MIXED && !(w.mp.d == 0 && w.mp.u == 0 && in_b != B_MIXED) && !G.prog_l.stages.empty();
+  const bool dec_out = out_b != B_MIXED && !(w.mp.d == 0 && w.mp.u == 0 && in_b != B_MIXED);
   int rc;
   if (in_b == B_CRT) {
     if (hipMemcpyAsync(work, cs, sizeof(int64_t) * (size_t)(ncs * slab), hipMemcpyDeviceToDevice, s) != hipSuccess)
       return LOLHIP_ERR_HIP;
-    rc = capi_do_crt(F, s, work, (int64_t)ncs * B, true); if (rc) return rc;
+    rc = do_crt(F, s, work, (int64_t)ncs * B, true); if (rc) return rc;
     in0 = in = work;
   }
   if (dec_in) {                                                       // c_0 -> decoding basis (empty for m = 2^k)
-    rc = capi_run_prog(F, F.prog_linv, s, work, B, in0 == work ? nullptr : cs); if (rc) return rc;
+    rc = run_prog(F, F.prog_linv, s, work, B, in0 == work ? nullptr : cs); if (rc) return rc;
     in0 = work;
   }
   if (launch_modswitch(s, in0, B * F.n, in, out, (i64)ncs * B * F.n, w.mp) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (dec_out) { rc = capi_run_prog(G, G.prog_l, s, out, B, nullptr); if (rc) return rc; }
-  if (out_b == B_CRT) { rc = capi_do_crt(G, s, out, (int64_t)ncs * B, false); if (rc) return rc; }
+  if (dec_out) { rc = run_prog_or_copy(G, G.prog_l, s, out, B); if (rc) return rc; }      // empty for m = 2^k
+  if (out_b == B_CRT) { rc = do_crt(G, s, out, (int64_t)ncs * B, false); if (rc) return rc; }
   return LOLHIP_OK;
 }
 
 int need_both(const lolhip_plan* a, const lolhip_plan* b) {
-  const int rc = capi_need_device(a);
-  return rc ? rc : capi_need_device(b);
+  const int rc = need_device(a);
+  return rc ? rc : need_device(b);
 }
 
 i64 modswitch_words(const Plan& F, int ncs, int64_t B) { return (i64)ncs * B * F.n * F.T; }
@@ -190,7 +171,7 @@ int lolhip_tunnel_chain_create(int nhops, const lolhip_ext* const* x_er, const l
       return LOLHIP_ERR_INVALID;
     if (i > 0 && !same_index(*x_es[i - 1]->X.hi, *ER.hi)) return LOLHIP_ERR_INVALID;
     DecompParams dp;
-    const int rc = capi_make_decomp(*ES.hi, base, dp); if (rc) return rc;
+    const int rc = make_decomp(*ES.hi, base, dp); if (rc) return rc;
     c->er.push_back(x_er[i]); c->es.push_back(x_es[i]); c->ys.push_back(ys_crt[i]); c->hints.push_back(hints[i]);
     if (ES.hi->n > c->n_max) c->n_max = ES.hi->n;
   }
@@ -253,8 +234,8 @@ int lolhip_tunnel_chain_batch(const lolhip_tunnel_chain* c, void* stream, const 
     if (rc) return rc;
     cur ^= 1;
     // back to (decoding, powerful): what the next hop and the rescale take
-    rc = capi_do_crt(S, s, buf[cur], 2 * B, true); if (rc) return rc;
-    if (!S.prog_linv.stages.empty()) { rc = capi_run_prog(S, S.prog_linv, s, buf[cur], B, nullptr); if (rc) return rc; }
+    rc = do_crt(S, s, buf[cur], 2 * B, true); if (rc) return rc;
+    rc = run_prog_or_copy(S, S.prog_linv, s, buf[cur], B); if (rc) return rc;
   }
   rc = run(down, s, buf[cur], 2, B_MIXED, out, out_crt ? B_CRT : B_POW, sub, B); if (rc) return rc;
   *l_out = (int64_t)down.l2;                                          // last: not written where a launch fails

@@ -15,8 +15,8 @@
 
 #include <type_traits>
 
+#include "elementwise_dev.h"
 #include "pipeline.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
@@ -27,12 +27,6 @@ typedef unsigned __int128 u128;
 // component) is divided once per workgroup in 64 bits and per element in 32 bits only.
 constexpr int EPT = 2;                       // elements per thread
 constexpr i64 TILE = 256 * EPT;
-static inline bool tiles_for(i64 total, unsigned* blocks) {
-  const i64 b = (total + TILE - 1) / TILE;
-  if (b > 0x7fffffff) return false;
-  *blocks = (unsigned)(b < 1 ? 1 : b);
-  return true;
-}
 
 // ---------------------------------------------------------------------------------------
 // ct x ct
@@ -69,7 +63,7 @@ hipError_t launch_ctmul(hipStream_t s, const i64* c0, const i64* c1, const i64* 
   const i64 total = B * n * T;
   if (total == 0) return hipSuccess;
   unsigned blocks;
-  if (!tiles_for(total, &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(total, TILE, &blocks)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_ctmul, dim3(blocks), dim3(256), 0, s, c0, c1, d0, d1, e0, e1, e2, gcrt, total,
                      (u32)(n * T), T, mod);
   return hipGetLastError();
@@ -86,20 +80,12 @@ __device__ __forceinline__ i64 floor_div(i64 x, const DecompParams& p) {
   return x >= 0 ? (i64)q : -(i64)q - 1;
 }
 
-// residue of a signed integer (|d| < 2^63) modulo q
-__device__ __forceinline__ u64 reduce_signed(i64 d, const ModCtx& mc) {
-  const u64 a = d >= 0 ? (u64)d : (u64)(-d);
-  const u64 r = rem128(0, a, mc);
-  return (d < 0 && r != 0) ? mc.q - r : r;
-}
-
 // One thread per ROW (coefficient): the T components are lifted and their digits extracted once, every
 // digit is reduced into the T target components and stored as one contiguous T-word chunk, so a wave
 // writes 64 * T consecutive words per digit.  (The first version ran one thread per output column: every
 // digit was extracted T times and a store instruction covered only every T-th word.)
 // Q32: every modulus below 2^31 and base <= 2^31: digits fit 31 bits, one-word Barrett reduction.
 // V2: T = 2 and a 16-byte aligned digit slab: the pair goes out as one 16-byte store.
-typedef u64 dec_u64x2 __attribute__((ext_vector_type(2)));
 template <bool Q32, bool V2>
 __global__ void __launch_bounds__(256)
 k_decompose(const i64* __restrict__ c, i64* __restrict__ digits, i64 rows, DecompParams p,
@@ -115,14 +101,14 @@ k_decompose(const i64* __restrict__ c, i64* __restrict__ digits, i64 rows, Decom
       x = min(x, x - q);
       return (u64)((d < 0 && x != 0) ? q - x : x);
     } else {
-      return reduce_signed(d, mod[s]);
+      return mod_any(d, mod[s]);
     }
   };
   auto put = [&](i64 j, i64 r, i64 d) {                       // digit j of row r: reduced into every component
     i64* o = digits + (j * rows + r) * T;
     if constexpr (V2) {
-      dec_u64x2 w; w.x = red(d, 0); w.y = red(d, 1);
-      *reinterpret_cast<dec_u64x2*>(o) = w;
+      u64x2 w; w.x = red(d, 0); w.y = red(d, 1);
+      *reinterpret_cast<u64x2*>(o) = w;
     } else {
       for (int s = 0; s < T; ++s) o[s] = (i64)red(d, s);
     }
@@ -154,7 +140,7 @@ hipError_t launch_decompose(hipStream_t s, const i64* c, i64* digits, i64 B, i64
   const i64 rows = B * n;
   if (rows == 0) return hipSuccess;
   unsigned blocks;
-  if (!tiles_for(rows, &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(rows, TILE, &blocks)) return hipErrorInvalidValue;
   const bool fast = q32 && p.base <= ((i64)1 << 31);
   const bool v2 = p.T == 2 && (((uintptr_t)digits) & 15) == 0;
 #define LOLHIP_DEC(QQ, VV) hipLaunchKernelGGL((k_decompose<QQ, VV>), dim3(blocks), dim3(256), 0, s, c, digits, rows, p, mod)
@@ -190,8 +176,7 @@ k_knapsack(const i64* __restrict__ xs, int L, const i64* __restrict__ hint, cons
     for (int k = 0; k < K; ++k) acc[k] = 0;
     auto fold = [&](Acc a) -> u64 {
       if constexpr (Q32) {
-        const u64 rr = (u64)a - __umul64hi((u64)a, mc.mu) * mc.q;       // [0, 2q)
-        return rr >= mc.q ? rr - mc.q : rr;
+        return trim((u64)a - __umul64hi((u64)a, mc.mu) * mc.q, mc.q);
       } else {
         return reduce128((u64)((u128)a >> 64), (u64)a, mc);
       }
@@ -223,7 +208,7 @@ hipError_t launch_knapsack(hipStream_t s, const i64* xs, int L, const i64* hint,
   const i64 total = B * n * T;
   if (total == 0) return hipSuccess;
   unsigned blocks;
-  if (!tiles_for(total, &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(total, TILE, &blocks)) return hipErrorInvalidValue;
   const dim3 grid(blocks), block(256);
   const u32 per = (u32)(n * T);
 #define LOLHIP_KS(KK, QQ) hipLaunchKernelGGL((k_knapsack<KK, QQ>), grid, block, 0, s, xs, L, hint, addend, out, total, per, T, mod)
@@ -263,7 +248,7 @@ k_rescale(const i64* __restrict__ c, i64* __restrict__ out, i64 rows, RescalePar
     const u64 a = canon_in(c[r * p.T], qa);
     const i64 z = (2 * a < qa) ? (i64)a : (i64)a - (i64)qa;      // lift a
     const u64 b = canon_in(c[r * p.T + s], ms.q);
-    out[g] = (i64)mulmod(submod(b, reduce_signed(z, ms), ms.q), p.qa_inv[s], ms);
+    out[g] = (i64)mulmod(submod(b, mod_any(z, ms), ms.q), p.qa_inv[s], ms);
   }
 }
 
@@ -272,7 +257,7 @@ hipError_t launch_rescale(hipStream_t s, const i64* c, i64* out, i64 B, i64 n, c
   const i64 rows = B * n;
   if (rows == 0 || p.T < 2) return hipSuccess;
   unsigned blocks;
-  if (!tiles_for(rows * (p.T - 1), &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(rows * (p.T - 1), TILE, &blocks)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_rescale, dim3(blocks), dim3(256), 0, s, c, out, rows, p, mod);
   return hipGetLastError();
 }
@@ -314,7 +299,7 @@ hipError_t launch_coeffs(hipStream_t s, i64* out, const i64* in, const int32_t* 
   const i64 total = B * n_hi * T;
   if (total == 0) return hipSuccess;
   unsigned blocks;
-  if (!tiles_for(total, &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(total, TILE, &blocks)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_coeffs, dim3(blocks), dim3(256), 0, s, out, in, idx, B, (u32)n_lo, (u32)n_hi, T, mod);
   return hipGetLastError();
 }

@@ -11,8 +11,8 @@
 // 64 bits and walks its words in 32 bits.  V2: two words per lane, 16-byte loads and plain 16-byte global stores.
 #include <hip/hip_runtime.h>
 
+#include "elementwise_dev.h"
 #include "public.h"
-#include "zq_dev.h"
 
 namespace lolhip {
 
@@ -20,26 +20,7 @@ namespace {
 constexpr int TPB = 256;
 constexpr int EPT = 2;                       // accesses per thread
 
-typedef u64 pub_u64x2 __attribute__((ext_vector_type(2)));
-
-bool tiles(i64 total, i64 tile, unsigned* blocks) {
-  const i64 b = (total + tile - 1) / tile;
-  if (b > 0x7fffffff) return false;
-  *blocks = (unsigned)(b < 1 ? 1 : b);
-  return true;
-}
-
-__device__ __forceinline__ u64 scale_mod(u64 x, u64 w, u64 wp, u64 q) {
-  const u64 r = shoup_lazy(x, w, wp, q);              // [0, 2q)
-  return r >= q ? r - q : r;
-}
-
-// x mod q of any int64 (INT64_MIN included)
-__device__ __forceinline__ u64 mod_any(i64 x, const ModCtx& mc) {
-  const u64 a = x >= 0 ? (u64)x : 0 - (u64)x;
-  const u64 r = rem128(0, a, mc);
-  return (x < 0 && r != 0) ? mc.q - r : r;
-}
+__device__ __forceinline__ u64 scale_mod(u64 x, u64 w, u64 wp, u64 q) { return trim(shoup_lazy(x, w, wp, q), q); }
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
@@ -84,8 +65,8 @@ k_ct_lincomb(const i64* a, int na, const i64* b, int nb, i64* out, i64 total, i6
     }
     // every input word is read before the store: out may alias a or b
     if constexpr (V2) {
-      pub_u64x2 v; v.x = o[0]; v.y = o[1];
-      *reinterpret_cast<pub_u64x2*>(out + g) = v;
+      u64x2 v; v.x = o[0]; v.y = o[1];
+      *reinterpret_cast<u64x2*>(out + g) = v;
     } else {
       out[g] = (i64)o[0];
     }
@@ -100,7 +81,7 @@ hipError_t launch_ct_lincomb(hipStream_t s, const i64* a, int na, const i64* b, 
   if (sc.T < 1 || sc.T > PIPE_MAX_T || slab % sc.T) return hipErrorInvalidValue;
   const bool v2 = (slab & 1) == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out)) & 15) == 0;
   unsigned blocks;
-  if (!tiles(total, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(total, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
   const bool hb = b && nb > 0;
 #define LOLHIP_LC(VV, BB) \
   hipLaunchKernelGGL((k_ct_lincomb<VV, BB>), dim3(blocks), dim3(TPB), 0, s, a, na, b, hb ? nb : 0, out, total, slab, sc)
@@ -191,8 +172,8 @@ k_pub_apply(const i64* __restrict__ a, i64 a_item, const int32_t* __restrict__ i
       }
     }
     if constexpr (V2) {
-      pub_u64x2 v; v.x = o[0]; v.y = o[1];
-      *reinterpret_cast<pub_u64x2*>(out + g) = v;
+      u64x2 v; v.x = o[0]; v.y = o[1];
+      *reinterpret_cast<u64x2*>(out + g) = v;
     } else {
       out[g] = (i64)o[0];
     }
@@ -208,7 +189,7 @@ hipError_t launch_pub_apply(hipStream_t s, int mode, const i64* a, i64 a_item, c
   const i64 c_item = c_shared ? 0 : per, c_comp = c_shared ? per : B * per;
   const bool v2 = (per & 1) == 0 && ((((uintptr_t)c) | ((uintptr_t)out)) & 15) == 0;
   unsigned blocks;
-  if (!tiles(total, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
+  if (!tiles_for(total, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
 #define LOLHIP_PA(MM, VV)                                                                                       \
   hipLaunchKernelGGL((k_pub_apply<MM, VV>), dim3(blocks), dim3(TPB), 0, s, a, a_item, idx, c, c_item, c_comp, out, B, \
                      total, (u32)per, sc, mod)

@@ -3,43 +3,12 @@
 // public.hip and the existing transforms.
 #include <hip/hip_runtime_api.h>
 
-#include "capi_internal.h"
-#include "hostmath.h"
 #include "public.h"
+#include "she_host.h"
 
 using namespace lolhip;
 
 namespace {
-
-constexpr int64_t P_MAX = (int64_t)1 << 62;
-
-u64 canon(int64_t x, u64 q) {
-  const int64_t r = (int64_t)((__int128)x % (__int128)q);
-  return r < 0 ? (u64)(r + (int64_t)q) : (u64)r;
-}
-
-// Q mod p, Q = prod q_t
-u64 q_mod(const Plan& P, u64 p) {
-  u64 r = 1 % p;
-  for (u64 q : P.qs) r = mulmod(r, q % p, p);
-  return r;
-}
-
-// the encoding factors of ZqBasic.hs:132-137 over the product ring (Prelude.hs:310-315):
-//   lsdToMSD = (-Q mod p, p^-1 mod q_t),   msdToLSD = ((-Q)^-1 mod p, p mod q_t)
-int encode_scales(const Plan& P, int64_t p, bool to_msd, u64* zq, u64* zp) {
-  if (p < 2 || p >= P_MAX) return LOLHIP_ERR_MODULUS;
-  const u64 up = (u64)p;
-  const u64 negq = (up - q_mod(P, up)) % up;
-  for (int t = 0; t < P.T; ++t) {
-    const u64 q = P.qs[(size_t)t];
-    zq[t] = to_msd ? invmod(up % q, q) : up % q;
-    if (to_msd && zq[t] == 0) return LOLHIP_ERR_MODULUS;
-  }
-  *zp = to_msd ? negq : invmod(negq, up);
-  if (!to_msd && *zp == 0) return LOLHIP_ERR_MODULUS;
-  return LOLHIP_OK;
-}
 
 void set_scale(PubScales& sc, const Plan& P, const u64* a, const u64* b) {
   sc = PubScales();
@@ -58,9 +27,7 @@ void set_scale(PubScales& sc, const Plan& P, const u64* a, const u64* b) {
 const Plan* lo_plan(const Plan& P, const lolhip_ext* x_q) {
   if (!x_q) return &P;
   const ExtPlan& X = x_q->X;
-  if (X.hi->m != P.m || X.hi->qs != P.qs || X.hi->pps.size() != P.pps.size()) return nullptr;
-  for (size_t i = 0; i < P.pps.size(); ++i)
-    if (X.hi->pps[i].p != P.pps[i].p || X.hi->pps[i].e != P.pps[i].e) return nullptr;
+  if (!same_index(*X.hi, P) || X.hi->qs != P.qs) return nullptr;
   return X.lo;
 }
 
@@ -81,7 +48,7 @@ int public_checks(const lolhip_plan* pq, const lolhip_ext* x_q, int64_t stride, 
 
 // device checks: the plans and the ext's tables live on the calling thread's device
 int public_device(const lolhip_plan* pq, const lolhip_ext* x_q) {
-  int rc = capi_need_device(pq); if (rc) return rc;
+  int rc = need_device(pq); if (rc) return rc;
   if (x_q && (!x_q->X.d_embed_pow || !x_q->X.d_embed_crt || !x_q->X.lo->device)) return LOLHIP_ERR_NO_DEVICE;
   return LOLHIP_OK;
 }
@@ -107,7 +74,7 @@ int lolhip_ct_lincomb_batch(const lolhip_plan* pq, void* stream, const int64_t* 
   if (na < 1 || nb < 0 || B < 0 || P.T > PIPE_MAX_T || !alpha || (nb > 0 && (!b || !beta)) || (nb == 0 && b))
     return LOLHIP_ERR_INVALID;
   if (B > 0 && (!a || !out)) return LOLHIP_ERR_INVALID;
-  int rc = capi_need_device(pq); if (rc) return rc;
+  int rc = need_device(pq); if (rc) return rc;
   if (B == 0) return LOLHIP_OK;
   u64 al[PIPE_MAX_T], be[PIPE_MAX_T];
   for (int t = 0; t < P.T; ++t) {
@@ -116,8 +83,7 @@ int lolhip_ct_lincomb_batch(const lolhip_plan* pq, void* stream, const int64_t* 
   }
   PubScales sc;
   set_scale(sc, P, al, be);
-  return launch_ct_lincomb((hipStream_t)stream, a, na, nb > 0 ? b : nullptr, nb, out, B * P.n * P.T, sc) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_ct_lincomb((hipStream_t)stream, a, na, nb > 0 ? b : nullptr, nb, out, B * P.n * P.T, sc));
 }
 
 int64_t lolhip_public_work_len(const lolhip_plan* pq, const lolhip_ext* x_q, int64_t B) {
@@ -142,15 +108,15 @@ int lolhip_add_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, const 
   if ((enc != 0 && enc != 1) || k < 0 || !l_out) return LOLHIP_ERR_INVALID;
   if (k > 0 && (!pp_m || pp_m->P.T != 1 || pp_m->P.m != lo->m || (int64_t)pp_m->P.qs[0] != p)) return LOLHIP_ERR_INVALID;
   if (cs_crt && (!P.has_crt || !lo->has_crt)) return LOLHIP_ERR_NO_CRT;
-  if (p < 2 || p >= P_MAX) return LOLHIP_ERR_MODULUS;
+  if (!p_ok(p)) return LOLHIP_ERR_MODULUS;
   const u64 up = (u64)p;
   u64 zq[PIPE_MAX_T], zp = 1;
   if (enc == 1) { rc = encode_scales(P, p, false, zq, &zp); if (rc) return rc; }      // msdToLSD
-  const u64 l2 = mulmod(canon(l, up), zp, up);                                     // l after toLSD
+  const u64 l2 = encode_l(l, zp, up);                                              // l after toLSD
   const u64 linv = invmod(l2, up);
   if (linv == 0) return LOLHIP_ERR_MODULUS;
   rc = public_device(pq, x_q); if (rc) return rc;
-  if (k > 0) { rc = capi_need_device(pp_m); if (rc) return rc; }
+  if (k > 0) { rc = need_device(pp_m); if (rc) return rc; }
   *l_out = (int64_t)l2;
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -161,19 +127,19 @@ int lolhip_add_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, const 
     const Plan& PP = pp_m->P;
     int64_t* pw = work + items * n_m * P.T;                          // [items][n_m] residues mod p
     if (launch_pub_lift(s, b_pow, b_stride, items, n_m, pw, 1, PP.d_mod, mp, 1) != hipSuccess) return LOLHIP_ERR_HIP;
-    for (int64_t i = 0; i < k && !PP.prog_gpow.stages.empty(); ++i) {
-      rc = capi_run_prog(PP, PP.prog_gpow, s, pw, items, nullptr); if (rc) return rc;
+    for (int64_t i = 0; i < k; ++i) {
+      rc = run_prog_or_copy(PP, PP.prog_gpow, s, pw, items); if (rc) return rc;
     }
     if (launch_pub_lift(s, pw, n_m, items, n_m, lifted, P.T, lo->d_mod, mp, linv) != hipSuccess) return LOLHIP_ERR_HIP;
   } else if (launch_pub_lift(s, b_pow, b_stride, items, n_m, lifted, P.T, lo->d_mod, mp, linv) != hipSuccess) {
     return LOLHIP_ERR_HIP;
   }
-  if (cs_crt) { rc = capi_do_crt(*lo, s, lifted, items, false); if (rc) return rc; }
+  if (cs_crt) { rc = do_crt(*lo, s, lifted, items, false); if (rc) return rc; }
   const int32_t* idx = x_q ? (cs_crt ? x_q->X.d_embed_crt : x_q->X.d_embed_pow) : nullptr;
   PubScales sc;
   set_scale(sc, P, enc == 1 ? zq : nullptr, nullptr);
-  return launch_pub_apply(s, PUB_ADD, lifted, b_stride == 0 ? 0 : n_m * P.T, idx, cs, cs_shared != 0, out, ncs, B, P.n,
-                          sc, P.d_mod) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_pub_apply(s, PUB_ADD, lifted, b_stride == 0 ? 0 : n_m * P.T, idx, cs, cs_shared != 0, out,
+                                     ncs, B, P.n, sc, P.d_mod));
 }
 
 // mulPublic (SymmSHE.hs:405-411): every c_i times embed (reduce (decode' a)), CRT basis.  Launch plan: k_pub_lift (a ->
@@ -185,18 +151,19 @@ int lolhip_mul_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, void* 
   int rc = public_checks(pq, x_q, a_stride, ncs, cs_shared, cs, out, work, a_pow, B, &lo); if (rc) return rc;
   const Plan& P = pq->P;
   if (!P.has_crt || !lo->has_crt) return LOLHIP_ERR_NO_CRT;
-  if (p < 2 || p >= P_MAX) return LOLHIP_ERR_MODULUS;
+  if (!p_ok(p)) return LOLHIP_ERR_MODULUS;
   rc = public_device(pq, x_q); if (rc) return rc;
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const i64 n_m = lo->n, items = a_stride == 0 ? 1 : B;
   if (launch_pub_lift(s, a_pow, a_stride, items, n_m, work, P.T, lo->d_mod, make_modctx((u64)p), 1) != hipSuccess)
     return LOLHIP_ERR_HIP;
-  rc = capi_do_crt(*lo, s, work, items, false); if (rc) return rc;
+  rc = do_crt(*lo, s, work, items, false); if (rc) return rc;
   PubScales sc;
   set_scale(sc, P, nullptr, nullptr);
-  return launch_pub_apply(s, PUB_MUL, work, a_stride == 0 ? 0 : n_m * P.T, x_q ? x_q->X.d_embed_crt : nullptr, cs,
-                          cs_shared != 0, out, ncs, B, P.n, sc, P.d_mod) == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_pub_apply(s, PUB_MUL, work, a_stride == 0 ? 0 : n_m * P.T,
+                                     x_q ? x_q->X.d_embed_crt : nullptr, cs, cs_shared != 0, out, ncs, B, P.n, sc,
+                                     P.d_mod));
 }
 
 }  // extern "C"

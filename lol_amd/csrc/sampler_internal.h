@@ -6,10 +6,9 @@
 
 #include <cmath>
 
-#include "capi_internal.h"
 #include "kernels.h"
-#include "pipeline.h"
 #include "rng_dev.h"
+#include "she_host.h"
 
 namespace lolhip {
 
@@ -51,13 +50,11 @@ inline bool svar_ok(double svar) { return std::isfinite(svar) && svar > 0; }
 inline int sample_error(const Plan& P, hipStream_t s, double* d, const int64_t* rep, int64_t p, int64_t* out, int mode,
                         const ChaChaKey& key, uint64_t ctr, int domain, double sigma, int64_t B) {
   if (two_power(P))
-    return launch_enc_error(s, nullptr, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma) == hipSuccess
-               ? LOLHIP_OK : LOLHIP_ERR_HIP;
+    return hip_status(launch_enc_error(s, nullptr, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma));
   if (launch_enc_gauss(s, d, B, P.n, key, ctr, domain, sigma) != hipSuccess) return LOLHIP_ERR_HIP;
   if (launch_gauss(s, d, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
     return LOLHIP_ERR_HIP;
-  return launch_enc_error(s, d, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma) == hipSuccess
-             ? LOLHIP_OK : LOLHIP_ERR_HIP;
+  return hip_status(launch_enc_error(s, d, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma));
 }
 
 }  // namespace lolhip

@@ -1,0 +1,96 @@
+// lol_amd/csrc/she_host.h — what the host translation units of the C ABI share: the handle types behind
+// include/lolhip.h, the launch helpers capi.cpp owns (defined there) and the one definition of every small piece of
+// SymmSHE host arithmetic and glue the *_api.cpp files need.  Pure host C++; not part of the public
+// interface.  A new feature adds here rather than copying.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include "hostmath.h"
+#include "lolhip.h"
+#include "pipeline.h"
+#include "plan.h"
+
+struct lolhip_plan { lolhip::Plan P; };
+struct lolhip_ext { lolhip::ExtPlan X; };
+
+namespace lolhip {
+
+// ---- defined in capi.cpp -----------------------------------------------------------------------------------------
+// LOLHIP_OK, or why the plan cannot compute on the calling thread's current device
+int need_device(const lolhip_plan* p);
+// y = program(src or y) over B polynomials (the vector interpreter or the scalar one)
+int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src = nullptr);
+// crt / crtInv of B polynomials in place, through whichever path the plan has
+int do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse);
+// 1 when divG is possible modulo every q_t of the plan
+int divg_ok(const Plan& P);
+// digit counts (gadlen, ZqBasic.hs:238-240) and the invariant-divisor constants of `base` over the plan's moduli
+int make_decomp(const Plan& P, int64_t base, DecompParams& d);
+
+// ---- glue --------------------------------------------------------------------------------------------------------
+inline int hip_status(hipError_t e) { return e == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP; }
+
+// y = program(src or y), or a copy when the program is empty (L and L^-1 of m = 2^k: the powerful and decoding
+// bases coincide)
+inline int run_prog_or_copy(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B,
+                            const int64_t* src = nullptr) {
+  if (!sp.stages.empty()) return run_prog(P, sp, s, y, B, src);
+  if (!src || src == y || B == 0) return LOLHIP_OK;
+  return hip_status(hipMemcpyAsync(y, src, sizeof(int64_t) * (size_t)(B * P.n * P.T), hipMemcpyDeviceToDevice, s));
+}
+
+// the same index with the same tensor order: m and every (p, e)
+inline bool same_index(const Plan& a, const Plan& b) {
+  if (a.m != b.m || a.pps.size() != b.pps.size()) return false;
+  for (size_t i = 0; i < a.pps.size(); ++i)
+    if (a.pps[i].p != b.pps[i].p || a.pps[i].e != b.pps[i].e) return false;
+  return true;
+}
+
+// floor(2^32 (2^l - base) / base) + 1, l = ceil(log2 base): the 32-bit invariant-divisor constant of the fused key
+// switches (1 for TrivGad, base = 0)
+inline uint32_t magic32(int64_t base) {
+  if (base < 2) return 1;
+  int lg = 0;
+  while (((u64)1 << lg) < (u64)base) ++lg;
+  return (uint32_t)((((u64)1 << 32) * (((u64)1 << lg) - (u64)base)) / (u64)base) + 1;
+}
+
+// ---- arithmetic over the plaintext modulus -------------------------------------------------------------------------
+// a plaintext modulus the SHE entries take: 2 <= p < 2^62
+inline bool p_ok(int64_t p) { return p >= 2 && p < ((int64_t)1 << 62); }
+
+// x mod q in [0, q) for any int64 x
+inline u64 canon(int64_t x, u64 q) {
+  const int64_t r = (int64_t)((__int128)x % (__int128)q);
+  return r < 0 ? (u64)(r + (int64_t)q) : (u64)r;
+}
+
+// Q mod p, Q = prod q_t
+inline u64 q_mod(const Plan& P, u64 p) {
+  u64 r = 1 % p;
+  for (u64 q : P.qs) r = mulmod(r, q % p, p);
+  return r;
+}
+
+// the encoding factors of ZqBasic.hs:132-137 over the product ring (Prelude.hs:310-315), P.T <= PIPE_MAX_T:
+//   lsdToMSD = (zp = -Q mod p, zq[t] = p^-1 mod q_t),   msdToLSD = (zp = (-Q)^-1 mod p, zq[t] = p mod q_t)
+// LOLHIP_ERR_MODULUS for a p out of range or where an inverse is missing
+inline int encode_scales(const Plan& P, int64_t p, bool to_msd, u64* zq, u64* zp) {
+  if (!p_ok(p)) return LOLHIP_ERR_MODULUS;
+  const u64 up = (u64)p;
+  const u64 negq = (up - q_mod(P, up)) % up;
+  for (int t = 0; t < P.T; ++t) {
+    const u64 q = P.qs[(size_t)t];
+    zq[t] = to_msd ? invmod(up % q, q) : up % q;
+    if (to_msd && zq[t] == 0) return LOLHIP_ERR_MODULUS;
+  }
+  *zp = to_msd ? negq : invmod(negq, up);
+  if (!to_msd && *zp == 0) return LOLHIP_ERR_MODULUS;
+  return LOLHIP_OK;
+}
+
+// the ciphertext scalar after the conversion whose factor is zp: l' = l zp mod p (zp = 1: l mod p)
+inline u64 encode_l(int64_t l, u64 zp, u64 p) { return mulmod(canon(l, p), zp, p); }
+
+}  // namespace lolhip

@@ -623,6 +623,26 @@ class Plan:
         out = tuple(t.cpu().numpy() if host else t for t in tensors)
         return out if len(out) > 1 else out[0]
 
+    @staticmethod
+    def _run_staged(call, stream, inputs, B, work_len, out_shape, out=None):
+        """The protocol of the batched SymmSHE entries.  call(stream, ptrs, out, work, B) wraps one C entry: first a dry
+        run at B = 0 with null pointers, so every host status is raised before anything touches the device; then numpy
+        inputs (inputs[0] decides) are staged, the work buffer (work_len() words, at least one) and the output
+        (out_shape(), unless `out` is given) allocated, the real call made and the output unstaged."""
+        import torch
+        _check(call(None, [None] * len(inputs), None, None, 0))
+        host = isinstance(inputs[0], np.ndarray)
+        if host:
+            _, inputs = Plan._stage(*inputs)
+        dev = inputs[0].device
+        wl = work_len()
+        _check(min(wl, 0))
+        work = torch.empty((max(wl, 1),), dtype=torch.int64, device=dev)
+        if out is None:
+            out = torch.empty(out_shape(), dtype=torch.int64, device=dev)
+        _check(call(_stream(stream), [_devptr(t) for t in inputs], _devptr(out), _devptr(work), B))
+        return Plan._unstage(host, out)
+
     def ctMulCRT(self, c0, c1, d0, d1, stream=None):
         """(g c0 d0, g (c0 d1 + c1 d0), g c1 d1): mulG <$> c*d for two linear ciphertexts, every
         operand in the CRT basis (SymmSHE.hs:444-449)."""
@@ -686,21 +706,6 @@ class Plan:
         return self._unstage(host, out)
 
     # ---- errorTerm / decrypt (lol-apps SymmSHE.hs:153-178) ------------------------------
-    def _ct_args(self, cs, s_crt):
-        """(host?, stacked cs [ncs][B][n][T] and s_crt [n][T] as device tensors, ncs, B); numpy stays on the host side
-        until _stage, so the host checks of the library run first"""
-        import torch
-        if isinstance(cs, (list, tuple)):
-            host = isinstance(cs[0], np.ndarray)
-            cs = np.stack([np.asarray(c, dtype=np.int64) for c in cs]) if host else torch.stack(list(cs))
-        else:
-            host = isinstance(cs, np.ndarray)
-        ncs = int(cs.shape[0])
-        B = (cs.size if host else cs.numel()) // max(ncs * self.n * self.T, 1)
-        if ncs * B * self.n * self.T != (cs.size if host else cs.numel()):
-            raise ValueError("cs is not [ncs][B][n][T]")
-        return host, cs, s_crt, ncs, B
-
     @staticmethod
     def _enc(enc):
         return {"LSD": 0, "MSD": 1, 0: 0, 1: 1}[enc]
@@ -709,35 +714,25 @@ class Plan:
         """liftCyc Dec (evaluate c s) after toLSD (SymmSHE.hs:153-157): ciphertext components cs (a list of [B][n][T]
         or one [ncs][B][n][T] array; powerful basis, or CRT basis with cs_crt), secret key s_crt [n][T] in the CRT
         basis -> [B][n] int64 centred lifts mod Q (INT64_MIN where the lift does not fit)."""
-        import torch
         L = lib()
-        host, cs, s_crt, ncs, B = self._ct_args(cs, s_crt)
+        _, cs, ncs, B = self._cs(cs)
         e = self._enc(enc)
-        _check(L.lolhip_error_term_batch(self._h, None, None, ncs, int(cs_crt), None, e, int(p), None, None, 0))
-        host, (cs, s_crt) = self._stage(cs, s_crt) if host else (False, (cs, s_crt))
-        work = torch.empty((max(L.lolhip_decrypt_work_len(self._h, ncs, B), 1),), dtype=torch.int64, device=cs.device)
-        out = torch.empty((B, self.n), dtype=torch.int64, device=cs.device)
-        _check(L.lolhip_error_term_batch(self._h, _stream(stream), _devptr(cs), ncs, int(cs_crt), _devptr(s_crt), e, int(p),
-                                         _devptr(out), _devptr(work), B))
-        return self._unstage(host, out)
+        return self._run_staged(
+            lambda st, i, o, w, b: L.lolhip_error_term_batch(self._h, st, i[0], ncs, int(cs_crt), i[1], e, int(p), o, w, b),
+            stream, (cs, s_crt), B, lambda: L.lolhip_decrypt_work_len(self._h, ncs, B), lambda: (B, self.n))
 
     def decrypt(self, cs, s_crt, pp, ext=None, enc="LSD", k=0, l=1, cs_crt=False, stream=None):
         """SymmSHE decrypt (SymmSHE.hs:169-174): l' twace (divG^k (reduce_p (errorTerm))).  pp: the Plan of index m' over
         the plaintext modulus p alone; ext: an Ext from the Plan of (m, p) to pp, or None for m = m'.  Returns [B][n_m]
         residues mod p in the powerful basis of R_m."""
-        import torch
         L = lib()
-        host, cs, s_crt, ncs, B = self._ct_args(cs, s_crt)
+        _, cs, ncs, B = self._cs(cs)
         e, xh = self._enc(enc), (None if ext is None else ext._h)
-        args = (int(k), int(l))
-        _check(L.lolhip_decrypt_batch(self._h, pp._h, xh, None, None, ncs, int(cs_crt), None, e, *args, None, None, 0))
-        host, (cs, s_crt) = self._stage(cs, s_crt) if host else (False, (cs, s_crt))
         n_out = pp.n if ext is None else ext.lo.n
-        work = torch.empty((max(L.lolhip_decrypt_work_len(self._h, ncs, B), 1),), dtype=torch.int64, device=cs.device)
-        out = torch.empty((B, n_out), dtype=torch.int64, device=cs.device)
-        _check(L.lolhip_decrypt_batch(self._h, pp._h, xh, _stream(stream), _devptr(cs), ncs, int(cs_crt), _devptr(s_crt), e,
-                                      *args, _devptr(out), _devptr(work), B))
-        return self._unstage(host, out)
+        return self._run_staged(
+            lambda st, i, o, w, b: L.lolhip_decrypt_batch(self._h, pp._h, xh, st, i[0], ncs, int(cs_crt), i[1], e, int(k),
+                                                           int(l), o, w, b),
+            stream, (cs, s_crt), B, lambda: L.lolhip_decrypt_work_len(self._h, ncs, B), lambda: (B, n_out))
 
     # ---- encrypt / genSK (lol-apps SymmSHE.hs:120-146) -------------------------------------
     @staticmethod
@@ -753,23 +748,17 @@ class Plan:
         out_crt.  pp: the Plan of index m' over p alone; ext: an Ext from the Plan of (m, p) to pp, or None for m = m'.
         Samples from the ChaCha20 stream of (key, ctr + b) (include/lolhip.h); key None draws a fresh one.  Never reuse
         (key, ctr + b): advance ctr by B between calls."""
-        import torch
         L = lib()
         kb, xh = self._key(key), (None if ext is None else ext._h)
-        host = isinstance(pt, np.ndarray)
         n_m = pp.n if ext is None else ext.lo.n
-        size = pt.size if host else pt.numel()
+        size = pt.size if isinstance(pt, np.ndarray) else pt.numel()
         B = size // max(n_m, 1)
         if B * n_m != size:
             raise ValueError("pt is not [B][n_m]")
-        _check(L.lolhip_encrypt_batch(self._h, pp._h, xh, None, None, None, float(svar), kb, int(ctr), int(out_crt), None,
-                                      None, 0))
-        host, (pt, s_crt) = self._stage(pt, s_crt) if host else (False, (pt, s_crt))
-        work = torch.empty((max(L.lolhip_encrypt_work_len(self._h, B), 1),), dtype=torch.int64, device=pt.device)
-        out = torch.empty((2, B, self.n, self.T), dtype=torch.int64, device=pt.device)
-        _check(L.lolhip_encrypt_batch(self._h, pp._h, xh, _stream(stream), _devptr(pt), _devptr(s_crt), float(svar), kb,
-                                      int(ctr), int(out_crt), _devptr(out), _devptr(work), B))
-        return self._unstage(host, out)
+        return self._run_staged(
+            lambda st, i, o, w, b: L.lolhip_encrypt_batch(self._h, pp._h, xh, st, i[0], i[1], float(svar), kb, int(ctr),
+                                                           int(out_crt), o, w, b),
+            stream, (pt, s_crt), B, lambda: L.lolhip_encrypt_work_len(self._h, B), lambda: (2, B, self.n, self.T))
 
     def errorRounded(self, svar, B=1, key=None, ctr=0, stream=None):
         """errorRounded svar (UCyc.hs:422-429; genSK, SymmSHE.hs:120-122): [B][n] int64 decoding-basis coefficients,
@@ -788,24 +777,18 @@ class Plan:
         (CRT basis) -> [B][L][2][n][T] CRT-basis hints; [b] is the hint keySwitch takes.  Row j of item b is LWE sample
         ctr + b L + j of the ChaCha20 stream (include/lolhip.h): advance ctr by B L between calls; key None draws a
         fresh key."""
-        import torch
         L = lib()
         kb = self._key(key)
-        host = isinstance(vals_crt, np.ndarray)
-        size = vals_crt.size if host else vals_crt.numel()
+        size = vals_crt.size if isinstance(vals_crt, np.ndarray) else vals_crt.numel()
         per = self.n * self.T
         B = size // per
         if B * per != size:
             raise ValueError("vals_crt is not [B][n][T]")
-        _check(L.lolhip_kshint_batch(self._h, None, None, None, float(svar), int(base), kb, int(ctr), None, None, 0))
-        host, (vals_crt, s_crt) = self._stage(vals_crt, s_crt) if host else (False, (vals_crt, s_crt))
-        nL = self.decomposeLen(base)
-        work = torch.empty((max(L.lolhip_kshint_work_len(self._h, int(base), B), 1),), dtype=torch.int64,
-                           device=vals_crt.device)
-        out = torch.empty((B, nL, 2, self.n, self.T), dtype=torch.int64, device=vals_crt.device)
-        _check(L.lolhip_kshint_batch(self._h, _stream(stream), _devptr(s_crt), _devptr(vals_crt), float(svar), int(base),
-                                     kb, int(ctr), _devptr(out), _devptr(work), B))
-        return self._unstage(host, out)
+        return self._run_staged(
+            lambda st, i, o, w, b: L.lolhip_kshint_batch(self._h, st, i[1], i[0], float(svar), int(base), kb, int(ctr),
+                                                          o, w, b),
+            stream, (vals_crt, s_crt), B, lambda: L.lolhip_kshint_work_len(self._h, int(base), B),
+            lambda: (B, self.decomposeLen(base), 2, self.n, self.T))
 
     def ksLinearHint(self, s_out_crt, s_in_crt, svar, base, key=None, ctr=0, stream=None):
         """ksLinearHint skout skin (SymmSHE.hs:330-335) = ksHint skout s_in: one [L][2][n][T] hint."""
@@ -948,42 +931,32 @@ class Plan:
         (or one [n_m] for the whole batch) in the powerful basis of R_m, any int64; ext: an Ext from the Plan of (m, qs)
         to this one, or None for m = m'; pp_m: the Plan of index m over p alone (k > 0).  cs_shared: one ciphertext
         ([ncs][1][n][T]) for all B items."""
-        import torch
-        host, cs, ncs, Bc = self._cs(cs)
+        _, cs, ncs, Bc = self._cs(cs)
         B = Bc if B is None else int(B)
         n_m = self.n if ext is None else ext.lo.n
         b, stride = self._public(b, n_m, B, stride)
         L, xh, pph = lib(), (None if ext is None else ext._h), (None if pp_m is None else pp_m._h)
         lo = C.c_int64(0)
         args = (int(cs_shared), int(cs_crt), self._enc(enc), int(k), int(l), int(p))
-        _check(L.lolhip_add_public_batch(self._h, xh, pph, None, None, stride, None, ncs, *args, None, C.byref(lo), None, 0))
-        if host:
-            _, (b, cs) = self._stage(np.ascontiguousarray(b, dtype=np.int64), cs)
-        work = torch.empty((max(L.lolhip_public_work_len(self._h, xh, B), 1),), dtype=torch.int64, device=cs.device)
-        out = torch.empty((ncs, B, self.n, self.T), dtype=torch.int64, device=cs.device)
-        _check(L.lolhip_add_public_batch(self._h, xh, pph, _stream(stream), _devptr(b), stride, _devptr(cs), ncs, *args,
-                                         _devptr(out), C.byref(lo), _devptr(work), B))
-        return self._unstage(host, out), "LSD", int(lo.value)
+        out = self._run_staged(
+            lambda st, i, o, w, nb: L.lolhip_add_public_batch(self._h, xh, pph, st, i[1], stride, i[0], ncs, *args, o,
+                                                               C.byref(lo), w, nb),
+            stream, (cs, b), B, lambda: L.lolhip_public_work_len(self._h, xh, B), lambda: (ncs, B, self.n, self.T))
+        return out, "LSD", int(lo.value)
 
     def mulPublic(self, a, cs, p, ext=None, cs_shared=False, stride=None, B=None, out=None, stream=None):
         """mulPublic a (SymmSHE.hs:405-411): every c_i times embed (reduce (decode' a)), cs and the result in the CRT
         basis; enc, k and l do not change.  a [B][n_m] (or one [n_m]), any int64, powerful basis of R_m; stride: the
         item stride of a (e.g. L n for KHPRF.eval's [B][L][n]); out may be cs unless cs is shared and B > 1."""
-        import torch
-        host, cs, ncs, Bc = self._cs(cs)
+        _, cs, ncs, Bc = self._cs(cs)
         B = Bc if B is None else int(B)
         n_m = self.n if ext is None else ext.lo.n
         a, stride = self._public(a, n_m, B, stride)
         L, xh = lib(), (None if ext is None else ext._h)
-        _check(L.lolhip_mul_public_batch(self._h, xh, None, None, stride, int(p), None, ncs, int(cs_shared), None, None, 0))
-        if host:
-            _, (a, cs) = self._stage(np.ascontiguousarray(a, dtype=np.int64), cs)
-        work = torch.empty((max(L.lolhip_public_work_len(self._h, xh, B), 1),), dtype=torch.int64, device=cs.device)
-        if out is None:
-            out = torch.empty((ncs, B, self.n, self.T), dtype=torch.int64, device=cs.device)
-        _check(L.lolhip_mul_public_batch(self._h, xh, _stream(stream), _devptr(a), stride, int(p), _devptr(cs), ncs,
-                                         int(cs_shared), _devptr(out), _devptr(work), B))
-        return self._unstage(host, out)
+        return self._run_staged(
+            lambda st, i, o, w, b: L.lolhip_mul_public_batch(self._h, xh, st, i[1], stride, int(p), i[0], ncs,
+                                                              int(cs_shared), o, w, b),
+            stream, (cs, a), B, lambda: L.lolhip_public_work_len(self._h, xh, B), lambda: (ncs, B, self.n, self.T), out=out)
 
     def modSwitchPT(self, cs, p, p2, enc="LSD", l=1, stream=None):
         """modSwitchPT from p to p2 | p (SymmSHE.hs:255-261): toMSD, then l' = decode'_p(l) mod p2 -> (cs, "MSD", l')"""
@@ -997,19 +970,14 @@ class Plan:
         are a suffix of these (up to 5 dropped), of which these are a suffix (up to 5 added), or the same (toMSD):
         lolhip_modswitch_batch, one pass for the encoding scale and the whole rescale.  cs [ncs][B][n][T] in the powerful
         basis (or the CRT basis with cs_crt) -> (out [ncs][B][n][T'] in the basis out_crt asks for, "MSD", l')."""
-        import torch
-        host, cs, ncs, B = self._cs(cs)
+        _, cs, ncs, B = self._cs(cs)
         L, lo = lib(), C.c_int64(0)
         args = (ncs, int(cs_crt), self._enc(enc), int(l), int(p))
-        _check(L.lolhip_modswitch_batch(self._h, to._h, None, None, *args, None, int(out_crt), C.byref(lo), None, 0))
-        host, (cs,) = self._stage(cs) if host else (False, (cs,))
-        wl = L.lolhip_modswitch_work_len(self._h, to._h, ncs, B)
-        _check(min(wl, 0))
-        work = torch.empty((max(wl, 1),), dtype=torch.int64, device=cs.device)
-        out = torch.empty((ncs, B, to.n, to.T), dtype=torch.int64, device=cs.device)
-        _check(L.lolhip_modswitch_batch(self._h, to._h, _stream(stream), _devptr(cs), *args, _devptr(out), int(out_crt),
-                                        C.byref(lo), _devptr(work), B))
-        return self._unstage(host, out), "MSD", int(lo.value)
+        out = self._run_staged(
+            lambda st, i, o, w, b: L.lolhip_modswitch_batch(self._h, to._h, st, i[0], *args, o, int(out_crt),
+                                                             C.byref(lo), w, b),
+            stream, (cs,), B, lambda: L.lolhip_modswitch_work_len(self._h, to._h, ncs, B), lambda: (ncs, B, to.n, to.T))
+        return out, "MSD", int(lo.value)
 
     def absorbGFactors(self, cs, k, pp, stream=None):
         """absorbGFactors (SymmSHE.hs:464-473) of a CRT-basis ciphertext: every c_i times decode'(divG^k 1), divG over
@@ -1183,19 +1151,15 @@ class TunnelChain:
     def __call__(self, cs, p, enc="LSD", l=1, cs_crt=False, out_crt=False, stream=None):
         """cs [2][B][n_R'][T_in], a linear ciphertext with k = 0 (Plan.absorbGFactors first otherwise), powerful basis or
         CRT basis (cs_crt) -> (out [2][B][n_S'][T_out], "MSD", l')."""
-        import torch
-        host, cs, ncs, B = self.p_in._cs(cs)
+        _, cs, ncs, B = self.p_in._cs(cs)
         if ncs != 2:
             raise LolHipError(ERR_INVALID, "tunnelH takes a linear ciphertext")
         L, lo = lib(), C.c_int64(0)
         args = (int(cs_crt), Plan._enc(enc), int(l), int(p))
-        _check(L.lolhip_tunnel_chain_batch(self._h, None, None, *args, None, int(out_crt), C.byref(lo), None, 0))
-        host, (cs,) = Plan._stage(cs) if host else (False, (cs,))
-        work = torch.empty((max(self.workLen(B), 1),), dtype=torch.int64, device=cs.device)
-        out = torch.empty((2, B, self.p_out.n, self.p_out.T), dtype=torch.int64, device=cs.device)
-        _check(L.lolhip_tunnel_chain_batch(self._h, _stream(stream), _devptr(cs), *args, _devptr(out), int(out_crt),
-                                           C.byref(lo), _devptr(work), B))
-        return Plan._unstage(host, out), "MSD", int(lo.value)
+        out = Plan._run_staged(
+            lambda st, i, o, w, b: L.lolhip_tunnel_chain_batch(self._h, st, i[0], *args, o, int(out_crt), C.byref(lo), w, b),
+            stream, (cs,), B, lambda: self.workLen(B), lambda: (2, B, self.p_out.n, self.p_out.T))
+        return out, "MSD", int(lo.value)
 
     @staticmethod
     def hints(exts_er, exts_es, exts_f, funcs, s_in_crt, p, svar, base, key=None, ctr=0, stream=None):
