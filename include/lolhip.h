@@ -113,7 +113,11 @@ LOLHIP_API int lolhip_plan_has_crt(const lolhip_plan *p);
  *          3 gCRT  4 gInvCRT (CPP.hs:444-454; [n*T] AoS)            5 qs
  *          10 / 11 (inspection, tests): the stage program a lone crt / crtInv of an index that is not a power
  *          of two launches, four values per stage: kind, prime (first level for the 2-power tiles), vector
- *          length (levels for the tiles), stride
+ *          length (levels for the tiles), stride.  The choice is the launch's own, current A/B switches included: the
+ *          one-launch program with 2-power tiles where the vector interpreter takes it, the odd primes' program
+ *          where the 2-power factor goes through the m = 2^k kernels, the whole stage program otherwise
+ *          13 / 14 (inspection, tests): the forward / inverse program of a poly-mul that runs as one launch of the
+ *          vector interpreter, same four values per stage; empty when the poly-mul is composed of lone transforms
  *          12 (inspection, tests): the lift constants of errorTerm / decrypt, [T + T*T + T]: (q_0 ... q_{i-1})^-1
  *          mod q_i (1 for i = 0); q_j mod q_i at [T + i*T + j]; the mixed-radix digits of floor((Q-1)/2),
  *          Q = prod q_t, least significant first                                  */

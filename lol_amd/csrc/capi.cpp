@@ -175,27 +175,58 @@ int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, i
   return hip_status(launch_generic(a));
 }
 
-// crt / crtInv of B polynomials through whichever path the plan has: the m = 2^k kernels,
-// the 2-power factor through them and the odd primes through the stage program, or the
-// stage program alone
-int do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse) {
-  if (P.is_pow2) return run_pow2(P, inverse ? 1 : 0, s, y, nullptr, nullptr, B);
-  // a lone transform of m = 2^e * odd: one launch of the interpreter, except with 64-bit residues and
-  // e >= 5, where the m = 2^k kernels' cheaper butterflies outweigh the second pass over the slab
-  // (measured at 58 bits: m = 11648 0.62 vs 0.55 ms, m = 14336 0.65 vs 0.52 ms; with the even/odd form of round 3 0.54 vs 0.48 and
-  // 0.62 vs 0.50, m = 14400 0.457 vs 0.448; at 26 bits fused wins everywhere)
+// How a lone crt / crtInv of the plan runs.  ONE choice for do_crt and for lolhip_plan_table 10 / 11, so the table
+// cannot report a program that is never launched:
+//   POW2    the m = 2^k kernels;
+//   FUSED2  m = 2^e * odd in one launch of the vector interpreter (2-power tiles + the odd primes' stages), except with
+//           64-bit residues and e >= 5, where the m = 2^k kernels' cheaper butterflies outweigh the second pass over
+//           the slab (measured at 58 bits: m = 11648 0.62 vs 0.55 ms, m = 14336 0.65 vs 0.52 ms; with the even/odd
+//           form of round 3 0.54 vs 0.48 and 0.62 vs 0.50, m = 14400 0.457 vs 0.448; at 26 bits fused wins everywhere);
+//   SPLIT   the 2-power factor through the m = 2^k kernels, the odd primes through prog_crt(inv)_odd;
+//   STAGES  the stage program alone (zq_crt / zq_crtinv).
+// The 2-power tiles exist in the vector interpreter only: a plan it refuses (mixed_ok) never takes FUSED2.
+enum CrtRoute { ROUTE_POW2, ROUTE_FUSED2, ROUTE_SPLIT, ROUTE_STAGES };
+CrtRoute crt_route(const Plan& P) {
+  if (P.is_pow2) return ROUTE_POW2;
   const bool wide = P.mixed_cls == 0 || P.mixed_cls == 3;
-  if (use_fused2(P) && !(wide && P.pow2_part)) return run_prog(P, inverse ? fused_crtinv(P) : fused_crt(P), s, y, B);
-  if (P.pow2_part && !sw(SW_NO_POW2_PART)) {
-    const int64_t blocks = B * (P.n >> P.pow2.L);       // contiguous 2^(e-1)-coefficient blocks
-    if (!inverse) {
-      int rc = run_pow2(P, 0, s, y, nullptr, nullptr, blocks);
-      return rc ? rc : run_prog(P, P.prog_crt_odd, s, y, B);
-    }
-    int rc = run_prog(P, P.prog_crtinv_odd, s, y, B);
-    return rc ? rc : run_pow2(P, 1, s, y, nullptr, nullptr, blocks);
+  if (use_fused2(P) && !(wide && P.pow2_part)) return ROUTE_FUSED2;
+  if (P.pow2_part && !sw(SW_NO_POW2_PART)) return ROUTE_SPLIT;
+  return ROUTE_STAGES;
+}
+// the stage program of that route (POW2 launches none: the staged list, for inspection)
+const StageProgram& crt_route_prog(const Plan& P, CrtRoute r, bool inverse) {
+  switch (r) {
+    case ROUTE_FUSED2: return inverse ? fused_crtinv(P) : fused_crt(P);
+    case ROUTE_SPLIT: return inverse ? P.prog_crtinv_odd : P.prog_crt_odd;
+    default: return inverse ? zq_crtinv(P) : zq_crt(P);
   }
-  return run_prog(P, inverse ? zq_crtinv(P) : zq_crt(P), s, y, B);
+}
+// poly-mul as ONE launch of the vector interpreter (a-hat in registers, b through the same LDS buffer); otherwise it is
+// composed from lone transforms
+bool polymul_one_launch(const Plan& P) {
+  if (P.is_pow2 || sw(SW_POLYMUL_UNFUSED)) return false;
+  const bool fused2 = use_fused2(P);
+  const bool split2 = !fused2 && P.pow2_part && !sw(SW_NO_POW2_PART);   // the 2-power factor has its own kernels
+  return !split2 && (fused2 || (use_mixed(P, zq_crt(P)) && use_mixed(P, zq_crtinv(P))));
+}
+
+// crt / crtInv of B polynomials through whichever path the plan has (crt_route)
+int do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse) {
+  const CrtRoute r = crt_route(P);
+  const StageProgram& sp = crt_route_prog(P, r, inverse);
+  switch (r) {
+    case ROUTE_POW2: return run_pow2(P, inverse ? 1 : 0, s, y, nullptr, nullptr, B);
+    case ROUTE_SPLIT: {
+      const int64_t blocks = B * (P.n >> P.pow2.L);       // contiguous 2^(e-1)-coefficient blocks
+      if (!inverse) {
+        int rc = run_pow2(P, 0, s, y, nullptr, nullptr, blocks);
+        return rc ? rc : run_prog(P, sp, s, y, B);
+      }
+      int rc = run_prog(P, sp, s, y, B);
+      return rc ? rc : run_pow2(P, 1, s, y, nullptr, nullptr, blocks);
+    }
+    default: return run_prog(P, sp, s, y, B);
+  }
 }
 
 int divg_ok(const Plan& P) {
@@ -281,10 +312,13 @@ int64_t lolhip_plan_table(const lolhip_plan* p, int which, int k, int64_t* out, 
     case 3: src = &P.gcrt; break;
     case 4: if (P.has_ginvcrt) src = &P.ginvcrt; break;
     case 5: for (u64 q : P.qs) tmp.push_back((i64)q); src = &tmp; break;
-    case 10: case 11: {      // the stage program a lone crt (10) / crtInv (11) launches, four values per stage
-      const bool inv = which == 11;
-      const StageProgram& sp = (P.fused2 && !sw(SW_NO_FUSED2)) ? (inv ? fused_crtinv(P) : fused_crt(P)) : (inv ? zq_crtinv(P) : zq_crt(P));
-      for (const Stage& st : sp.stages) { tmp.push_back(st.kind); tmp.push_back(st.p); tmp.push_back(st.d); tmp.push_back(st.rts); }
+    case 10: case 11:        // the stage program a lone crt (10) / crtInv (11) launches (do_crt's own choice), four values per stage
+    case 13: case 14: {      // the forward (13) / inverse (14) program of the one-launch poly-mul; empty when it is composed of lone transforms
+      const bool inv = which == 11 || which == 14;
+      const StageProgram* sp = nullptr;
+      if (which <= 11) sp = &crt_route_prog(P, crt_route(P), inv);
+      else if (polymul_one_launch(P)) sp = use_fused2(P) ? (inv ? &fused_crtinv(P) : &fused_crt(P)) : (inv ? &zq_crtinv(P) : &zq_crt(P));
+      if (sp) for (const Stage& st : sp->stages) { tmp.push_back(st.kind); tmp.push_back(st.p); tmp.push_back(st.d); tmp.push_back(st.rts); }
       src = &tmp;
       break;
     }
@@ -333,10 +367,8 @@ int lolhip_polymul_batch(const lolhip_plan* p, void* stream, int64_t* c, const i
   const Plan& P = p->P;
   hipStream_t s = (hipStream_t)stream;
   if (P.is_pow2) return run_pow2(P, 2, s, c, a, b, B);
-  const bool unfused = sw(SW_POLYMUL_UNFUSED);                                      // A/B switch
   const bool fused2 = use_fused2(P);
-  const bool split2 = !fused2 && P.pow2_part && !sw(SW_NO_POW2_PART);   // the 2-power factor has its own kernels
-  if (!unfused && !split2 && (fused2 || (use_mixed(P, zq_crt(P)) && use_mixed(P, zq_crtinv(P))))) {
+  if (polymul_one_launch(P)) {
     // one launch: a-hat in registers, b through the same LDS buffer, 3 slab passes (mixed.hip)
     const StageProgram& pf = fused2 ? fused_crt(P) : zq_crt(P);
     const StageProgram& pi = fused2 ? fused_crtinv(P) : zq_crtinv(P);

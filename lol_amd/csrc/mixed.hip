@@ -33,7 +33,14 @@ bool mixed_ok(i64 n, const Stage* host_stages, int nstages, const u64* qs, int T
     const Stage& st = host_stages[s];
     if (st.kind == ST_DIAG || st.kind == ST_SCALE) continue;
     if (st.kind == ST_POW2F || st.kind == ST_POW2I) { if (st.d < 1 || st.d > 4) return false; continue; }
+    // a prime >= 17 goes to the scalar interpreter whatever its length: 19 has the 18 of the merged 3^3, whose vector
+    // code (mixed_impl.h stage_vec_big) is a dense matrix without a diagonal in classes 2 / 4 and nothing else
+    if (st.p > 13) return false;
     const int d = st.d;
+    // stage_vec_big applies no diagonal.  No index produces a merged 18- or 20-vector with one today: merge_stages only
+    // reaches these lengths with a WHOLE prime power (3^3, 5^2), whose last diagonal lies inside the merged block, and a
+    // constant folds into the matrix; its `carry` case arises for the DFT_9 tail of 3^e, e >= 4, a 9-vector (stage_vec)
+    if ((d == 18 || d == 20) && st.tw_off >= 0) return false;
     if (!(d == 2 || d == 3 || d == 4 || d == 5 || d == 6 || d == 7 || d == 8 || d == 9 || d == 10 || d == 11 || d == 12 || d == 13 || d == 18 || d == 20)) return false;      // 18, 20: merged prime powers, class 2 / 4 plans only (plan.cpp)
   }
   return true;

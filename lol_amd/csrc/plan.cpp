@@ -202,8 +202,10 @@ static void build_crt_programs(const std::vector<PP>& pps, const Ring& R, PoolBu
 // phi(p^e) x phi(p^e) matrix over Z_q — the same linear map, so the same residues bit for bit — and
 // phi <= 20 fits one register vector: 20 multiply-adds and ONE reduction per coefficient instead of
 // (4 + 5) multiply-adds, two diagonal products and three reductions.  Built by pushing the unit vectors
-// through the staged form on the host; the merged stage replaces the run in a COPY of the program
-// (the floating-point path and the scalar interpreter keep the staged list).
+// through the staged form on the host; the merged stage replaces the run in a COPY of the program: the
+// floating-point path keeps the staged list, and so does GENERIC_SCALAR.  A merged plan that the vector interpreter
+// refuses all the same (a prime >= 17 beside the merged factor: m = 153, 459, 425, 255) launches the MERGED copy on
+// the scalar interpreter (capi.cpp zq_crt), whose dense-row loop takes any length.
 // KRON: the second pass — two ADJACENT tensor factors that are one dense stage each (after the first pass: a prime or a
 // merged prime power) and whose Kronecker product is a vector length the kernels hold: 3 (x) 5 as ONE 8-vector stage
 // (m = 15015: five round trips become four), 3 (x) 7 as a 12-vector.  Same host construction, same residues.
@@ -643,6 +645,27 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
     P.prog_crt_odd.stages = crt_odd.st;
     P.prog_crtinv_odd.stages = crtinv_odd.st;
   }
+  // class of the vector interpreter (mixed.hip); a function of the moduli alone, so host-only plans have it too
+  // (the choice of a lone transform's route reads it: capi.cpp crt_route):
+  //   2: every q odd with 13 (q-1)^2 < 2^64: 32-bit residues, one 64-bit accumulator per dot
+  //      product, constants pre-scaled by 2^32, one 32-bit Montgomery reduction per output;
+  //   1: every q < 2^32 otherwise (128-bit accumulators, exact division step);
+  //   3: 64-bit residues, every q odd and below 2^61: constants pre-scaled by 2^64, one 64-bit
+  //      Montgomery reduction per output;   0: anything else (exact two-step division).
+  bool fits32 = true, acc64 = true, odd = true, below61 = true;
+  for (u64 q : P.qs) {
+    if (q >= ((u64)1 << 32)) fits32 = false;
+    if ((unsigned __int128)13 * (q - 1) * (q - 1) >= ((unsigned __int128)1 << 64)) acc64 = false;
+    if (!(q & 1)) odd = false;
+    if (q >= ((u64)1 << 61)) below61 = false;
+  }
+  P.mixed_cls = fits32 ? ((acc64 && odd) ? 2 : 1) : ((odd && below61) ? 3 : 0);
+  //   4: class 2 with every q below 2^27: lazy dense stages (values in [0,2q) between them: a 3-instruction Montgomery step)
+  if (P.mixed_cls == 2 && !sw(SW_NO_LAZY)) {
+    bool below27 = true;
+    for (u64 q : P.qs) if (q >= ((u64)1 << 27)) below27 = false;
+    if (below27) P.mixed_cls = 4;
+  }
   return LOLHIP_OK;
 }
 
@@ -757,28 +780,6 @@ int plan_upload(Plan& P) {
   // polynomials too large for the LDS ping-pong run the generic path out of an HBM scratch ring
   // (allocated per call, stream-ordered: run_prog in capi.cpp)
   P.needs_scratch = 2 * (size_t)P.n * sizeof(u64) > 152 * 1024;
-  // class of the vector interpreter: 32-bit residues when every q < 2^32; a dot product of up to 13
-  // terms in ONE 64-bit accumulator when 13 (q-1)^2 < 2^64
-  // class of the vector interpreter (mixed.hip):
-  //   2: every q odd with 13 (q-1)^2 < 2^64: 32-bit residues, one 64-bit accumulator per dot
-  //      product, constants pre-scaled by 2^32, one 32-bit Montgomery reduction per output;
-  //   1: every q < 2^32 otherwise (128-bit accumulators, exact division step);
-  //   3: 64-bit residues, every q odd and below 2^61: constants pre-scaled by 2^64, one 64-bit
-  //      Montgomery reduction per output;   0: anything else (exact two-step division).
-  bool fits32 = true, acc64 = true, odd = true, below61 = true;
-  for (u64 q : P.qs) {
-    if (q >= ((u64)1 << 32)) fits32 = false;
-    if ((unsigned __int128)13 * (q - 1) * (q - 1) >= ((unsigned __int128)1 << 64)) acc64 = false;
-    if (!(q & 1)) odd = false;
-    if (q >= ((u64)1 << 61)) below61 = false;
-  }
-  P.mixed_cls = fits32 ? ((acc64 && odd) ? 2 : 1) : ((odd && below61) ? 3 : 0);
-  //   4: class 2 with every q below 2^27: lazy dense stages (values in [0,2q) between them: a 3-instruction Montgomery step)
-  if (P.mixed_cls == 2 && !sw(SW_NO_LAZY)) {
-    bool below27 = true;
-    for (u64 q : P.qs) if (q >= ((u64)1 << 27)) below27 = false;
-    if (below27) P.mixed_cls = 4;
-  }
   if (P.mixed_cls == 2 || P.mixed_cls == 4 || P.mixed_cls == 3) {
     const int sh = P.mixed_cls == 3 ? 64 : 32;
     std::vector<u64> mont(P.host_consts.size());

@@ -507,9 +507,11 @@ class Plan:
         t, T = self._table(12), self.T
         return {"pinv": t[:T], "qmod": t[T:T + T * T].reshape(T, T), "half": t[T + T * T:]}
 
-    def program(self, inverse=False):
-        """Stage program of a lone crt / crtInv (inspection): rows (kind, prime or first level, length or levels, stride)."""
-        return self._table(11 if inverse else 10).reshape(-1, 4)
+    def program(self, inverse=False, polymul=False):
+        """Stage program a lone crt / crtInv launches (inspection): rows (kind, prime or first level, length or levels,
+        stride).  polymul=True: the forward / inverse program of the one-launch poly-mul (no rows when poly-mul is composed
+        of lone transforms)."""
+        return self._table((13 if polymul else 10) + (1 if inverse else 0)).reshape(-1, 4)
 
     # ---- helpers ------------------------------------------------------------------
     def _batch(self, a):

@@ -148,18 +148,21 @@ def test_class2_plans_merge_small_prime_powers():
     reference's benchmark index 64*9*25 (Benchmarks/Default.hs:49-50) launches.  Kinds: 12/13 = 2-power tile
     forward/inverse, 1 = DFT_p, 2 = CRT_p, 3 = CRT_p^-1 (plan.h)."""
     import lol_amd
-    def prog(q, inverse=False, m=14400):
-        return [tuple(int(v) for v in r) for r in lol_amd.Plan(lm.factor_pps(m), [q], host_only=True).program(inverse)]
+    def prog(q, inverse=False, m=14400, polymul=False):
+        return [tuple(int(v) for v in r) for r in lol_amd.Plan(lm.factor_pps(m), [q], host_only=True).program(inverse, polymul)]
     q26, q30, q45 = (lm.first_good_q(14400, 2 ** b) for b in (26, 30, 45))
     assert prog(q26) == [(12, 1, 4, 1), (12, 5, 1, 16), (2, 3, 6, 32), (2, 5, 20, 192)]
     assert prog(q26, True) == [(3, 3, 6, 32), (3, 5, 20, 192), (13, 5, 1, 16), (13, 1, 4, 1)]      # tensor factors commute: same order of primes
     # 20 (q-1)^2 no longer fits 64 bits: 5^2 stays staged, 3^2 (6 terms) still merges
     assert prog(q30) == [(12, 1, 4, 1), (12, 5, 1, 16), (2, 3, 6, 32), (2, 5, 4, 192), (1, 5, 5, 768)]
-    # 64-bit residues: the staged form, four levels per tile
-    assert prog(q45) == [(12, 1, 4, 1), (12, 5, 1, 16), (2, 3, 2, 32), (1, 3, 3, 64), (2, 5, 4, 192), (1, 5, 5, 768)]
+    # 64-bit residues: the staged form, four levels per tile.  With e >= 5 that is the program of the one-launch poly-mul;
+    # a lone crt sends the 2-power factor through the m = 2^k kernels and launches the odd primes' stages alone
+    staged = [(12, 1, 4, 1), (12, 5, 1, 16), (2, 3, 2, 32), (1, 3, 3, 64), (2, 5, 4, 192), (1, 5, 5, 768)]
+    assert prog(q45, polymul=True) == staged and prog(q45) == staged[2:]
+    assert prog(q26, polymul=True) == prog(q26) and prog(q30, polymul=True) == prog(q30)
     lol_amd.debug_set("NO_MERGE", True)
     try:
-        assert prog(q26) == prog(q45)
+        assert prog(q26) == prog(q45, polymul=True) == staged
     finally:
         lol_amd.debug_set("NO_MERGE", False)
     # adjacent small factors as one Kronecker stage: 3 (x) 5 = an 8-vector (BASELINE config 4's index); not for 64-bit residues

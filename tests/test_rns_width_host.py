@@ -101,7 +101,9 @@ def test_decompose_len_refuses_17_moduli(lolhip):
 
 
 def _prog(lolhip, m, qs, inverse=False):
-    return [tuple(int(v) for v in r) for r in lolhip.Plan(lm.factor_pps(m), qs, host_only=True).program(inverse)]
+    """the program of the one-launch poly-mul, which both indices below have in every class (a lone crt of 14400 with
+    64-bit residues launches the odd primes' stages alone: test_scalar_interp_host.py)"""
+    return [tuple(int(v) for v in r) for r in lolhip.Plan(lm.factor_pps(m), qs, host_only=True).program(inverse, polymul=True)]
 
 
 def test_mixed_width_tuples_take_the_class_of_their_widest_modulus(lolhip):
