@@ -116,7 +116,8 @@ instance Tensor HT where
            , onGPU OpCRT c, onGPU OpCRTInv ci )
 
   tGaussianDec v = HT <$> tGaussianDec v       -- Double elements: CPU (GPU form: lolhip_gaussian_dec_batch, HIP.Batch)
-  gSqNormDec (HT x) = gSqNormDec x
+  gSqNormDec (HT x) = gSqNormDec x             -- single elements: CPU, wrapping in Int64 (GPU form: lolhip_gsqnorm_batch /
+                                               -- lolhip_gsqnorm_f64_batch over a slab, exact or saturated; HIP.Batch)
 
   twacePowDec = viaExt ExtTwacePowDec twacePowDec False
   embedPow    = viaExt ExtEmbedPow    embedPow    True

@@ -518,6 +518,68 @@ LOLHIP_API int lolhip_tunnel_chain_batch(const lolhip_tunnel_chain *c, void *str
                                          int64_t l, int64_t p, int64_t *out, int out_crt, int64_t *l_out, int64_t *work,
                                          int64_t B);
 
+/* --- gSqNormDec and RLWE / RLWR instances (lol RLWE/{Continuous,Discrete,RLWR}.hs; rlwe-challenges Generate.hs:192-218,
+ * Verify.hs:346-366), device pointers ------------------------------------------------------------------------------
+ * gSqNormDec (Tensor.hs:147-151; norm.cpp:15-75): e_dec [B][n] decoding-basis coefficients -> out [B],
+ *     out_b = <e_b, y_b>,  y = (I_{p^(e-1)} (x) (I+J)_{p-1}) e  applied along the prime dimension of every odd prime p of m
+ *   (the first prime power of the plan fastest-varying, tensor.h:40-80); sum e_j^2 for m = 2^k.  The plan supplies the
+ *   index only; any index with n <= 16384 (no limit on the primes).
+ *   lolhip_gsqnorm_batch: exact, or saturated: out = min(value, INT64_MAX), and INT64_MAX when a coefficient is INT64_MIN
+ *   (the unliftable marker of lolhip_error_term_batch).  The reference wraps in Int64 instead.
+ *   lolhip_gsqnorm_f64_batch: float64 under the tolerance contract above (relative 1e-12); the summation order is a
+ *   function of n alone: no atomics, the same bits run to run, for every B and however a batch is split.
+ * Samplers.  Three more domains of the ChaCha20 stream above, the item of sample b of a call being ctr + b: 5 = the
+ *   uniform a, 6 = the Gaussians, 7 = the uniform secret; bit layouts of Gaussians and uniform residues exactly those of
+ *   domains 0-2.  THE CALLER'S DUTY extends to them: never use one (key, ctr + b) twice for a domain; advance ctr by B
+ *   after a sample call, and draw each secret at a ctr of its own (domain 7 is disjoint from 5 and 6 at equal ctr).
+ *   kind: 0 = Discrete, 1 = Continuous, 2 = RLWR.
+ *   lolhip_rlwe_secret: s_crt [n][T] uniform, CRT basis, item ctr of domain 7.
+ *   lolhip_rlwe_sample_batch: a_crt [B][n][T] uniform, CRT basis, and
+ *     Disc: b_out int64 [B][n][T], CRT basis, b = a s + reduce e, e = errorRounded svar with the arithmetic of
+ *           lolhip_error_rounded_batch on domain 6 (Discrete.hs:38-45); any T <= 16.
+ *     Cont: b_out double [B][n], decoding basis of K/(qR), in [0, q) (Continuous.hs:45-54 over RRq.hs:47-84): with
+ *           x = (double) of the decoding-basis residue of a s in [0, q) and g = tGaussianDec svar (unrounded),
+ *           r = g - q floor(g / q);  z = x + r;  b = z >= q ? z - q : z, these IEEE double operations in this order (b is
+ *           a pure function of (x, g)).  T = 1.
+ *     RLWR: b_out int64 [B][n] in [0, p), decoding basis, = roundedProd s a below; svar is ignored; T = 1, 2 <= p < q.
+ *   p is read for RLWR only.  work: lolhip_rlwe_work_len(pq, kind, B) int64 of device scratch, which serves the sample
+ *   call and the error / rounding calls of that kind alike.
+ * lolhip_rlwe_error_batch (kind 0 or 1): the error term of B samples (a, b) under the purported secret s_crt and its
+ *   gSqNorm.  Disc (Discrete.hs:48-59): e int64 [B][n] = liftDec (b - a s), the centred mixed-radix lift of
+ *   lolhip_error_term_batch (INT64_MIN where it does not fit), norm int64 [B] as lolhip_gsqnorm_batch.  Cont
+ *   (Continuous.hs:57-68): with x as above, nx = (-x) - q floor((-x) / q);  z = b + nx;  y = z >= q ? z - q : z;
+ *   e = y + y < q ? y : y - q, doubles [B][n]; norm double [B] as lolhip_gsqnorm_f64_batch.  e_out or norm_out may be
+ *   NULL (not both): with e_out = NULL the error slab stays in work.  norm_out needs n <= 16384.
+ * lolhip_rlwr_rounded_prod_batch (RLWR.hs:34-44): per decoding-basis residue x of a s, l = 2x < q ? x : x - q,
+ *   b = floor((p l + floor(q/2)) / q) mod p in [0, p), floor division in exact 128-bit integers (the reference agrees
+ *   wherever its Int64 does not overflow).  lolhip_rlwr_check_batch: mismatch [B] int32 = the coefficients of sample b
+ *   where the given b differs from that value, counted on the device; a valid sample has 0.
+ * Limits: T <= 16; for Disc and Cont samples the sampler's index limits of lolhip_encrypt_batch.
+ * Status, decided in this order on the host before any launch (outputs are then not written): LOLHIP_ERR_INVALID for an
+ *   unknown kind, B < 0, T > 16, T != 1 where one modulus is required, p outside [2, q), svar <= 0 or not finite, an
+ *   index beyond the limits; LOLHIP_ERR_NO_CRT when pq has no CRT basis; LOLHIP_ERR_MODULUS for a Disc error term over
+ *   moduli that are not pairwise coprime; LOLHIP_ERR_NO_DEVICE on a host-only plan; LOLHIP_ERR_INVALID for NULL pointers
+ *   at B > 0.  No call synchronises or allocates; output does not depend on how a batch is split.
+ * lolhip_rlwe_error_bound (host; Continuous.hs:74-84, Discrete.hs:65-76): the bound the gSqNorm of an error of scaled
+ *   variance svar over the index pps stays below except with probability about eps.  kind 1: mhat n svar stabilize(1/2pi)
+ *   with x' = (1/2 + log(2 pi x)/2 - log(eps)/n)/pi iterated until x' - x < 0.0001; kind 0: ceiling(2^(odd primes of m) n
+ *   stabilize'(1/2pi) + the continuous bound), x' = (1/2 + log(2 pi x)/2 - log eps)/pi, a double holding an integer.
+ *   LOLHIP_ERR_INVALID for svar <= 0, eps outside (0, 1), non-finite inputs, a malformed prime-power list or kind. */
+LOLHIP_API int lolhip_gsqnorm_batch    (const lolhip_plan *p, void *stream, const int64_t *e_dec, int64_t *out, int64_t B);
+LOLHIP_API int lolhip_gsqnorm_f64_batch(const lolhip_plan *p, void *stream, const double *e_dec, double *out, int64_t B);
+LOLHIP_API int64_t lolhip_rlwe_work_len(const lolhip_plan *pq, int kind, int64_t B);
+LOLHIP_API int lolhip_rlwe_secret(const lolhip_plan *pq, void *stream, const uint8_t key[32], uint64_t ctr, int64_t *s_crt);
+LOLHIP_API int lolhip_rlwe_sample_batch(const lolhip_plan *pq, void *stream, int kind, int64_t p, const int64_t *s_crt,
+                                        double svar, const uint8_t key[32], uint64_t ctr, int64_t *a_crt, void *b_out,
+                                        int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwe_error_batch(const lolhip_plan *pq, void *stream, int kind, const int64_t *a_crt, const void *b,
+                                       const int64_t *s_crt, void *e_out, void *norm_out, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwr_rounded_prod_batch(const lolhip_plan *pq, int64_t p, void *stream, const int64_t *a_crt,
+                                              const int64_t *s_crt, int64_t *b_out, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwr_check_batch(const lolhip_plan *pq, int64_t p, void *stream, const int64_t *a_crt, const int64_t *b,
+                                       const int64_t *s_crt, int32_t *mismatch, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwe_error_bound(const lolhip_pp *pps, int npps, double svar, double eps, int kind, double *out);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

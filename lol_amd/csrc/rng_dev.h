@@ -21,8 +21,9 @@
 namespace lolhip {
 
 // 3 / 4: the Gaussians and c1 of key-switch hint rows (kshint.hip; item = LWE sample ctr + b L + j)
+// 5 / 6 / 7: the uniform a, the Gaussians and the uniform secret of RLWE / RLWR instances (rlwe.hip; item = ctr + b)
 enum { CHACHA_DOM_ENC_GAUSS = 0, CHACHA_DOM_UNIFORM = 1, CHACHA_DOM_ERR_ROUNDED = 2, CHACHA_DOM_HINT_GAUSS = 3,
-       CHACHA_DOM_HINT_UNIFORM = 4 };
+       CHACHA_DOM_HINT_UNIFORM = 4, CHACHA_DOM_RLWE_UNIFORM = 5, CHACHA_DOM_RLWE_GAUSS = 6, CHACHA_DOM_RLWE_SECRET = 7 };
 
 // the 256-bit key as eight little-endian words (passed to kernels by value)
 struct ChaChaKey { uint32_t k[8]; };

@@ -142,6 +142,16 @@ def lib():
     L.lolhip_tunnel_chain_work_len.argtypes = [vp, i64]
     L.lolhip_tunnel_chain_work_len.restype = i64
     L.lolhip_tunnel_chain_batch.argtypes = [vp, vp, vp, ci, ci, i64, i64, vp, ci, _i64p, vp, i64]
+    L.lolhip_gsqnorm_batch.argtypes = [vp, vp, vp, vp, i64]
+    L.lolhip_gsqnorm_f64_batch.argtypes = [vp, vp, vp, vp, i64]
+    L.lolhip_rlwe_work_len.argtypes = [vp, ci, i64]
+    L.lolhip_rlwe_work_len.restype = i64
+    L.lolhip_rlwe_secret.argtypes = [vp, vp, C.c_char_p, C.c_uint64, vp]
+    L.lolhip_rlwe_sample_batch.argtypes = [vp, vp, ci, i64, vp, C.c_double, C.c_char_p, C.c_uint64, vp, vp, vp, i64]
+    L.lolhip_rlwe_error_batch.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, i64]
+    L.lolhip_rlwr_rounded_prod_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64]
+    L.lolhip_rlwr_check_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64]
+    L.lolhip_rlwe_error_bound.argtypes = [pp, ci, C.c_double, C.c_double, ci, C.POINTER(C.c_double)]
     L.lolhip_chacha20_block.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.lolhip_chacha20_block.restype = None
     L.lolhip_ext_create.argtypes = [vp, vp, C.POINTER(vp)]
@@ -1333,3 +1343,202 @@ class KHPRF:
         _check(L.lolhip_khprf_batch(self._h, _stream(stream), _devptr(s), nkeys, int(p), int(x0), int(B), _devptr(out),
                                     _devptr(work)))
         return out[0] if single else out
+
+
+class RLWE:
+    """RLWE / RLWR instances over one plan (lol RLWE/{Continuous,Discrete,RLWR}.hs; rlwe-challenges Generate.hs:192-218,
+    Verify.hs:346-366): batched sampling against one secret, error terms, their gSqNorm and the validity checks.  Arrays
+    are numpy (staged through HBM, numpy out) or CUDA tensors (CUDA tensors out); samplers return CUDA tensors.  a and
+    the secret are in the CRT basis ([B][n][T], [n][T]); Disc b [B][n][T] in the CRT basis, Cont b float64 [B][n] and
+    RLWR b int64 [B][n] in the decoding basis.  Samples come from the ChaCha20 stream of (key, ctr + b), domains 5-7
+    (include/lolhip.h): never reuse (key, ctr + b); advance ctr by B between calls."""
+
+    DISC, CONT, RLWR = 0, 1, 2
+
+    def __init__(self, plan: Plan):
+        self.plan = plan
+
+    # ---- helpers ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _dev(x, dtype):
+        """a contiguous CUDA tensor of dtype from numpy or a CUDA tensor; (host?, tensor)"""
+        import torch
+        host = isinstance(x, np.ndarray)
+        if host:
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64 if dtype == torch.float64 else np.int64)).cuda()
+        if not (x.is_cuda and x.is_contiguous() and x.dtype == dtype):
+            raise TypeError(f"expected a contiguous {dtype} CUDA tensor")
+        return host, x
+
+    def _batch(self, a):
+        per = self.plan.n * self.plan.T
+        size = a.size if isinstance(a, np.ndarray) else a.numel()
+        if size % per:
+            raise ValueError(f"a is not a whole number of [n={self.plan.n}, T={self.plan.T}] polynomials")
+        return size // per
+
+    def _work(self, kind, B, device="cuda"):
+        import torch
+        wl = lib().lolhip_rlwe_work_len(self.plan._h, kind, int(B))
+        _check(min(wl, 0))
+        return torch.empty((max(wl, 1),), dtype=torch.int64, device=device)
+
+    # ---- gSqNormDec -------------------------------------------------------------------------------------------------
+    def gSqNorm(self, e, stream=None):
+        """gSqNormDec (Tensor.hs:147-151) of decoding-basis coefficients [B][n] -> [B]: int64 exact or saturated at
+        INT64_MAX (also for a coefficient INT64_MIN), float64 with a fixed summation order."""
+        import torch
+        L = lib()
+        isf = (e.dtype == np.float64) if isinstance(e, np.ndarray) else (e.dtype == torch.float64)
+        fn = L.lolhip_gsqnorm_f64_batch if isf else L.lolhip_gsqnorm_batch
+        _check(fn(self.plan._h, None, None, None, 0))
+        host, e = self._dev(e, torch.float64 if isf else torch.int64)
+        if e.numel() % self.plan.n:
+            raise ValueError("e is not [B][n]")
+        B = e.numel() // self.plan.n
+        out = torch.empty((B,), dtype=e.dtype, device=e.device)
+        _check(fn(self.plan._h, _stream(stream), e.data_ptr(), out.data_ptr(), B))
+        return out.cpu().numpy() if host else out
+
+    # ---- samplers ---------------------------------------------------------------------------------------------------
+    def secret(self, key=None, ctr=0, stream=None):
+        """a uniform secret [n][T] in the CRT basis (Generate.hs:192-218), item ctr of domain 7"""
+        import torch
+        L, P = lib(), self.plan
+        kb = Plan._key(key)
+        rc = L.lolhip_rlwe_secret(P._h, None, kb, int(ctr), None)      # the host statuses first (INVALID: the null output)
+        if rc != ERR_INVALID:
+            _check(rc)
+        s = torch.empty((P.n, P.T), dtype=torch.int64, device="cuda")
+        _check(L.lolhip_rlwe_secret(P._h, _stream(stream), kb, int(ctr), s.data_ptr()))
+        return s
+
+    def _sample(self, kind, s_crt, B, svar, p, key, ctr, stream):
+        import torch
+        L, P = lib(), self.plan
+        kb = Plan._key(key)
+        call = lambda st, sp, a, b, w, nb: L.lolhip_rlwe_sample_batch(P._h, st, kind, int(p), sp, float(svar), kb, int(ctr),
+                                                                      a, b, w, nb)
+        _check(call(None, None, None, None, None, 0))
+        _, s_crt = self._dev(s_crt, torch.int64)
+        B = int(B)
+        a = torch.empty((B, P.n, P.T), dtype=torch.int64, device=s_crt.device)
+        b = torch.empty((B, P.n, P.T) if kind == self.DISC else (B, P.n),
+                        dtype=torch.float64 if kind == self.CONT else torch.int64, device=s_crt.device)
+        work = self._work(kind, B, s_crt.device)
+        _check(call(_stream(stream), s_crt.data_ptr(), a.data_ptr(), b.data_ptr(), work.data_ptr(), B))
+        return a, b
+
+    def sampleDisc(self, s_crt, B, svar, key=None, ctr=0, stream=None):
+        """B discrete samples (a, b = a s + reduce (errorRounded svar)) (Discrete.hs:38-45), both [B][n][T], CRT basis"""
+        return self._sample(self.DISC, s_crt, B, svar, 0, key, ctr, stream)
+
+    def sampleCont(self, s_crt, B, svar, key=None, ctr=0, stream=None):
+        """B continuous samples (a, b = a s + reduce (tGaussian svar)) (Continuous.hs:45-54): a [B][n][1] in the CRT basis,
+        b float64 [B][n] in [0, q), decoding basis"""
+        return self._sample(self.CONT, s_crt, B, svar, 0, key, ctr, stream)
+
+    def sampleRLWR(self, s_crt, B, p, key=None, ctr=0, stream=None):
+        """B RLWR samples (a, b = roundedProd s a) (RLWR.hs:34-38): a [B][n][1] in the CRT basis, b [B][n] in [0, p)"""
+        return self._sample(self.RLWR, s_crt, B, 1.0, p, key, ctr, stream)
+
+    # ---- error terms and norms ----------------------------------------------------------------------------------------
+    def _error(self, kind, s_crt, a, b, want_e, want_norm, stream):
+        import torch
+        L, P = lib(), self.plan
+        call = lambda st, ap, bp, sp, e, nm, w, nb: L.lolhip_rlwe_error_batch(P._h, st, kind, ap, bp, sp, e, nm, w, nb)
+        _check(call(None, None, None, None, None, None, None, 0))
+        dt = torch.float64 if kind == self.CONT else torch.int64
+        B = self._batch(a)
+        host, a = self._dev(a, torch.int64)
+        _, b = self._dev(b, dt)
+        _, s_crt = self._dev(s_crt, torch.int64)
+        if b.numel() != B * P.n * (P.T if kind == self.DISC else 1):
+            raise ValueError("a and b are not the same number of samples")
+        e = torch.empty((B, P.n), dtype=dt, device=a.device) if want_e else None
+        nm = torch.empty((B,), dtype=dt, device=a.device) if want_norm else None
+        work = self._work(kind, B, a.device)
+        _check(call(_stream(stream), a.data_ptr(), b.data_ptr(), s_crt.data_ptr(), None if e is None else e.data_ptr(),
+                    None if nm is None else nm.data_ptr(), work.data_ptr(), B))
+        out = tuple(t.cpu().numpy() if host else t for t in (e, nm) if t is not None)
+        return out if len(out) > 1 else out[0]
+
+    def errorTermDisc(self, s_crt, a, b, norm=False, stream=None):
+        """liftDec (b - a s) (Discrete.hs:48-52): int64 [B][n], INT64_MIN where the lift does not fit; norm=True: (e, norm)"""
+        return self._error(self.DISC, s_crt, a, b, True, norm, stream)
+
+    def errorTermCont(self, s_crt, a, b, norm=False, stream=None):
+        """lift (b - a s) in K/(qR) (Continuous.hs:57-61): float64 [B][n]; norm=True: (e, norm)"""
+        return self._error(self.CONT, s_crt, a, b, True, norm, stream)
+
+    def errorGSqNormDisc(self, s_crt, a, b, stream=None):
+        """gSqNorm . errorTerm (Discrete.hs:56-59): int64 [B], saturated; the error slab is not returned"""
+        return self._error(self.DISC, s_crt, a, b, False, True, stream)
+
+    def errorGSqNormCont(self, s_crt, a, b, stream=None):
+        """gSqNorm . errorTerm (Continuous.hs:65-68): float64 [B]"""
+        return self._error(self.CONT, s_crt, a, b, False, True, stream)
+
+    # ---- RLWR ---------------------------------------------------------------------------------------------------------
+    def roundedProd(self, s_crt, a, p, stream=None):
+        """roundedProd s a (RLWR.hs:40-44): [B][n] in [0, p), decoding basis"""
+        import torch
+        L, P = lib(), self.plan
+        _check(L.lolhip_rlwr_rounded_prod_batch(P._h, int(p), None, None, None, None, None, 0))
+        B = self._batch(a)
+        host, a = self._dev(a, torch.int64)
+        _, s_crt = self._dev(s_crt, torch.int64)
+        out = torch.empty((B, P.n), dtype=torch.int64, device=a.device)
+        work = self._work(self.RLWR, B, a.device)
+        _check(L.lolhip_rlwr_rounded_prod_batch(P._h, int(p), _stream(stream), a.data_ptr(), s_crt.data_ptr(),
+                                                out.data_ptr(), work.data_ptr(), B))
+        return out.cpu().numpy() if host else out
+
+    def mismatchRLWR(self, s_crt, a, b, p, stream=None):
+        """per sample, the coefficients where b differs from roundedProd s a: int32 [B]"""
+        import torch
+        L, P = lib(), self.plan
+        _check(L.lolhip_rlwr_check_batch(P._h, int(p), None, None, None, None, None, None, 0))
+        B = self._batch(a)
+        host, a = self._dev(a, torch.int64)
+        _, b = self._dev(b, torch.int64)
+        _, s_crt = self._dev(s_crt, torch.int64)
+        if b.numel() != B * P.n:
+            raise ValueError("a and b are not the same number of samples")
+        out = torch.empty((B,), dtype=torch.int32, device=a.device)
+        work = self._work(self.RLWR, B, a.device)
+        _check(L.lolhip_rlwr_check_batch(P._h, int(p), _stream(stream), a.data_ptr(), b.data_ptr(), s_crt.data_ptr(),
+                                         out.data_ptr(), work.data_ptr(), B))
+        return out.cpu().numpy() if host else out
+
+    # ---- instance verification (Verify.hs:346-366): one copy of B values, then the comparison on the host --------------
+    def validDisc(self, bound, s_crt, a, b, stream=None):
+        """bound > errorGSqNorm for every sample (Verify.hs:350): bool [B]"""
+        nm = self.errorGSqNormDisc(s_crt, a, b, stream)
+        nm = nm if isinstance(nm, np.ndarray) else nm.cpu().numpy()
+        return np.asarray(nm.astype(object) < bound, dtype=bool)       # Python integers: exact for any bound
+
+    def validCont(self, bound, s_crt, a, b, stream=None):
+        """bound > errorGSqNorm for every sample (Verify.hs:356): bool [B]"""
+        nm = self.errorGSqNormCont(s_crt, a, b, stream)
+        nm = nm if isinstance(nm, np.ndarray) else nm.cpu().numpy()
+        return float(bound) > nm
+
+    def validRLWR(self, s_crt, a, b, p, stream=None):
+        """b == roundedProd s a for every sample (Verify.hs:362): bool [B]"""
+        mm = self.mismatchRLWR(s_crt, a, b, p, stream)
+        mm = mm if isinstance(mm, np.ndarray) else mm.cpu().numpy()
+        return mm == 0
+
+    @staticmethod
+    def errorBound(m, svar, eps=2.0 ** -25, kind="cont"):
+        """errorBound svar eps over index m (host): kind "cont" (Continuous.hs:74-84) a float, "disc" (Discrete.hs:65-76)
+        an int"""
+        k = {"disc": 0, "cont": 1, 0: 0, 1: 1}[kind]
+        pps = factor_pps(int(m))
+        arr = (_PP * max(1, len(pps)))()
+        for i, (p, e) in enumerate(pps):
+            arr[i].prime, arr[i].exponent = p, e
+        out = C.c_double()
+        _check(lib().lolhip_rlwe_error_bound(arr, len(pps), float(svar), float(eps), k, C.byref(out)))
+        return int(out.value) if k == 0 else out.value

@@ -3,7 +3,8 @@
 (BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone), of encrypt / errorRounded
 (`--encrypt`: that leg alone), of the key-switch / tunnel hints (`--kshint`: that leg alone) and of the key-homomorphic
 ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q = 2^k alone), of ciphertext modSwitch
-(`--modswitch`: that leg alone) and of multi-hop tunnelling (`--tunnel-chain`: that leg alone).  Operands resident in HBM, HIP events on
+(`--modswitch`: that leg alone), of multi-hop tunnelling (`--tunnel-chain`: that leg alone) and of RLWE instance
+verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -458,8 +459,52 @@ def tunnel_chain_leg(gen):
            note="Plan.modSwitch up, per hop lInv / Ext.tunnel / crtInv, two Plan.modSwitch down")
 
 
+def rlwe_leg(gen):
+    """RLWE instance verification norm-only (lolhip_rlwe_error_batch with e_out = NULL) and gSqNorm alone
+    (lolhip_gsqnorm_batch), at the challenge shape and at m = 2^14.  alg_bytes: a and b read once and the [B] norms
+    written (verify; the secret, shared by the batch, is not counted); e read once and the norms written (gsqnorm)."""
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    key = bytes(range(32))
+    lines = []
+
+    def rep(name, cfg, ms, items, alg):
+        d = {"op": name, "config": cfg, "ms": round(ms, 4), "items_per_s": round(items / ms * 1e3, 1),
+             "alg_GBps": round(alg / ms / 1e6, 1)}
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+
+    for label, m, q, B, svar in (("m=256 q=7681", 256, 7681, 65536, 0.28125),
+                                 ("m=2^14 30-bit", 2 ** 14, lol_amd.good_q(2 ** 14, 2 ** 29), 4096, 0.28125)):
+        P = lol_amd.Plan.for_index(m, [q])
+        n = P.n
+        s_crt = torch.empty((n, 1), dtype=torch.int64, device="cuda")
+        assert L.lolhip_rlwe_secret(P._h, st, key, 0, ptr(s_crt)) == 0
+        a = torch.empty((B, n, 1), dtype=torch.int64, device="cuda")
+        nm = torch.empty((B,), dtype=torch.int64, device="cuda")
+        cfg = f"{label} T=1 B={B}"
+        for kind, name in ((0, "rlwe_verify_disc"), (1, "rlwe_verify_cont")):
+            work = torch.empty((L.lolhip_rlwe_work_len(P._h, kind, B),), dtype=torch.int64, device="cuda")
+            b = torch.empty((B, n), dtype=torch.int64, device="cuda")           # 8-byte words of either kind
+            assert L.lolhip_rlwe_sample_batch(P._h, st, kind, 0, ptr(s_crt), svar, key, 0, ptr(a), ptr(b), ptr(work), B) == 0
+            call = lambda: L.lolhip_rlwe_error_batch(P._h, st, kind, ptr(a), ptr(b), ptr(s_crt), None, ptr(nm), ptr(work), B)
+            assert call() == 0
+            rep(name, cfg, timeit(call), B, 2 * B * n * 8 + B * 8)
+            del work, b
+        e = torch.randint(-2 ** 20, 2 ** 20, (B, n), dtype=torch.int64, device="cuda", generator=gen)
+        rep("gsqnorm_i64", cfg, timeit(lambda: L.lolhip_gsqnorm_batch(P._h, st, ptr(e), ptr(nm), B)), B, B * n * 8 + B * 8)
+        del a, e, nm
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rlwe_pipelines.jsonl")
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--rlwe" in sys.argv:             # the RLWE verification / gSqNorm leg alone
+        rlwe_leg(gen)
+        return
     if "--modswitch" in sys.argv:        # the ciphertext modSwitch leg alone
         modswitch_leg(gen)
         return
@@ -545,6 +590,7 @@ def main():
     streaming(gen)
     decrypt_leg(gen)
     encrypt_leg(gen)
+    rlwe_leg(gen)
 
 
 def streaming(gen):
