@@ -17,6 +17,11 @@ Method by method this follows the reference instance (CPP.hs:204-264):
   twacePowDec, embedPow, embedDec, crtExtFuncs, coeffs         ->  lolhip_ext_host (index tables in HBM)
   scalarPow, powBasisPow, crtSetDec, tGaussianDec, gSqNormDec,
   fmapT, unzipT, entail*                                       ->  CT
+
+The batched SymmSHE entries of include/lolhip.h sit beside the class (INTEGRATION.md): (*) -> lolhip_ctmul_crt_batch,
+keySwitchQuadCirc -> lolhip_keyswitch_batch, modSwitch -> lolhip_modswitch_batch, addPublic / mulPublic ->
+lolhip_add_public_batch / lolhip_mul_public_batch, tunnelH -> lolhip_tunnel_chain_batch, ptRound (HomomPRF.hs:215-270)
+-> lolhip_ptround_batch over lolhip_ct_affine_mul_batch; homomPRF is mulPublic, tunnelH and ptRound in a row.
 -}
 
 {-# LANGUAGE ConstraintKinds       #-}

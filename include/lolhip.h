@@ -518,6 +518,70 @@ LOLHIP_API int lolhip_tunnel_chain_batch(const lolhip_tunnel_chain *c, void *str
                                          int64_t l, int64_t p, int64_t *out, int out_crt, int64_t *l_out, int64_t *work,
                                          int64_t B);
 
+/* Homomorphic rounding 2^e -> 2 (ptRound, lol-apps HomomPRF.hs:215-270 over SymmSHE.hs:236-258, 361-390, 444-452).
+ * lolhip_ct_affine_mul_batch: the ciphertext product with both affine pre-steps folded in, CRT basis, one pass.  a, b:
+ *   linear ciphertexts [2][B][n'][T], residues in (-q_t, q_t); the same pointer may be passed for both.  alpha, beta:
+ *   HOST arrays [T] of any int64 (the toLSD / toMSD factors of lolhip_encode_scales, or 1).  va, vb: polynomials
+ *   [npairs][n'][T] shared by the batch, residues in (-q_t, q_t), or NULL (zero).  For every pair j < npairs
+ *     A0 = alpha_t a_0 + va_j,  A1 = alpha_t a_1;   B0 = beta_t b_0 + vb_j,  B1 = beta_t b_1
+ *     out_j = (g A0 B0, g (A0 B1 + A1 B0), g A1 B1),  g = gCRT (as lolhip_ctmul_crt_batch)
+ *   out [npairs][3][B][n'][T], canonical; with npairs = 1 it may alias a or b.  x (p x + v) (addPublic then (*)) is
+ *   a = b = x, beta = p, vb = v; the fan-out (x + v_{2j-1}) (p (x + v_{2j})) over the pairs j reads x once per pair and
+ *   never stores the fanned-out ciphertexts.  Two words per lane with 16-byte accesses when n' T is even and every pointer
+ *   is 16-byte aligned, else one word per lane.
+ *   Status: LOLHIP_ERR_INVALID for npairs < 1 or > 65535, B < 0, T > 16, NULL pointers (va, vb excepted), out = a or b
+ *   with npairs > 1; LOLHIP_ERR_NO_CRT; LOLHIP_ERR_NO_DEVICE / LOLHIP_ERR_DEVICE as elsewhere; all before the launch.
+ * lolhip_ptround_create: ptRound from plaintext modulus p = 2^e (1 <= e <= 16) to 2.  p_lvl[i], i < e: the plan of
+ *   index m' over Z_i, Z_{i+1} = Z_i without its first modulus (ZqDown); p_up[i], i < e - 1: the plan of index m' over
+ *   U_i = Z_i with one more modulus in front (ZqUp); hints[i], i < e - 1: DEVICE pointer, borrowed, ksQuadCircHint of
+ *   the key over U_i, [L_i][2][n'][T(U_i)] with L_i = lolhip_decompose_len(p_up[i], base) (all hints over one gadget);
+ *   pp_m: the plan of index m over p alone (mulGPow of the public constants; needed for e >= 2); x_q0 / x_q1: exts from
+ *   the plans of (m, Z_0) / (m, Z_1) into p_lvl[0] / p_lvl[1], or both NULL for m = m'.  Plans, exts and hints are
+ *   borrowed and must outlive the handle.  Create validates, copies host metadata and uploads the public constants'
+ *   source (1 and y (1 - y), y = 1 .. p/4, as elements of R_m: (p/4 + 1) n_m words) when the plans are device plans.
+ *   Status: LOLHIP_ERR_INVALID for e < 1 or > 16, NULL pointers, lists that are not this ladder, plans of different
+ *   indices, T(U_0) > 16, a bad base, pp_m not of index m over p alone, exts not ending in p_lvl[0] / p_lvl[1] or not
+ *   from one index; LOLHIP_ERR_MODULUS for p != 2^e or an even modulus (gcd(Q, 2) != 1); LOLHIP_ERR_NO_CRT for a plan
+ *   of the ladder without a CRT basis; LOLHIP_ERR_HIP for a failing upload.
+ * lolhip_ptround_batch: cs [2][B][n'][T(Z_0)], CT enc k l over plaintext modulus p, powerful basis (cs_crt = 0) or CRT
+ *   basis (cs_crt = 1), enc 0 = LSD, 1 = MSD -> out [2][B][n'][T(Z_{e-1})], an MSD ciphertext of the rounding over
+ *   plaintext modulus 2 in the basis out_crt asks for, *k_out = 2^(e-1) (k + 1) - 1, *l_out as the reference moves l
+ *   (toLSD / toMSD factors, products, reduce . lift into every halved modulus).  e = 1: out = cs (copied when the
+ *   pointers differ, the basis converted when cs_crt != out_crt), enc, k and l unchanged.  Launch plan, level i over
+ *   plaintext modulus p_i = p / 2^i:
+ *     constants  k_pub_lift -> mulGPow k times on pp_m -> k_pub_lift (l^-1 folded in) -> crt at index m -> k_pub_apply
+ *                (the embed gather) -> k_ct_lincomb (the toMSD factor), once per call at B = 1: the constant 1 for level
+ *                0, y (1 - y) for level 1
+ *     level 0    k_ct_affine_mul x (p x + 1)  (a = b = x, beta = p for MSD input)
+ *     level 1    k_ct_affine_mul (p_1 (xprod + v_{2j-1})) (xprod + v_{2j}) for every pair j < p/8, from xprod alone
+ *     level >= 2 k_ct_affine_mul (p_i a) b over the pairs of the previous level's outputs
+ *     then, per product: lolhip_modswitch_batch Z_i -> U_i (3 components, CRT in, powerful out), crt over c_0, c_1,
+ *                lolhip_keyswitch_batch(hints[i]) over U_i, lolhip_modswitch_batch U_i -> Z_{i+1} (CRT in; CRT out, or
+ *                the caller's basis into out after the last level)
+ *   work: lolhip_ptround_work_len(c, B) int64 of device scratch, 16-byte aligned, with N = B n', T_i = T(Z_i),
+ *   T_u = T_0 + 1 and every term rounded up to even:  the products max(3 N T_0, 3 (p/8) N T_1)  +  two ciphertext lists
+ *   of max(2 N T_0, 2 (p/8) N T_2) each  +  3 N T_u (up)  +  2 N T_u (key-switch output)  +  max_i L_i N T_u (digits)
+ *   +  max(3 N T_0, 2 N T_u) (modSwitch scratch)  +  the constants: (p/4 + 1) (n' T_0 + n_m T_0 + n_m) + n' T_0.
+ *   0 for B = 0 or e = 1; a negative status for bad arguments.
+ *   Status: LOLHIP_ERR_INVALID for NULL pointers, B < 0, enc not 0 / 1, k < 0 or k > 2^40 / p; LOLHIP_ERR_MODULUS
+ *   for l not invertible mod p, and as lolhip_modswitch_batch; LOLHIP_ERR_NO_DEVICE on host-only plans;
+ *   LOLHIP_ERR_DEVICE as elsewhere.
+ *   Every status but a failing launch is decided on the host before the first launch: out, *k_out and *l_out are then
+ *   not written.  A failing launch (LOLHIP_ERR_HIP) leaves out undefined and the scalars unwritten.  The call does not
+ *   allocate or synchronise. */
+LOLHIP_API int lolhip_ct_affine_mul_batch(const lolhip_plan *pq, void *stream, const int64_t *a, const int64_t *alpha,
+                                          const int64_t *va, const int64_t *b, const int64_t *beta, const int64_t *vb,
+                                          int npairs, int64_t *out, int64_t B);
+typedef struct lolhip_ptround lolhip_ptround;
+LOLHIP_API int lolhip_ptround_create(int e, int64_t p, const lolhip_plan *const *p_lvl, const lolhip_plan *const *p_up,
+                                     const int64_t *const *hints, int64_t base, const lolhip_plan *pp_m,
+                                     const lolhip_ext *x_q0, const lolhip_ext *x_q1, lolhip_ptround **out);
+LOLHIP_API void lolhip_ptround_destroy(lolhip_ptround *c);
+LOLHIP_API int64_t lolhip_ptround_work_len(const lolhip_ptround *c, int64_t B);
+LOLHIP_API int lolhip_ptround_batch(const lolhip_ptround *c, void *stream, const int64_t *cs, int cs_crt, int enc, int64_t k,
+                                    int64_t l, int64_t *out, int out_crt, int64_t *k_out, int64_t *l_out, int64_t *work,
+                                    int64_t B);
+
 /* --- gSqNormDec and RLWE / RLWR instances (lol RLWE/{Continuous,Discrete,RLWR}.hs; rlwe-challenges Generate.hs:192-218,
  * Verify.hs:346-366), device pointers ------------------------------------------------------------------------------
  * gSqNormDec (Tensor.hs:147-151; norm.cpp:15-75): e_dec [B][n] decoding-basis coefficients -> out [B],

@@ -10,27 +10,6 @@ using namespace lolhip;
 
 namespace {
 
-void set_scale(PubScales& sc, const Plan& P, const u64* a, const u64* b) {
-  sc = PubScales();
-  sc.T = P.T;
-  for (int t = 0; t < P.T; ++t) {
-    const u64 q = P.qs[(size_t)t];
-    sc.q[t] = q;
-    sc.a[t] = a ? a[t] : 1 % q;
-    sc.ap[t] = make_shoup(sc.a[t], q).wp;
-    sc.b[t] = b ? b[t] : 0;
-    sc.bp[t] = make_shoup(sc.b[t], q).wp;
-  }
-}
-
-// the plan of index m behind x_q (pq itself for x_q = NULL); null when x_q does not end in pq's ring and moduli
-const Plan* lo_plan(const Plan& P, const lolhip_ext* x_q) {
-  if (!x_q) return &P;
-  const ExtPlan& X = x_q->X;
-  if (!same_index(*X.hi, P) || X.hi->qs != P.qs) return nullptr;
-  return X.lo;
-}
-
 // the checks both public entries share, in the order of their statuses.  *lo: the plan of index m
 int public_checks(const lolhip_plan* pq, const lolhip_ext* x_q, int64_t stride, int ncs, int cs_shared,
                   const int64_t* cs, const int64_t* out, const int64_t* work, const int64_t* pub, int64_t B,

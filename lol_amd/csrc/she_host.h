@@ -9,6 +9,7 @@
 #include "lolhip.h"
 #include "pipeline.h"
 #include "plan.h"
+#include "public.h"
 
 struct lolhip_plan { lolhip::Plan P; };
 struct lolhip_ext { lolhip::ExtPlan X; };
@@ -54,6 +55,28 @@ inline uint32_t magic32(int64_t base) {
   int lg = 0;
   while (((u64)1 << lg) < (u64)base) ++lg;
   return (uint32_t)((((u64)1 << 32) * (((u64)1 << lg) - (u64)base)) / (u64)base) + 1;
+}
+
+// the per-modulus Shoup pairs of two scalars over the plan's moduli (a null: 1, b null: 0), P.T <= PIPE_MAX_T
+inline void set_scale(PubScales& sc, const Plan& P, const u64* a, const u64* b) {
+  sc = PubScales();
+  sc.T = P.T;
+  for (int t = 0; t < P.T; ++t) {
+    const u64 q = P.qs[(size_t)t];
+    sc.q[t] = q;
+    sc.a[t] = a ? a[t] : 1 % q;
+    sc.ap[t] = make_shoup(sc.a[t], q).wp;
+    sc.b[t] = b ? b[t] : 0;
+    sc.bp[t] = make_shoup(sc.b[t], q).wp;
+  }
+}
+
+// the plan of index m behind x_q (P itself for x_q = NULL); null when x_q does not end in P's ring and moduli
+inline const Plan* lo_plan(const Plan& P, const lolhip_ext* x_q) {
+  if (!x_q) return &P;
+  const ExtPlan& X = x_q->X;
+  if (!same_index(*X.hi, P) || X.hi->qs != P.qs) return nullptr;
+  return X.lo;
 }
 
 // ---- arithmetic over the plaintext modulus -------------------------------------------------------------------------

@@ -142,6 +142,13 @@ def lib():
     L.lolhip_tunnel_chain_work_len.argtypes = [vp, i64]
     L.lolhip_tunnel_chain_work_len.restype = i64
     L.lolhip_tunnel_chain_batch.argtypes = [vp, vp, vp, ci, ci, i64, i64, vp, ci, _i64p, vp, i64]
+    L.lolhip_ct_affine_mul_batch.argtypes = [vp, vp, vp, _i64p, vp, vp, _i64p, vp, ci, vp, i64]
+    L.lolhip_ptround_create.argtypes = [ci, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i64, vp, vp, vp, C.POINTER(vp)]
+    L.lolhip_ptround_destroy.argtypes = [vp]
+    L.lolhip_ptround_destroy.restype = None
+    L.lolhip_ptround_work_len.argtypes = [vp, i64]
+    L.lolhip_ptround_work_len.restype = i64
+    L.lolhip_ptround_batch.argtypes = [vp, vp, vp, ci, ci, i64, i64, vp, ci, _i64p, _i64p, vp, i64]
     L.lolhip_gsqnorm_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_gsqnorm_f64_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_rlwe_work_len.argtypes = [vp, ci, i64]
@@ -991,6 +998,33 @@ class Plan:
             stream, (cs,), B, lambda: L.lolhip_modswitch_work_len(self._h, to._h, ncs, B), lambda: (ncs, B, to.n, to.T))
         return out, "MSD", int(lo.value)
 
+    def ctAffineMul(self, a, alpha, b=None, beta=1, va=None, vb=None, npairs=1, out=None, stream=None):
+        """The ciphertext product with both affine pre-steps folded in (lolhip_ct_affine_mul_batch), CRT basis: for every
+        pair j, (g A0 B0, g (A0 B1 + A1 B0), g A1 B1) with A0 = alpha a_0 + va_j, A1 = alpha a_1, B0 = beta b_0 + vb_j,
+        B1 = beta b_1.  a, b [2][B][n][T] (b None: b = a, read once); alpha, beta: an int or one int per modulus; va, vb
+        [npairs][n][T] or None -> [npairs][3][B][n][T].  With npairs = 1, out may be a or b."""
+        import torch
+        host, a, na, B = self._cs(a)
+        if b is not None:
+            _, b, nb, Bb = self._cs(b)
+            if Bb != B or nb != 2:
+                raise ValueError("b is not a linear ciphertext of a's batch")
+        if na != 2:
+            raise ValueError("a is not a linear ciphertext [2][B][n][T]")
+        al, be, L, npairs = self._per_mod(alpha), self._per_mod(beta), lib(), int(npairs)
+        _check(L.lolhip_ct_affine_mul_batch(self._h, None, None, al, None, None, be, None, npairs, None, 0))
+        if host:
+            _, (a, b, va, vb) = self._stage(a, b, va, vb)
+        for v in (va, vb):
+            if v is not None and v.numel() != npairs * self.n * self.T:
+                raise ValueError("va / vb are not [npairs][n][T]")
+        if out is None:
+            out = torch.empty((npairs, 3, B, self.n, self.T), dtype=torch.int64, device=a.device)
+        opt = lambda t: None if t is None else _devptr(t)
+        _check(L.lolhip_ct_affine_mul_batch(self._h, _stream(stream), _devptr(a), al, opt(va), _devptr(a if b is None else b),
+                                            be, opt(vb), npairs, _devptr(out), B))
+        return self._unstage(host, out)
+
     def absorbGFactors(self, cs, k, pp, stream=None):
         """absorbGFactors (SymmSHE.hs:464-473) of a CRT-basis ciphertext: every c_i times decode'(divG^k 1), divG over
         pp (the Plan of this index over p alone) -> (cs, 0)"""
@@ -1206,6 +1240,72 @@ class TunnelChain:
             ctr += rel * L
             s_in = s_out.reshape(S.n, S.T)
         return out_h, out_y, s_in, ctr
+
+
+class PTRound:
+    """ptRound (HomomPRF.hs:215-270): homomorphic rounding from plaintext modulus p = 2^e to 2 as one call
+    (lolhip_ptround_batch).  plans[i], i < e: the Plan of index m' over Z_i, each list the one before without its first
+    modulus; up_plans[i], i < e - 1: the Plan over U_i = one more modulus in front of Z_i; hints[i] [L_i][2][n'][T(U_i)]:
+    ksQuadCircHint of the key over U_i as CUDA tensors (kept alive here; PTRound.hints makes them); pp_m: the Plan of
+    index m over p alone (made here when None); exts: (Ext from (m, Z_0) to plans[0], Ext from (m, Z_1) to plans[1]), or
+    None for m = m'."""
+
+    def __init__(self, plans, up_plans, hints, base, p, pp_m=None, exts=None):
+        self.plans, self.up_plans, self.hint_slabs = list(plans), list(up_plans), list(hints)
+        self.base, self.p, self.exts = int(base), int(p), (None if exts is None else tuple(exts))
+        e = len(self.plans)
+        if e < 1 or len(self.up_plans) != e - 1 or len(self.hint_slabs) != e - 1:
+            raise ValueError("e plans, e - 1 up plans and e - 1 hints")
+        if pp_m is None and e > 1:
+            lo = self.plans[0] if self.exts is None else self.exts[0].lo
+            pp_m = Plan(lo.pps, [self.p])
+        self.pp_m = pp_m
+        arr = lambda vals: (C.c_void_p * max(len(vals), 1))(*vals)
+        xs = (None, None) if self.exts is None else tuple(None if x is None else x._h for x in self.exts)
+        h = C.c_void_p()
+        _check(lib().lolhip_ptround_create(e, self.p, arr([q._h for q in self.plans]), arr([q._h for q in self.up_plans]),
+                                           arr([_devptr(x) for x in self.hint_slabs]), self.base,
+                                           None if pp_m is None else pp_m._h, xs[0], xs[1] if e > 1 else None, C.byref(h)),
+               "ptround_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.lolhip_ptround_destroy(h)
+
+    def workLen(self, B):
+        w = lib().lolhip_ptround_work_len(self._h, int(B))
+        _check(min(w, 0))
+        return w
+
+    def __call__(self, cs, enc="MSD", k=0, l=1, cs_crt=False, out_crt=False, stream=None):
+        """cs [2][B][n'][T(Z_0)]: CT enc k l over plaintext modulus p, powerful basis or CRT basis (cs_crt) ->
+        (out [2][B][n'][T(Z_{e-1})], "MSD", k_out, l_out) over plaintext modulus 2; for e = 1 the input itself, its
+        encoding, k and l unchanged."""
+        _, cs, ncs, B = self.plans[0]._cs(cs)
+        if ncs != 2:
+            raise LolHipError(ERR_INVALID, "ptRound takes a linear ciphertext")
+        L, ko, lo, last = lib(), C.c_int64(0), C.c_int64(0), self.plans[-1]
+        args = (int(cs_crt), Plan._enc(enc), int(k), int(l))
+        out = Plan._run_staged(
+            lambda st, i, o, w, b: L.lolhip_ptround_batch(self._h, st, i[0], *args, o, int(out_crt), C.byref(ko), C.byref(lo),
+                                                           w, b),
+            stream, (cs,), B, lambda: self.workLen(B), lambda: (2, B, last.n, last.T))
+        return out, ("MSD" if len(self.plans) > 1 else ("LSD", "MSD")[Plan._enc(enc)]), int(ko.value), int(lo.value)
+
+    @staticmethod
+    def hints(up_plans, s_crts, svar, base, key=None, ctr=0, stream=None):
+        """roundHints (HomomPRF.hs:255-258) on the device: one Plan.ksQuadCircHint per level, over U_i.  s_crts[i]
+        [n'][T(U_i)]: the key reduced into U_i's moduli, CRT basis.  Stream items: level i draws its L_i =
+        up_plans[i].decomposeLen(base) LWE samples at items ctr_i .. ctr_i + L_i - 1 of the hint domains, ctr_0 = ctr and
+        ctr_(i+1) = ctr_i + L_i, so two levels never share a stream block under one key.
+        Returns (hints, the next free ctr)."""
+        out = []
+        for U, s in zip(up_plans, s_crts):
+            out.append(U.ksQuadCircHint(s, svar, base, key=key, ctr=ctr, stream=stream))
+            ctr += U.decomposeLen(base)
+        return out, ctr
 
 
 # ---- key-homomorphic ring PRF (lol-apps KeyHomomorphicPRF.hs) -------------------------------

@@ -3,7 +3,8 @@
 (BASELINE configs 3 and 5 shapes), of decrypt (`--decrypt`: that leg alone), of encrypt / errorRounded
 (`--encrypt`: that leg alone), of the key-switch / tunnel hints (`--kshint`: that leg alone) and of the key-homomorphic
 ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q = 2^k alone), of ciphertext modSwitch
-(`--modswitch`: that leg alone), of multi-hop tunnelling (`--tunnel-chain`: that leg alone) and of RLWE instance
+(`--modswitch`: that leg alone), of multi-hop tunnelling (`--tunnel-chain`: that leg alone), of homomorphic rounding
+(`--ptround`: that leg alone, also written to profiles/ptround_pipelines.jsonl) and of RLWE instance
 verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl).  Operands resident in HBM, HIP events on
 the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
@@ -459,6 +460,177 @@ def tunnel_chain_leg(gen):
            note="Plan.modSwitch up, per hop lInv / Ext.tunnel / crtInv, two Plan.modSwitch down")
 
 
+def ptround_leg(gen):
+    """Homomorphic rounding 2^e -> 2 (lolhip_ptround_batch) at the tail of HomomPRF: index 9*5*7*13 (n' = 1728, m = m'),
+    p = 8, ZQ3 -> ZQ1 with the up lists ZQ4 / ZQ3, base 2, B = 512 (the key switch's digit buffer over ZQ4 is then
+    L B n' T 8 bytes = 100 * 512 * 1728 * 4 * 8 = 2.8 GB), random hints (timing only).
+      (a) k_ct_affine_mul against the same step composed from the entries that were there before it: level 0 as
+          lolhip_add_public_batch then lolhip_ctmul_crt_batch; the fan-out + pair step as two lolhip_add_public_batch, two
+          toMSD (modSwitchPT) and one toLSD ((*) of two MSD operands) through lolhip_ct_lincomb_batch, then
+          lolhip_ctmul_crt_batch.  The routes alternate in one process, five rounds of ten calls; median, min and max.
+      (b) the whole chain and every pass of it alone at the chain's shapes.
+      (c) the achieved bytes/s of (a) against lolhip_copy_slab on a slab of the product's size.
+    alg_bytes of the products: 2 component slabs read and 3 written (gCRT and the constants are cache-resident).
+    Also written to profiles/ptround_pipelines.jsonl."""
+    import ctypes
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    m, p, base, B = 9 * 5 * 7 * 13, 8, 2, 512
+    lv = [lol_amd.Plan.for_index(m, ZQ5[2 + i:]) for i in range(3)]
+    up = [lol_amd.Plan.for_index(m, ZQ5[1 + i:]) for i in range(2)]
+    pp = lol_amd.Plan.for_index(m, [p])
+    n = lv[0].n
+    lines = []
+
+    def rep(name, cfg, times, items, alg, note=None):
+        ms = statistics.median(times)
+        d = {"op": name, "config": cfg, "ms": round(ms, 4), "ms_min": round(min(times), 4), "ms_max": round(max(times), 4),
+             "rounds": len(times), "items_per_s": round(items / ms * 1e3, 1), "alg_GBps": round(alg / ms / 1e6, 1),
+             "frac_of_8TBps": round(alg / ms / 1e6 / 8000, 4)}
+        if note:
+            d["note"] = note
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+
+    def alternate(f, g, rounds=5):
+        tf, tg = [], []
+        for _ in range(rounds):
+            tf.append(timeit(f)); tg.append(timeit(g))
+        return tf, tg
+
+    arr = lambda P, v: (ctypes.c_int64 * P.T)(*[int(x) for x in v])
+    lo_out = ctypes.c_int64(0)
+    one_src = torch.zeros((1, n), dtype=torch.int64, device="cuda"); one_src[0, 0] = 1
+    # ---- (a) level 0: x (p x + 1), MSD input, k = 0 -------------------------------------------------------------------
+    Z = lv[0]
+    slab = B * n * Z.T * 8
+    x = rnd(gen, Z.qs, 2, B, n)
+    v1 = rnd(gen, Z.qs, 1, n)
+    prod = torch.empty((1, 3, B, n, Z.T), dtype=torch.int64, device="cuda")
+    xp = torch.empty_like(x)
+    e = [torch.empty((B, n, Z.T), dtype=torch.int64, device="cuda") for _ in range(3)]
+    wpub = torch.empty((max(L.lolhip_public_work_len(Z._h, None, B), 1),), dtype=torch.int64, device="cuda")
+    ones, ps = arr(Z, [1] * Z.T), arr(Z, [p] * Z.T)
+
+    def fused0():
+        rc = L.lolhip_ct_affine_mul_batch(Z._h, st, ptr(x), ones, None, ptr(x), ps, ptr(v1), 1, ptr(prod), B)
+        assert rc == 0, rc
+
+    def composed0():
+        rc = L.lolhip_add_public_batch(Z._h, None, pp._h, st, ptr(one_src), 0, ptr(x), 2, 0, 1, 1, 0, 1, p, ptr(xp),
+                                       ctypes.byref(lo_out), ptr(wpub), B)
+        assert rc == 0, rc
+        L.lolhip_ctmul_crt_batch(Z._h, st, ptr(x[0]), ptr(x[1]), ptr(xp[0]), ptr(xp[1]), ptr(e[0]), ptr(e[1]), ptr(e[2]), B)
+
+    # the same words: the fused pass given the constant the composed route adds, decode'(l^-1) with l = 1 through toLSD
+    # (a scalar with k = 0 is a constant vector in the CRT basis)
+    dec = lambda v: v % p - p if 2 * (v % p) >= p else v % p
+    v1[:] = torch.tensor([dec(pow(Z.encodeScales(p, False)[1], -1, p)) % q for q in Z.qs], dtype=torch.int64, device="cuda")
+    fused0(); composed0()
+    torch.cuda.synchronize()
+    assert all(torch.equal(prod[0, i], e[i]) for i in range(3)), "level 0: the two routes differ"
+    cfg = f"m'={m} ZQ3 p={p} B={B} MSD k=0"
+    tf, tc = alternate(fused0, composed0)
+    rep("ptround_level0_fused", cfg, tf, B, 5 * slab, note="one k_ct_affine_mul pass")
+    rep("ptround_level0_composed", cfg, tc, B, 5 * slab, note="lolhip_add_public_batch then lolhip_ctmul_crt_batch")
+    # ---- (a) fan-out + pair over Z_1: (p_1 (xprod + v_1)) (xprod + v_2) ---------------------------------------------------
+    Z = lv[1]
+    slab = B * n * Z.T * 8
+    x = rnd(gen, Z.qs, 2, B, n)
+    prod = torch.empty((1, 3, B, n, Z.T), dtype=torch.int64, device="cuda")
+    xs = [torch.empty_like(x) for _ in range(2)]
+    e = [torch.empty((B, n, Z.T), dtype=torch.int64, device="cuda") for _ in range(3)]
+    wpub = torch.empty((max(L.lolhip_public_work_len(Z._h, None, B), 1),), dtype=torch.int64, device="cuda")
+    ys = [torch.zeros((1, n), dtype=torch.int64, device="cuda") for _ in range(2)]
+    ys[1][0, 0] = -2                                                 # y (1 - y) for y = 1, 2
+    zq_m = arr(Z, Z.encodeScales(p, True)[0])                       # toMSD over plaintext modulus p
+    zq_l = arr(Z, Z.encodeScales(p // 2, False)[0])                 # toLSD over p / 2
+    inv_p = [pow(p, -1, q) for q in Z.qs]
+    # the constants as the fused pass takes them: addPublic's polynomial through toMSD's p^-1 (and toLSD's p_1 on the a side);
+    # a scalar with l = 1 and k = 0 is a constant vector in the CRT basis
+    va = torch.tensor([[0] * Z.T] * n, dtype=torch.int64, device="cuda").reshape(1, n, Z.T)
+    c2 = dec(-2 * pow(Z.encodeScales(p, False)[1], -1, p))
+    vb = torch.tensor([[(c2 * w) % q for w, q in zip(inv_p, Z.qs)]] * n, dtype=torch.int64, device="cuda").reshape(1, n, Z.T)
+    ones = arr(Z, [1] * Z.T)
+
+    def fused1():
+        rc = L.lolhip_ct_affine_mul_batch(Z._h, st, ptr(x), zq_l, ptr(va), ptr(x), ones, ptr(vb), 1, ptr(prod), B)
+        assert rc == 0, rc
+
+    def composed1():
+        for y, o in zip(ys, xs):
+            rc = L.lolhip_add_public_batch(Z._h, None, pp._h, st, ptr(y), 0, ptr(x), 2, 0, 1, 1, 0, 1, p, ptr(o),
+                                           ctypes.byref(lo_out), ptr(wpub), B)
+            assert rc == 0, rc
+            L.lolhip_ct_lincomb_batch(Z._h, st, ptr(o), 2, zq_m, None, 0, None, ptr(o), B)       # modSwitchPT: toMSD
+        L.lolhip_ct_lincomb_batch(Z._h, st, ptr(xs[0]), 2, zq_l, None, 0, None, ptr(xs[0]), B)   # (*): toLSD of the first
+        L.lolhip_ctmul_crt_batch(Z._h, st, ptr(xs[0][0]), ptr(xs[0][1]), ptr(xs[1][0]), ptr(xs[1][1]), ptr(e[0]), ptr(e[1]),
+                                 ptr(e[2]), B)
+
+    fused1(); composed1()
+    torch.cuda.synchronize()
+    assert all(torch.equal(prod[0, i], e[i]) for i in range(3)), "fan-out: the two routes differ"
+    cfg = f"m'={m} ZQ2 p={p} B={B} one pair"
+    tf, tc = alternate(fused1, composed1)
+    rep("ptround_fanout_pair_fused", cfg, tf, B, 5 * slab, note="one k_ct_affine_mul pass")
+    rep("ptround_fanout_pair_composed", cfg, tc, B, 5 * slab,
+        note="2 lolhip_add_public_batch, 3 lolhip_ct_lincomb_batch (2 toMSD, 1 toLSD), lolhip_ctmul_crt_batch")
+    # ---- (c) the copy yardstick on a slab of the level-0 product's traffic ----------------------------------------------
+    words = 5 * B * n * lv[0].T // 2
+    src = torch.empty((words,), dtype=torch.int64, device="cuda"); dst = torch.empty_like(src)
+    tcopy = [timeit(lambda: L.lolhip_copy_slab(st, ptr(dst), ptr(src), words * 8, 0)) for _ in range(5)]
+    rep("copy_slab", f"{words * 8 >> 20} MiB read + written", tcopy, B, 2 * words * 8, note="lolhip_copy_slab, the HBM yardstick")
+    del x, prod, xs, e, src, dst, xp
+    # ---- (b) the whole chain and its passes ------------------------------------------------------------------------------
+    hints = [rnd(gen, U.qs, U.decomposeLen(base), 2, n) for U in up]
+    chain = lol_amd.PTRound(lv, up, hints, base, p, pp_m=pp)
+    cs = rnd(gen, lv[0].qs, 2, B, n)
+    work = torch.empty((chain.workLen(B),), dtype=torch.int64, device="cuda")
+    out = torch.empty((2, B, n, lv[2].T), dtype=torch.int64, device="cuda")
+    ko = ctypes.c_int64(0)
+
+    def whole():
+        rc = L.lolhip_ptround_batch(chain._h, st, ptr(cs), 1, 1, 0, 1, ptr(out), 1, ctypes.byref(ko), ctypes.byref(lo_out),
+                                    ptr(work), B)
+        assert rc == 0, rc
+
+    cfg = f"m'={m} p={p} ZQ3 -> ZQ1 up ZQ4 / ZQ3 base={base} B={B} CRT in/out"
+    alg = 8 * 2 * B * n * (lv[0].T + lv[2].T)
+    rep("ptround", cfg, [timeit(whole, iters=5) for _ in range(3)], B, alg,
+        note=f"one lolhip_ptround_batch call; work {work.numel() * 8 >> 20} MiB; alg_bytes: the input and output ciphertexts")
+    del work
+    for i in range(2):
+        Zi, U, Zn = lv[i], up[i], lv[i + 1]
+        pi = p >> i
+        p3 = rnd(gen, Zi.qs, 3, B, n)
+        u3 = torch.empty((3, B, n, U.T), dtype=torch.int64, device="cuda")
+        k2 = torch.empty((2, B, n, U.T), dtype=torch.int64, device="cuda")
+        o2 = torch.empty((2, B, n, Zn.T), dtype=torch.int64, device="cuda")
+        Ld = U.decomposeLen(base)
+        dig = torch.empty((Ld, B, n, U.T), dtype=torch.int64, device="cuda")
+        sub = torch.empty((max(3 * B * n * Zi.T, 2 * B * n * U.T),), dtype=torch.int64, device="cuda")
+        x2 = rnd(gen, Zi.qs, 2, B, n)
+        one_i = arr(Zi, [1] * Zi.T)
+        w = 8 * B * n
+        steps = (
+            ("k_ct_affine_mul", lambda: L.lolhip_ct_affine_mul_batch(Zi._h, st, ptr(x2), one_i, None, ptr(x2), one_i, None, 1, ptr(p3), B), 5 * w * Zi.T),
+            ("modswitch up (3 comps, CRT -> powerful)", lambda: L.lolhip_modswitch_batch(Zi._h, U._h, st, ptr(p3), 3, 1, 1, 1, pi, ptr(u3), 0, ctypes.byref(lo_out), ptr(sub), B), 3 * w * (Zi.T + U.T)),
+            ("crt c0, c1", lambda: L.lolhip_crt_batch(U._h, st, ptr(u3), 2 * B), 4 * w * U.T),
+            ("keyswitch", lambda: L.lolhip_keyswitch_batch(U._h, st, ptr(u3[2]), base, ptr(hints[i]), 2, ptr(u3), ptr(k2), ptr(dig), B), 5 * w * U.T),
+            ("modswitch down (2 comps, CRT -> CRT)", lambda: L.lolhip_modswitch_batch(U._h, Zn._h, st, ptr(k2), 2, 1, 1, 1, pi, ptr(o2), 1, ctypes.byref(lo_out), ptr(sub), B), 2 * w * (U.T + Zn.T)),
+        )
+        for name, fn, ab in steps:
+            assert fn() == 0
+            rep(f"  level {i}: {name}", f"T={Zi.T} up {U.T} L={Ld}", [timeit(fn, iters=5) for _ in range(3)], B, ab)
+        del p3, u3, k2, o2, dig, sub, x2
+    os.makedirs(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles"), exist_ok=True)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ptround_pipelines.jsonl")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def rlwe_leg(gen):
     """RLWE instance verification norm-only (lolhip_rlwe_error_batch with e_out = NULL) and gSqNorm alone
     (lolhip_gsqnorm_batch), at the challenge shape and at m = 2^14.  alg_bytes: a and b read once and the [B] norms
@@ -504,6 +676,9 @@ def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
     if "--rlwe" in sys.argv:             # the RLWE verification / gSqNorm leg alone
         rlwe_leg(gen)
+        return
+    if "--ptround" in sys.argv:          # the homomorphic rounding leg alone
+        ptround_leg(gen)
         return
     if "--modswitch" in sys.argv:        # the ciphertext modSwitch leg alone
         modswitch_leg(gen)
