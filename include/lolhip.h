@@ -735,7 +735,11 @@ LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_
 /* Test and A/B aid, not part of the drop-in surface: force a launch path.  `name` is one of
  * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built) and NO_TRUNC (each is
  * also read ONCE at first use from the environment variable LOLHIP_<name>); value 0 restores the
- * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID. */
+ * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID.
+ * Two environment variables are test hooks of the persistent pipelined poly-mul, read at EVERY launch of it:
+ *   LOLHIP_PIPE_GRID=<G>  its grid is G workgroups (clamped to the batch) instead of the resident-workgroup count;
+ *   LOLHIP_PIPE_INFO      (set to anything) each launch prints one line to stderr, before the grid is clamped:
+ *                         "k_pow2_pipe<L,AR>: lds <bytes> B, per_cu <w>, occupancy query <o> (err <e>), grid <G>". */
 LOLHIP_API int lolhip_debug_set(const char *name, int value);
 
 /* number of HIP devices visible (0 without a GPU); never initialises a context */
