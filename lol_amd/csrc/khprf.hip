@@ -14,7 +14,10 @@
 // when every one of the 2^c_v sub-inputs occurs in the window ("full") and w_v - (x0 >> s_v) otherwise.  Slot k of v
 // stands for w_v = k (full) or (x0 >> s_v) + k, and its children's prefixes are w_v >> (s_child - s_v).  When the
 // right child r is full, slots k, k + 2^c_r, k + 2 * 2^c_r, ... have one right slot: a thread takes KG of them, so
-// each D word it loads serves KG left slots (and each L word JG entries) from registers.
+// each D word it loads serves KG left slots (and each L word JG entries) from registers.  When r is not full no two
+// slots of v share a right slot (R = U_v: every group holds one slot).  A leaf child always counts as full: its two
+// slots are a0 and a1, picked by the low bit of its prefix.  A full v has full children; the root's slots are the
+// window itself (U = B, slot k = input x0 + k).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>

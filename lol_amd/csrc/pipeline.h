@@ -103,8 +103,9 @@ hipError_t launch_khprf_keymul(hipStream_t s, const i64* A, const i64* s_crt, i6
 // y = fst (divModCent (p lift y) q) mod p in place (rescaleMod, q odd, p q < 2^63)
 hipError_t launch_khprf_round(hipStream_t s, i64* y, i64 total, i64 p, const ModCtx& mc);
 // the lifted family (q = 2^qbits, node products exact mod the NTT prime Q): dst = the pass `mode` of src, words in
-// [0, Q) / [0, q); src == dst allowed, both 16-byte aligned.  LIFT_FROM_Q: reduce lift_Q x mod q; LIFT_TO_Q: lift_q into
-// [0, Q); LIFT_ROUND: fst (divModCent (p lift_q r) q) mod p (needs p q < 2^63; not with LIFT_TO_Q)
+// [0, Q) / [0, q); src == dst allowed; 16-byte accesses when both are 16-byte aligned, 8-byte ones otherwise.
+// LIFT_FROM_Q: reduce lift_Q x mod q; LIFT_TO_Q: lift_q into [0, Q); LIFT_ROUND: fst (divModCent (p lift_q r) q) mod p
+// (needs p q < 2^63; not with LIFT_TO_Q)
 enum { LIFT_FROM_Q = 1, LIFT_TO_Q = 2, LIFT_ROUND = 4 };
 struct KhprfLift {
   u64 Q;                       // the NTT prime
