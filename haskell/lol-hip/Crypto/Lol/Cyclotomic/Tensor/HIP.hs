@@ -15,13 +15,16 @@ Method by method this follows the reference instance (CPP.hs:204-264):
   zipWithT                           SV.zipWith                ->  unchanged (the class cannot see that f = (*));
                                                                    Cyc's ring product goes through HIP.Batch.mulCRT
   twacePowDec, embedPow, embedDec, crtExtFuncs, coeffs         ->  lolhip_ext_host (index tables in HBM)
-  scalarPow, powBasisPow, crtSetDec, tGaussianDec, gSqNormDec,
-  fmapT, unzipT, entail*                                       ->  CT
+  powBasisPow                                                  ->  lolhip_ext_table 6 (host tables; any element type)
+  crtSetDec                                                    ->  lolhip_crtset_dec (host; prime fields over Int64),
+                                                                   with liblolhip's own root of unity (include/lolhip.h)
+  scalarPow, tGaussianDec, gSqNormDec, fmapT, unzipT, entail*  ->  CT
 
 The batched SymmSHE entries of include/lolhip.h sit beside the class (INTEGRATION.md): (*) -> lolhip_ctmul_crt_batch,
 keySwitchQuadCirc -> lolhip_keyswitch_batch, modSwitch -> lolhip_modswitch_batch, addPublic / mulPublic ->
 lolhip_add_public_batch / lolhip_mul_public_batch, tunnelH -> lolhip_tunnel_chain_batch, ptRound (HomomPRF.hs:215-270)
--> lolhip_ptround_batch over lolhip_ct_affine_mul_batch; homomPRF is mulPublic, tunnelH and ptRound in a row.
+-> lolhip_ptround_batch over lolhip_ct_affine_mul_batch; homomPRF is mulPublic, tunnelH and ptRound in a row.  UCyc.crtSet
+-> lolhip_crtset, ptTunnel (HomomPRF.hs:510-531) -> lolhip_pt_tunnel_batch.
 -}
 
 {-# LANGUAGE ConstraintKinds       #-}
@@ -133,8 +136,22 @@ instance Tensor HT where
     return (viaExt ExtTwaceCRT tw False, viaExt ExtEmbedCRT em True)
 
   coeffs (HT x) = HT <$> coeffs x              -- list-valued; the slab form is HIP.Batch.coeffsBatch
-  powBasisPow   = (fmap HT) <$> powBasisPow
-  crtSetDec     = (fmap HT) <$> crtSetDec
+  -- unit vectors at the indices of lolhip_ext_table 6; needs no modulus, so the plans are taken over a dummy prime
+  powBasisPow :: forall m m' r . (m `Divides` m', Ring r, TElt HT r) => Tagged m [HT m' r]
+  powBasisPow = tag $
+    let phi' = proxy totientFact (Proxy :: Proxy m')
+        plan pm = planFor pm [12289]
+        ext = extFor (plan $ proxy ppsFact (Proxy :: Proxy m)) (plan $ proxy ppsFact (Proxy :: Proxy m'))
+    in [ HT $ fromVec $ SV.generate phi' (\j -> if j == k then LP.one else LP.zero) | k <- powBasisPowIdx ext ]
+
+  -- prime fields whose representation is Int64 take liblolhip's host routine; any other field stays on CT
+  crtSetDec :: forall m m' fp . (m `Divides` m', PrimeField fp, Coprime (PToF (CharOf fp)) m', TElt HT fp)
+            => Tagged m [HT m' fp]
+  crtSetDec = case hipModuli (Proxy :: Proxy fp) of
+    Just [p] -> tag $ map (HT . fromVec . SV.unsafeCast) $
+                  crtSetDecHost (proxy ppsFact (Proxy :: Proxy m)) (proxy ppsFact (Proxy :: Proxy m'))
+                                (fromIntegral p) (proxy totientFact (Proxy :: Proxy m'))
+    _        -> (fmap HT) <$> crtSetDec
 
   fmapT f (HT x) = HT (fmapT f x)
   zipWithT f (HT a) (HT b) = HT (zipWithT f a b)

@@ -18,6 +18,7 @@ module Crypto.Lol.Cyclotomic.Tensor.HIP.Backend
 ( PlanH, ExtH, Plan, Ext, Op(..), ExtOp(..)
 , planFor, extFor, planHasCRT
 , opHost, opHostMaybe, op2Host, extHost
+, powBasisPowIdx, crtSetDecHost
 , ok, errNotDivisible
 ) where
 
@@ -71,6 +72,12 @@ foreign import ccall safe "lolhip_op_host"
   c_opHost :: Ptr PlanH -> CInt -> Ptr Int64 -> Ptr Int64 -> Int64 -> IO CInt
 foreign import ccall safe "lolhip_ext_host"
   c_extHost :: Ptr ExtH -> CInt -> Ptr Int64 -> Ptr Int64 -> Int64 -> IO CInt
+
+-- host number theory (no device): powBasisPow as lolhip_ext_table 6, crtSetDec (include/lolhip.h)
+foreign import ccall unsafe "lolhip_ext_table"
+  c_extTable :: Ptr ExtH -> CInt -> Ptr Int32 -> Int64 -> IO Int64
+foreign import ccall unsafe "lolhip_crtset_dec"
+  c_crtSetDec :: Ptr CPP -> CInt -> Ptr CPP -> CInt -> Int64 -> Ptr Int64 -> Int64 -> IO Int64
 
 -- | One plan per (prime powers, moduli), created on first use and kept for the life of the
 -- process: where CT recomputes @ru@/@ruInv@ per type (CPP.hs:422-442) and re-marshals the moduli
@@ -145,3 +152,26 @@ extHost ext op b outLen x = unsafePerformIO $ do
           c_extHost pe (fromIntegral $ fromEnum op) (castPtr py) (castPtr px) b
   when (rc /= ok) $ error $ "lolhip_ext_host " ++ show op ++ ": status " ++ show rc
   SV.unsafeFreeze y
+
+-- | powBasisPow: the n'/n powerful-basis indices at which the relative powerful basis elements of O_m'/O_m are unit
+-- vectors (lolhip_ext_table 6; CPP/Extension.hs:131-141).
+powBasisPowIdx :: Ext -> [Int]
+powBasisPowIdx ext = unsafePerformIO $ withForeignPtr ext $ \px -> do
+  cnt <- c_extTable px 6 nullPtr 0
+  y <- SM.new (fromIntegral cnt)
+  _ <- SM.unsafeWith y $ \py -> c_extTable px 6 py cnt
+  map fromIntegral . SV.toList <$> SV.unsafeFreeze y
+
+-- | crtSetDec m m' p: the K elements of the mod-p CRT set of O_m'/O_m as rows of phi(m') residues in [0, p), decoding
+-- basis, in the reference's order (lolhip_crtset_dec).  The primitive m'-th root of unity follows the rule stated in
+-- include/lolhip.h, not CT's table of irreducibles: the set is the same, its order may be a permutation of CT's.
+crtSetDecHost :: [(Int, Int)] -> [(Int, Int)] -> Int -> Int -> [SV.Vector Int64]
+crtSetDecHost pps pps' p phi' = unsafePerformIO $
+  SV.unsafeWith (marshalFactors pps) $ \pm -> SV.unsafeWith (marshalFactors pps') $ \pm' -> do
+    let (nm, nm') = (fromIntegral $ length pps, fromIntegral $ length pps')
+    k <- c_crtSetDec pm nm pm' nm' (fromIntegral p) nullPtr 0
+    when (k < 0) $ error $ "lolhip_crtset_dec: status " ++ show k
+    y <- SM.new (fromIntegral k * phi')
+    _ <- SM.unsafeWith y $ \py -> c_crtSetDec pm nm pm' nm' (fromIntegral p) py k
+    v <- SV.unsafeFreeze y
+    return [SV.slice (i * phi') phi' v | i <- [0 .. fromIntegral k - 1]]

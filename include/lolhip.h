@@ -201,7 +201,9 @@ LOLHIP_API int lolhip_tunnel_batch(const lolhip_ext *x_er, const lolhip_ext *x_e
                                    const int64_t *hints, int64_t base, int64_t *out, int64_t *work, int64_t B);
 /* host index tables: which 0 extIndicesPowDec[n] 1 extIndicesCRT[n'] 2 embedPow[n'] (-1 = zero)
  * 3 embedDec[n'] (-1 zero, bit 30 = negate) 4 baseIndicesCRT[n'] (Tensor.hs:426-468)
- * 5 extIndicesCoeffs[n'/n][n] flattened (Tensor.hs:472-477) */
+ * 5 extIndicesCoeffs[n'/n][n] flattened (Tensor.hs:472-477)
+ * 6 powBasisPow[n'/n] (CPP/Extension.hs:131-141): element i of the relative powerful basis of O_m'/O_m is the
+ *   powerful-basis unit vector at index powBasisPow[i] (= table 5 at [i][0]); sum_i embedPow(coeffs_i x) b_i = x */
 LOLHIP_API int64_t lolhip_ext_table(const lolhip_ext *x, int which, int32_t *out, int64_t len);
 
 /* --- ring-level pipelines of SymmSHE, device pointers -----------
@@ -643,6 +645,79 @@ LOLHIP_API int lolhip_rlwr_rounded_prod_batch(const lolhip_plan *pq, int64_t p, 
 LOLHIP_API int lolhip_rlwr_check_batch(const lolhip_plan *pq, int64_t p, void *stream, const int64_t *a_crt, const int64_t *b,
                                        const int64_t *s_crt, int32_t *mismatch, int64_t *work, int64_t B);
 LOLHIP_API int lolhip_rlwe_error_bound(const lolhip_pp *pps, int npps, double svar, double eps, int kind, double *out);
+
+/* --- crtSetDec, crtSet, and the clear-text tunnel of HomomPRF (lol-cpp CPP/Extension.hs:131-164; lol UCyc.hs:540-565,
+ * ZmStar.hs:52-88, Tensor.hs:300-313; lol-apps HomomPRF.hs:400-411, 510-531) ---------------------------------------
+ * powBasisPow is lolhip_ext_table(x, 6): the n'/n indices at which the relative powerful basis elements are unit vectors.
+ * lolhip_crtset_dec (host): the mod-p CRT set of O_m'/O_m, p prime, p not dividing m', m | m'.  With d = ord_m'(p),
+ *   K = (phi(m')/d) / (phi(m)/ord_m(p)) elements; out [K][phi(m')] residues in [0, p), decoding basis of O_m':
+ *     element c, entry j = mhat'^-1 Tr_{GF(p^d)/F_p}( sum_{i in reps_c} twCRTs(j, zmsToIndex i) )
+ *   twCRTs(j, i) = prod_k w_k^(-pow_k(j_k) i) (1 - w_k^(i p_k^(e_k - 1)))  over the prime powers p_k^e_k of m' (the
+ *   second factor for odd p_k only), w_k = w^(m'/p_k^e_k), pow_k = indexToPow, j_0 (the first prime power) fastest.
+ *   reps_c: partitionCosets, in the reference's order.  The cosets of <p> in Z_m'^* are grouped by the coset of <p> in
+ *   Z_m^* they reduce to; the groups are ordered by their smallest residue mod m, each group holds its cosets by
+ *   DESCENDING smallest element, and element c takes coset c of every group (its smallest element is the representative).
+ *   THE ROOT w.  GF(p^d) = F_p[x]/(f): f = x^d + a_(d-1) x^(d-1) + ... + a_0 is the first irreducible when the tuples
+ *   (a_(d-1), ..., a_0) are counted up as base-p numbers, a_0 the least significant digit, from 0.  gen is the first
+ *   element of multiplicative order p^d - 1 when the polynomials c_0 + c_1 x + ... are counted up as base-p numbers
+ *   c = sum c_i p^i from 1.  w = gen^((p^d - 1)/m').  Another root only permutes the set; the reference's own choice
+ *   (its table of irreducibles) is not reproduced, and nothing needs it: a TunnelHint message carries its function.
+ *   cap: rows of out (out = NULL or cap = 0 queries K); min(K, cap) rows are written.  Returns K, or LOLHIP_ERR_INVALID
+ *   for malformed lists, m not dividing m', p not prime or p | m'; LOLHIP_ERR_MODULUS when p^d >= 2^62.
+ * crtSet(m, m', p, e): the mod-p^e CRT set of O_m'/O_m in the powerful basis, [K][phi(m')] residues in [0, p^e).
+ *   mbar, mbar' = m, m' without their p-parts; c = crtSetDec(mbar, mbar', p) lifted to [0, p), taken to the powerful
+ *   basis (l), reduced mod p^e, raised to the p-th power e - 1 times with a reduction mod p^e after every product,
+ *   then embedPow from mbar' to m'.  The products are exact: each is computed over the integers.
+ *   lolhip_crtset_modulus: the smallest prime Q = 1 mod mbar' with C_mbar' floor(p^e/2)^2 < Q/2 (C: the growth constant
+ *     of the lifted PRF above), or LOLHIP_ERR_MODULUS when there is none below 2^61.
+ *   lolhip_crtset (device): pQ = a one-modulus device plan of index mbar' over such a Q (CRT basis required, the bound
+ *     is checked again).  Launch plan: upload, l on pQ, k_relift (reduce mod p^e, centred lift mod Q), then per power
+ *     p - 1 times lolhip_polymul_batch over the K elements and k_relift, a last k_relift to residues, the embedPow
+ *     gather.  out_dev [cap][phi(m')] on the device; min(K, cap) rows are written.  Setup-time: allocates and
+ *     synchronises the stream.
+ *   lolhip_crtset_host: the same set by schoolbook products on the host (no device, no Q; out is a host array): the
+ *     same bits.  Meant for tests and small indices (its cost is K e phi(mbar')^2).
+ *   All three return K, or: LOLHIP_ERR_INVALID as lolhip_crtset_dec, for e < 1, a plan of another index or of more
+ *   than one modulus; LOLHIP_ERR_MODULUS when p^e >= 2^62 or no Q below 2^61 certifies the products (the host path
+ *   reports it too), or pQ's modulus does not; LOLHIP_ERR_NO_CRT; LOLHIP_ERR_NO_DEVICE on a host-only plan.
+ * ptTunnel: evalLin f_h hop by hop on a plaintext over Z_(p^e), which has no CRT basis.  Hop h maps R_h to S_h = R_(h+1)
+ *   over E_h; x_er[h] / x_es[h]: the exts E_h in R_h / E_h in S_h, all three plans over ONE NTT prime Q_h (CRT basis
+ *   required for S_h).  funcs_pow[h]: HOST array [rel_h][n_S_h], rel_h = n_R_h / n_E_h, the values of f_h on the
+ *   relative decoding basis, any int64 taken mod p^e, powerful basis of S_h (the shape of TunnelChain.hints' funcs).
+ *   Create lifts them (centred) and uploads crt of them mod Q_h.  Per hop: coeffs gather, embedDec, l, crt, knapsack
+ *   (lolhip_evallin_batch over Q_h), crtInv, then k_relift: one pass that reads crtInv's output, takes the centred lift
+ *   mod Q_h, reduces mod p^e and writes the residues in [0, p^e) (the hop's result, powerful basis of S_h) and / or
+ *   their centred lift mod Q_(h+1); lInv on R_(h+1) then gives the next hop's decoding-basis input.
+ *   Exactness, certified at create: with H = floor(p^e/2), C_S the growth constant of S_h, G_S = prod (p_k - 1) over
+ *   the odd primes of S_h (l on lifted coefficients) and D_R = 2^(odd primes of R_h) for h > 0, 1 for h = 0 (lInv on
+ *   lifted coefficients),   rel_h C_S G_S D_R H^2 < Q_h / 2.   lolhip_pt_tunnel_modulus(R_h, S_h, rel_h, first_hop, p, e):
+ *   twice the left side (Q_h must exceed it; first_hop != 0: D_R = 1), or LOLHIP_ERR_MODULUS when that is not below 2^61.
+ *   lolhip_pt_tunnel_batch: x_dec [B][n_R0] any int64 (taken mod p^e), decoding basis of R_0 -> out_pow [B][n_S_last]
+ *   residues in [0, p^e), powerful basis.  nhops = 0 is not a tunnel: LOLHIP_ERR_INVALID.  work:
+ *   lolhip_pt_tunnel_work_len(c, B) int64 of device scratch, 16-byte aligned: two slabs of B n_max (rounded up to even;
+ *   n_max over R_0 and every S_h: a hop's input and output) + max_h rel_h B (n_E_h + n_S_h) (evalLin's scratch).  The call
+ *   does not allocate or synchronise.
+ *   Status: LOLHIP_ERR_INVALID for NULL pointers, nhops < 1 or > 16, e < 1, B < 0, exts of one hop over different
+ *   E-plans or moduli, plans of more than one modulus, S_h and R_(h+1) of different indices; LOLHIP_ERR_MODULUS for
+ *   p < 2, p^e >= 2^62 or a hop whose Q_h fails the bound; LOLHIP_ERR_NO_CRT for an S_h without a CRT basis;
+ *   LOLHIP_ERR_NO_DEVICE from the compute calls of a chain over host-only plans (create then validates only);
+ *   LOLHIP_ERR_DEVICE as elsewhere.  All decided on the host before any launch. */
+LOLHIP_API int64_t lolhip_crtset_dec(const lolhip_pp *pps_m, int npps_m, const lolhip_pp *pps_m2, int npps_m2, int64_t p,
+                                     int64_t *out, int64_t cap);
+LOLHIP_API int64_t lolhip_crtset_modulus(const lolhip_pp *pps_m2, int npps_m2, int64_t p, int e);
+LOLHIP_API int64_t lolhip_crtset_host(const lolhip_pp *pps_m, int npps_m, const lolhip_pp *pps_m2, int npps_m2, int64_t p,
+                                      int e, int64_t *out, int64_t cap);
+LOLHIP_API int64_t lolhip_crtset(const lolhip_plan *pQ, const lolhip_pp *pps_m, int npps_m, const lolhip_pp *pps_m2,
+                                 int npps_m2, int64_t p, int e, void *stream, int64_t *out_dev, int64_t cap);
+typedef struct lolhip_pt_tunnel lolhip_pt_tunnel;
+LOLHIP_API int64_t lolhip_pt_tunnel_modulus(const lolhip_pp *pps_r, int npps_r, const lolhip_pp *pps_s, int npps_s,
+                                            int64_t rel, int first_hop, int64_t p, int e);
+LOLHIP_API int lolhip_pt_tunnel_create(int nhops, const lolhip_ext *const *x_er, const lolhip_ext *const *x_es,
+                                       const int64_t *const *funcs_pow, int64_t p, int e, lolhip_pt_tunnel **out);
+LOLHIP_API void lolhip_pt_tunnel_destroy(lolhip_pt_tunnel *c);
+LOLHIP_API int64_t lolhip_pt_tunnel_work_len(const lolhip_pt_tunnel *c, int64_t B);
+LOLHIP_API int lolhip_pt_tunnel_batch(const lolhip_pt_tunnel *c, void *stream, const int64_t *x_dec, int64_t *out_pow,
+                                      int64_t *work, int64_t B);
 
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */

@@ -138,14 +138,15 @@ int run_pow2(const Plan& P, int mode, hipStream_t s, int64_t* y, const int64_t* 
 // ---- what the other host translation units call too (she_host.h) --------------------------------------------------
 namespace lolhip {
 
-int need_device(const lolhip_plan* p) {
-  if (!p) return LOLHIP_ERR_INVALID;
-  if (!p->P.device) return LOLHIP_ERR_NO_DEVICE;
+int need_device(const Plan& P) {
+  if (!P.device) return LOLHIP_ERR_NO_DEVICE;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (dev != p->P.device_id) return LOLHIP_ERR_DEVICE;     // the plan's tables live on another GPU
+  if (dev != P.device_id) return LOLHIP_ERR_DEVICE;        // the plan's tables live on another GPU
   return LOLHIP_OK;
 }
+
+int need_device(const lolhip_plan* p) { return p ? need_device(p->P) : LOLHIP_ERR_INVALID; }
 
 int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
   if (use_mixed(P, sp)) {
@@ -635,6 +636,7 @@ void lolhip_ext_destroy(lolhip_ext* x) {
 int64_t lolhip_ext_table(const lolhip_ext* x, int which, int32_t* out, int64_t len) {
   if (!x) return 0;
   const std::vector<int32_t>* src = nullptr;
+  std::vector<int32_t> pbp;
   switch (which) {
     case 0: src = &x->X.host.twace_powdec; break;
     case 1: src = &x->X.host.ext_crt; break;
@@ -642,6 +644,7 @@ int64_t lolhip_ext_table(const lolhip_ext* x, int which, int32_t* out, int64_t l
     case 3: src = &x->X.host.embed_dec; break;
     case 4: src = &x->X.host.embed_crt; break;
     case 5: src = &x->X.host.coeffs; break;
+    case 6: pbp = pow_basis_pow(x->X.host); src = &pbp; break;
     default: return 0;
   }
   const int64_t avail = (int64_t)src->size();

@@ -167,6 +167,31 @@ std::vector<u64> g_crt(const std::vector<PP>& pps, const std::vector<u64>& omega
   return out;
 }
 
+// C_m = max_k sum_{i,j} |(b_i b_j)_k| over the powerful basis b: a product over the prime powers p^e of m.  The powerful
+// basis of p^e is {z^j : j < phi}, z^t = z^(t mod p^e), and z^(phi + r) = -sum_{l < p - 1} z^(l p^(e-1) + r) for
+// r < p^(e-1): each t = i + j (mult(t) = min(t, 2 phi - 2 - t) + 1 pairs) adds mult(t) to one or to p - 1 coefficients.
+// Saturates at 2^62.
+u64 growth(const std::vector<PP>& pps) {
+  const u64 cap = (u64)1 << 62;
+  u64 C = 1;
+  for (const PP& pe : pps) {
+    i64 pk = 1;
+    for (int e = 0; e < pe.e; ++e) pk *= pe.p;
+    const i64 pk1 = pk / pe.p, phi = pk - pk1;
+    std::vector<u64> acc((size_t)phi, 0);
+    for (i64 t = 0; t <= 2 * phi - 2; ++t) {
+      const u64 mult = (u64)(std::min(t, 2 * phi - 2 - t) + 1);
+      const i64 tt = t % pk;
+      if (tt < phi) { acc[(size_t)tt] += mult; continue; }
+      const i64 r = tt - phi;
+      for (i64 l = 0; l + 1 < pe.p; ++l) acc[(size_t)(l * pk1 + r)] += mult;
+    }
+    const u64 c = *std::max_element(acc.begin(), acc.end());
+    C = (unsigned __int128)C * c >= cap ? cap : C * c;
+  }
+  return C;
+}
+
 bool merge_pps(const std::vector<PP>& pps, const std::vector<PP>& pps2, std::vector<MergedPP>& out) {
   out.clear();
   size_t a = 0;
@@ -246,6 +271,12 @@ bool build_ext_tables(const std::vector<PP>& pps, const std::vector<PP>& pps2, E
     X.embed_dec[(size_t)i2] = none ? -1 : (int32_t)(idx | (neg ? EMBED_NEG_FLAG : 0));
   }
   return true;
+}
+
+std::vector<int32_t> pow_basis_pow(const ExtTables& X) {
+  std::vector<int32_t> out;
+  for (i64 i1 = 0; i1 * X.phi < X.phi2; ++i1) out.push_back(X.coeffs[(size_t)(i1 * X.phi)]);
+  return out;
 }
 
 }  // namespace lolhip

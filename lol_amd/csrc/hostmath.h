@@ -7,6 +7,8 @@
 //   ru / ruInv                               lol-cpp/Crypto/Lol/Cyclotomic/Tensor/CPP.hs:422-442
 //   gCRTK / gInvCRTK                         lol/Crypto/Lol/Cyclotomic/Tensor.hs:290-337
 //   index tables for twace/embed             lol/Crypto/Lol/Cyclotomic/Tensor.hs:390-509
+//   powBasisPow                              lol-cpp/Crypto/Lol/Cyclotomic/Tensor/CPP/Extension.hs:131-141
+// (crtSetDec / crtSet: crtset.h)
 #pragma once
 #include <cstdint>
 #include <utility>
@@ -48,6 +50,10 @@ u64 principal_root(u64 m, u64 q);
 // omega_p[k] = primitive p_k-th root of unity to use (p_k = pps[k].p)
 std::vector<u64> g_crt(const std::vector<PP>& pps, const std::vector<u64>& omega_p, u64 q, bool inverse);
 
+// C_m = max_k sum_{i,j} |(b_i b_j)_k| over the powerful basis b of index m: a product of two ring elements whose
+// powerful-basis coefficients are bounded by A and B has coefficients bounded by C_m A B.  Saturates at 2^62.
+u64 growth(const std::vector<PP>& pps);
+
 // ---- ring-extension index tables (m | m') --------------------------------
 struct MergedPP { int p, e, e2; };
 // false if pps does not divide pps2
@@ -66,5 +72,7 @@ struct ExtTables {
 };
 static const int32_t EMBED_NEG_FLAG = 1 << 30;
 bool build_ext_tables(const std::vector<PP>& pps, const std::vector<PP>& pps2, ExtTables& out);
+// powBasisPow (CPP/Extension.hs:131-141): the n'/n powerful-basis indices of the relative powerful basis
+std::vector<int32_t> pow_basis_pow(const ExtTables& X);
 
 }  // namespace lolhip

@@ -259,31 +259,6 @@ int upload_lifted(lolhip_khprf* f, const std::vector<int64_t>& a) {
   return rc;
 }
 
-// C_m = max_k sum_{i,j} |(b_i b_j)_k| over the powerful basis b: a product over the prime powers p^e of m.  The powerful
-// basis of p^e is {z^j : j < phi}, z^t = z^(t mod p^e), and z^(phi + r) = -sum_{l < p - 1} z^(l p^(e-1) + r) for
-// r < p^(e-1): each t = i + j (mult(t) = min(t, 2 phi - 2 - t) + 1 pairs) adds mult(t) to one or to p - 1 coefficients.
-// Saturates at 2^62.
-u64 growth(const std::vector<PP>& pps) {
-  const u64 cap = (u64)1 << 62;
-  u64 C = 1;
-  for (const PP& pe : pps) {
-    int64_t pk = 1;
-    for (int e = 0; e < pe.e; ++e) pk *= pe.p;
-    const int64_t pk1 = pk / pe.p, phi = pk - pk1;
-    std::vector<u64> acc((size_t)phi, 0);
-    for (int64_t t = 0; t <= 2 * phi - 2; ++t) {
-      const u64 mult = (u64)(std::min(t, 2 * phi - 2 - t) + 1);
-      const int64_t tt = t % pk;
-      if (tt < phi) { acc[(size_t)tt] += mult; continue; }
-      const int64_t r = tt - phi;
-      for (int64_t l = 0; l + 1 < pe.p; ++l) acc[(size_t)(l * pk1 + r)] += mult;
-    }
-    const u64 c = *std::max_element(acc.begin(), acc.end());
-    C = (unsigned __int128)C * c >= cap ? cap : C * c;
-  }
-  return C;
-}
-
 // the largest |digit| of decompose over lift_q: remainders in [-b/2, b/2), the last digit f^(k-1)(v) for v in
 // [-q/2, q/2) with f v = floor((v + b/2) / b) monotone; TrivGad: q/2
 u64 max_digit(u64 q, int64_t base, int k) {

@@ -19,6 +19,7 @@ namespace lolhip {
 // ---- defined in capi.cpp -----------------------------------------------------------------------------------------
 // LOLHIP_OK, or why the plan cannot compute on the calling thread's current device
 int need_device(const lolhip_plan* p);
+int need_device(const Plan& P);
 // y = program(src or y) over B polynomials (the vector interpreter or the scalar one)
 int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src = nullptr);
 // crt / crtInv of B polynomials in place, through whichever path the plan has

@@ -149,6 +149,19 @@ def lib():
     L.lolhip_ptround_work_len.argtypes = [vp, i64]
     L.lolhip_ptround_work_len.restype = i64
     L.lolhip_ptround_batch.argtypes = [vp, vp, vp, ci, ci, i64, i64, vp, ci, _i64p, _i64p, vp, i64]
+    L.lolhip_crtset_dec.argtypes = [pp, ci, pp, ci, i64, _i64p, i64]
+    L.lolhip_crtset_modulus.argtypes = [pp, ci, i64, ci]
+    L.lolhip_crtset_host.argtypes = [pp, ci, pp, ci, i64, ci, _i64p, i64]
+    L.lolhip_crtset.argtypes = [vp, pp, ci, pp, ci, i64, ci, vp, vp, i64]
+    L.lolhip_pt_tunnel_modulus.argtypes = [pp, ci, pp, ci, i64, ci, i64, ci]
+    for nm in ("crtset_dec", "crtset_modulus", "crtset_host", "crtset", "pt_tunnel_modulus"):
+        getattr(L, f"lolhip_{nm}").restype = i64
+    L.lolhip_pt_tunnel_create.argtypes = [ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(_i64p), i64, ci, C.POINTER(vp)]
+    L.lolhip_pt_tunnel_destroy.argtypes = [vp]
+    L.lolhip_pt_tunnel_destroy.restype = None
+    L.lolhip_pt_tunnel_work_len.argtypes = [vp, i64]
+    L.lolhip_pt_tunnel_work_len.restype = i64
+    L.lolhip_pt_tunnel_batch.argtypes = [vp, vp, vp, vp, vp, i64]
     L.lolhip_gsqnorm_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_gsqnorm_f64_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_rlwe_work_len.argtypes = [vp, ci, i64]
@@ -244,6 +257,61 @@ def factor_pps(m: int):
         if p * p > m and m > 1:
             out.append((m, 1))
             break
+    return out
+
+
+def _pps(x):
+    """a prime-power list [(p, e)] (or an index m) as ([(p, e)], the ctypes array, its length)"""
+    pps = factor_pps(int(x)) if isinstance(x, (int, np.integer)) else [(int(p), int(e)) for p, e in x]
+    arr = (_PP * max(1, len(pps)))()
+    for i, (p, e) in enumerate(pps):
+        arr[i].prime, arr[i].exponent = p, e
+    return pps, arr, len(pps)
+
+
+def _totient(pps):
+    n = 1
+    for p, e in pps:
+        n *= (p - 1) * p ** (e - 1)
+    return n
+
+
+def crtSetDec(pps_m, pps_m2, p):
+    """crtSetDec (CPP/Extension.hs:143-164) on the host: the mod-p CRT set of O_m'/O_m as [K][phi(m')] residues in
+    [0, p), decoding basis of O_m'.  pps_m, pps_m2: prime-power lists [(p, e)] or the indices themselves; p: a prime
+    that does not divide m'.  Order and root of unity: include/lolhip.h."""
+    (_, a, na), (pps2, b, nb) = _pps(pps_m), _pps(pps_m2)
+    L = lib()
+    K = L.lolhip_crtset_dec(a, na, b, nb, int(p), None, 0)
+    _check(min(K, 0), f"crtSetDec(p={p})")
+    out = np.zeros((K, _totient(pps2)), dtype=np.int64)
+    _check(min(L.lolhip_crtset_dec(a, na, b, nb, int(p), out.ctypes.data_as(_i64p), K), 0), f"crtSetDec(p={p})")
+    return out
+
+
+def crtSet(pps_m, pps_m2, p, e, host=False, stream=None):
+    """crtSet (UCyc.hs:540-565): the mod-p^e CRT set of O_m'/O_m as [K][phi(m')] residues in [0, p^e), powerful basis
+    of O_m'.  On the device (a CUDA tensor; lolhip_crtset over a plan of the p-free part of m' mod the NTT prime of
+    lolhip_crtset_modulus), or with host=True by schoolbook products on the host (numpy; small indices)."""
+    (_, a, na), (pps2, b, nb) = _pps(pps_m), _pps(pps_m2)
+    L, n2 = lib(), _totient(pps2)
+    if host:
+        K = L.lolhip_crtset_host(a, na, b, nb, int(p), int(e), None, 0)
+        _check(min(K, 0), f"crtSet(p={p}, e={e})")
+        out = np.zeros((K, n2), dtype=np.int64)
+        _check(min(L.lolhip_crtset_host(a, na, b, nb, int(p), int(e), out.ctypes.data_as(_i64p), K), 0), "crtSet")
+        return out
+    import torch
+    if all(q[0] == int(p) for q in pps2):
+        # m' is a power of p: its p-free part is the index 1, the set is {1}; nothing to run on the device
+        return torch.from_numpy(crtSet(pps_m, pps_m2, p, e, host=True)).cuda()
+    Q = L.lolhip_crtset_modulus(b, nb, int(p), int(e))
+    _check(min(Q, 0), f"crtSet(p={p}, e={e})")
+    plan = Plan([q for q in pps2 if q[0] != int(p)], [Q])
+    K = L.lolhip_crtset(plan._h, a, na, b, nb, int(p), int(e), None, None, 0)          # the statuses and the count
+    _check(min(K, 0), f"crtSet(p={p}, e={e})")
+    out = torch.empty((K, n2), dtype=torch.int64, device="cuda")
+    _check(min(L.lolhip_crtset(plan._h, a, na, b, nb, int(p), int(e), _stream(stream), _devptr(out), K), 0), "crtSet")
     return out
 
 
@@ -1076,6 +1144,11 @@ class Ext:
             L.lolhip_ext_table(self._h, which, out.ctypes.data_as(_i32p), cnt)
         return out
 
+    def powBasisPow(self):
+        """powBasisPow (CPP/Extension.hs:131-141): the n'/n powerful-basis indices at which the relative powerful basis
+        elements of O_m'/O_m are unit vectors; sum_i embedPow(coeffs_i x) b_i = x."""
+        return self.table(6)
+
     def _run(self, op, name, x, to_hi, out, stream):
         src, dst = (self.lo, self.hi) if to_hi else (self.hi, self.lo)
         if isinstance(x, np.ndarray):
@@ -1240,6 +1313,102 @@ class TunnelChain:
             ctr += rel * L
             s_in = s_out.reshape(S.n, S.T)
         return out_h, out_y, s_in, ctr
+
+
+    @staticmethod
+    def funcs(rings, p, e, host=False, stream=None):
+        """The linear functions of tunnelHintChain / ptTunnelFuncs (HomomPRF.hs:400-411, 516-531) for the plaintext rings
+        rings = [r_0, ..., r_H] (indices): per hop h, with e_h = gcd(r_h, r_(h+1)) and dim_h = phi(r_h) / phi(e_h), the
+        first dim_h elements of crtSet(e_h, r_(h+1), p, e) as [dim_h][n_S_h] residues mod p^e, powerful basis: the values
+        of f_h on the relative decoding basis, the `funcs` of TunnelChain.hints and PTTunnel.  CUDA tensors, or numpy
+        with host=True (crtSet's host path).  ValueError when a hop's CRT set has fewer than dim_h elements."""
+        import math
+        out = []
+        for r, s_ in zip(rings[:-1], rings[1:]):
+            eh = math.gcd(int(r), int(s_))
+            dim = _totient(factor_pps(int(r))) // _totient(factor_pps(eh))
+            cs = crtSet(eh, int(s_), p, e, host=host, stream=stream)
+            if cs.shape[0] < dim:
+                raise ValueError(f"the CRT set of O_{s_}/O_{eh} mod {p} has {cs.shape[0]} elements, the hop from {r} needs {dim}")
+            out.append(cs[:dim].copy() if host else cs[:dim].contiguous())
+        return out
+
+
+class PTTunnel:
+    """ptTunnel (HomomPRF.hs:510-531): evalLin f_h hop by hop on plaintexts over Z_(p^e) as one call
+    (lolhip_pt_tunnel_batch).  exts_er[h] / exts_es[h]: the Exts E_h in R_h / E_h in S_h over ONE NTT prime Q_h per hop
+    that exceeds PTTunnel.modulus (certified at creation); funcs[h] [rel_h][n_S_h]: the values of f_h on the relative
+    decoding basis, residues mod p^e in the powerful basis (TunnelChain.funcs; numpy or CUDA tensors)."""
+
+    def __init__(self, exts_er, exts_es, funcs, p, e):
+        self.exts_er, self.exts_es, self.p, self.e = list(exts_er), list(exts_es), int(p), int(e)
+        n = len(self.exts_er)
+        if not (len(self.exts_es) == len(funcs) == n):
+            raise ValueError("one ext pair and one function table per hop")
+        fs = []
+        for x, f in zip(self.exts_er, funcs):
+            f = np.ascontiguousarray(f if isinstance(f, np.ndarray) else f.cpu().numpy(), dtype=np.int64)
+            if f.size != (x.hi.n // x.lo.n) * self.exts_es[len(fs)].hi.n:
+                raise ValueError("funcs[h] must be [n_R/n_E][n_S]")
+            fs.append(f)
+        arr = lambda vals: (C.c_void_p * max(n, 1))(*vals)
+        fp = (_i64p * max(n, 1))(*[f.ctypes.data_as(_i64p) for f in fs])
+        h = C.c_void_p()
+        _check(lib().lolhip_pt_tunnel_create(n, arr([x._h for x in self.exts_er]), arr([x._h for x in self.exts_es]), fp,
+                                             self.p, self.e, C.byref(h)), "pt_tunnel_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.lolhip_pt_tunnel_destroy(h)
+
+    @staticmethod
+    def modulus(pps_r, pps_s, rel, first_hop, p, e):
+        """The exactness bound of one hop (include/lolhip.h): the hop's prime Q must exceed the returned value."""
+        (_, a, na), (_, b, nb) = _pps(pps_r), _pps(pps_s)
+        v = lib().lolhip_pt_tunnel_modulus(a, na, b, nb, int(rel), int(bool(first_hop)), int(p), int(e))
+        _check(min(v, 0), "pt_tunnel_modulus")
+        return int(v)
+
+    @classmethod
+    def for_rings(cls, rings, p, e, funcs=None, host_only=False):
+        """The tunnel over the plaintext rings [r_0, ..., r_H] with the functions of TunnelChain.funcs (or `funcs`): per
+        hop the plans of E_h = gcd, R_h and S_h over the smallest admissible prime Q_h = 1 mod r_(h+1)."""
+        import math
+        if funcs is None:
+            funcs = TunnelChain.funcs(rings, p, e, host=host_only)
+        er, es = [], []
+        for h, (r, s_) in enumerate(zip(rings[:-1], rings[1:])):
+            eh = math.gcd(int(r), int(s_))
+            rel = _totient(factor_pps(int(r))) // _totient(factor_pps(eh))
+            Q = good_q(int(s_), cls.modulus(int(r), int(s_), rel, h == 0, p, e))
+            E, R, S = (Plan.for_index(m, [Q], host_only=host_only) for m in (eh, int(r), int(s_)))
+            er.append(Ext(E, R))
+            es.append(Ext(E, S))
+        return cls(er, es, funcs, p, e)
+
+    def workLen(self, B):
+        w = lib().lolhip_pt_tunnel_work_len(self._h, int(B))
+        _check(min(w, 0))
+        return w
+
+    def __call__(self, x_dec, stream=None):
+        """x_dec [B][n_R0]: plaintexts mod p^e in the decoding basis of R_0 (numpy or a CUDA tensor) -> [B][n_S] residues
+        in [0, p^e), powerful basis of the last ring."""
+        import torch
+        L = lib()
+        _check(L.lolhip_pt_tunnel_batch(self._h, None, None, None, None, 0))          # the host statuses first
+        host = isinstance(x_dec, np.ndarray)
+        x = torch.from_numpy(np.ascontiguousarray(x_dec, dtype=np.int64)).cuda() if host else x_dec
+        nR, nS = self.exts_er[0].hi.n, self.exts_es[-1].hi.n
+        if x.numel() % nR:
+            raise ValueError("x_dec is not a whole number of plaintexts of R_0")
+        B = x.numel() // nR
+        work = torch.empty((max(self.workLen(B), 2),), dtype=torch.int64, device=x.device)
+        out = torch.empty((B, nS), dtype=torch.int64, device=x.device)
+        _check(L.lolhip_pt_tunnel_batch(self._h, _stream(stream), _devptr(x), _devptr(out), _devptr(work), B))
+        return out.cpu().numpy() if host else out
 
 
 class PTRound:
