@@ -165,7 +165,7 @@ k_keyswitch(const i64* __restrict__ c2, const i64* __restrict__ hint, const i64*
         r = csub32(r, qk.q);
         v[e] = (d < 0 && r != 0) ? qk.q - r : r;
       }
-      fwd_transform<AR, L, LIO, 10, true>(v, lds, tw, tau, qk);
+      fwd_transform<AR, L, LIO, true>(v, lds, tw, tau, qk);
       const u32 hoff = (u32)j * (u32)K * hstride;
 #pragma unroll
       for (int e = 0; e < E; ++e) {

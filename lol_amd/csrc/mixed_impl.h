@@ -32,9 +32,7 @@
 
 namespace lolhip {
 
-#ifndef LOLHIP_MIXED_W2
-#define LOLHIP_MIXED_W2 6      // waves/SIMD bound of the 32-bit single-program kernel (A/B with the 32-bit pool: 6 beats 8, which spills to scratch)
-#endif
+constexpr int MIXED_W2 = 6;    // waves/SIMD bound of the 32-bit single-program kernel (measured with the 32-bit pool: 6 beats 8, which spills to scratch)
 // coefficients a thread loads/stores: ppw * n <= KMAX * blockDim, KMAX in {12, 16} picked by the launcher
 // (m = 15015: 5760 / 512 = 11.25 -> 12: a quarter fewer predicated load/store/convert slots than 16)
 
@@ -42,13 +40,7 @@ template <int CLS> using MV = std::conditional_t<CLS == 0 || CLS == 3, u64, u32>
 template <int CLS> constexpr bool wide() { return CLS == 0 || CLS == 3; }
 // element type of the constant pool the kernel reads: the 32-bit classes get a 32-bit copy (half the
 // scalar-load bytes and SGPRs of a matrix row, half the bytes of a per-lane twiddle load)
-#ifndef LOLHIP_MIXED_HOIST0
-#define LOLHIP_MIXED_HOIST0 0     // hoisted dispatch in the single-program kernels too (A/B)
-#endif
-#ifndef LOLHIP_MIXED_POOL32
-#define LOLHIP_MIXED_POOL32 1
-#endif
-template <int CLS> using PT = std::conditional_t<(CLS == 1 || CLS == 2 || CLS == 4) && LOLHIP_MIXED_POOL32, u32, u64>;
+template <int CLS> using PT = std::conditional_t<CLS == 1 || CLS == 2 || CLS == 4, u32, u64>;
 // CLS 4 = class 2 for moduli below 2^27 with LAZY dense stages: a dot product of up to 16 terms of values below 2q has
 // T / 2^32 < q, so the Montgomery step's result h + ceil(m q / 2^32) is below 2q as it stands — 3 instructions instead
 // of the 9 of redc64 (no pre-subtraction, no canonicalising min-subtractions).  Values in [0, 2q) travel between dense
@@ -250,9 +242,7 @@ __device__ __forceinline__ void apply_kind(const Stage& st, const MV<CLS> (&v)[D
     case ST_DFTP:
     case ST_CRTP:
     case ST_CRTPINV: {
-#ifndef LH_NO_EO
       if constexpr (CLS == 3 && D >= 3 && D <= 13) { apply_eo<D>(st, v, o, cst, mc); break; }      // every class-3 plan carries the tables (plan.cpp finish)
-#endif
       const PT<CLS>* M = cst + st.mat_off;
 #pragma unroll
       for (int i = 0; i < D; ++i) o[i] = m_dot<CLS, D>(v, M + i * D, mc);
@@ -545,15 +535,8 @@ __device__ __forceinline__ void run_stages(MV<CLS>* __restrict__ buf, int tot, i
 #define LOLHIP_TILES(X) X(2, 1, false) X(3, 1, true) X(4, 2, false) X(5, 2, true) X(6, 3, false) X(7, 3, true) X(8, 4, false) X(9, 4, true)
 #define LOLHIP_VECS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(10) X(11) X(12) X(13)
 #define LOLHIP_VECS8(X) X(8) X(9)                                // BIG kernels only: 3 (x) 5 as one stage (plan.cpp merge_stages<true>)
-#ifdef LH_NO_VL
-#define LOLHIP_VECSL(X)
-#else
 #define LOLHIP_VECSL(X) X(18) X(20)                           // class 2 only: merged prime powers 3^3, 5^2
-#endif
   for (int s = 0; s < nstages; ++s) {
-#ifdef LH_ABL_SKIP_STAGES        // timing-only ablation: bit s set = stage s of every program is skipped (results garbage)
-    if ((LH_ABL_SKIP_STAGES >> s) & 1) continue;
-#endif
     const Stage st = stages[s];
     if (st.kind == ST_DIAG || st.kind == ST_SCALE) {
       for (int x = threadIdx.x; x < tot; x += blockDim.x) {
@@ -640,14 +623,14 @@ template <int CLS> __device__ __forceinline__ MV<CLS> from_raw(i64 x, u64 q) {
 // poly-mul keeps a-hat and b's loads live and gets 128 (4 waves/SIMD), as does the 64-bit class
 // (at 80 it spills: measured slower).
 template <int CLS, int MODE, int KMAX, bool BIG = false>
-__global__ void __launch_bounds__(512, (MODE == 0 && (CLS == 2 || CLS == 4)) ? LOLHIP_MIXED_W2 : (MODE == 0 && CLS == 1) ? 6 : 4)
+__global__ void __launch_bounds__(512, (MODE == 0 && (CLS == 2 || CLS == 4)) ? MIXED_W2 : (MODE == 0 && CLS == 1) ? 6 : 4)
 k_mixed(i64* y_out, const i64* a_in, const i64* b_in, i64 B, int T, int n, int ppw, i64 ngroups,
         const Stage* __restrict__ st_a, int n_a, const Stage* __restrict__ st_b, int n_b,
         const u64* __restrict__ consts64, const u32* __restrict__ consts32, int cpc, const ModCtx* __restrict__ mod) {
   using V = MV<CLS>;
   // hoisted dispatch (run_stages): the fused poly-mul of the 32-bit classes only — in the 64-bit classes it measured
   // no gain (m = 15015, 61 bits: 0.324 vs 0.320 ms)
-  constexpr bool HOISTED = ((MODE == 2 && !wide<CLS>()) || LOLHIP_MIXED_HOIST0) && !BIG;
+  constexpr bool HOISTED = (MODE == 2 && !wide<CLS>()) && !BIG;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   V* buf = reinterpret_cast<V*>(smem);
   const u64 n_magic = (((u64)1 << 40) / (u64)n) + 1;

@@ -42,20 +42,8 @@ namespace lolhip {
 constexpr int R = 4;
 constexpr int E = 1 << R;
 // levels whose eight twiddles are all distinct are fetched and consumed in this many parts
-// (2 or 4) in the register-lean schedule: 16 or 8 twiddle VGPRs live instead of 32
-#ifndef LOLHIP_LEVEL_PARTS
-#define LOLHIP_LEVEL_PARTS 4
-#endif
-
-// Diagnostic build (-DLOLHIP_STAMPS): per-wave s_memtime stamps at phase boundaries, written
-// to a side buffer nobody else reads.  Never enabled in the shipped library.
-#ifdef LOLHIP_STAMPS
-static __device__ unsigned long long* g_stamp_buf = nullptr;   // per translation unit (development builds only)
-#define LH_STAMP(i) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-    if (g_stamp_buf && (threadIdx.x & 63) == 0) g_stamp_buf[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32 + (i)] = t_; } while (0)
-#else
-#define LH_STAMP(i) do {} while (0)
-#endif
+// in the register-lean schedule: 8 twiddle VGPRs live instead of 32
+constexpr int LEVEL_PARTS = 4;
 
 struct Lay {
   int reg[R];     // position bit held by register-index bit k
@@ -198,49 +186,6 @@ __device__ __forceinline__ u32 csub32(u32 x, u32 m) { return min(x, x - m); }   
 // w*y mod q in [0,2q) for any 32-bit y
 __device__ __forceinline__ u32 shoup32(u32 y, u32 w, u32 wp, u32 q) { return w * y - __umulhi(wp, y) * q; }
 
-// ---- pair/mad form of the 32-bit lazy butterflies (LOLHIP_PAIR_BFLY: pow2_pipe.hip only) -----------------------
-// A residue sits in the LOW half of a 64-bit register pair (the high half is never read), so v_mad_u64_u32 does the
-// multiply AND the add: x + w y - Q q as two chained mads (nq = -q mod 2^32), 2x + 2q - X' as a mad by -1.  Forward 5
-// instructions instead of 7, inverse 7 instead of 9; the same values mod 2^32 as the 32-bit forms below, so the same
-// lazy ranges.  Twice the data registers: for the persistent kernel (4 waves per SIMD), not the 8-wave ones.
-// tools/microbench_bfly32.hip: -13 % / -6 % per butterfly, exact.
-#ifndef LOLHIP_PAIR_BFLY
-#define LOLHIP_PAIR_BFLY 0
-#endif
-__device__ __forceinline__ u64 pair_of(u32 lo) { typedef u32 u32p __attribute__((ext_vector_type(2))); u32p t; t.x = lo; return __builtin_bit_cast(u64, t); }
-// X' = x + w Y - Q q,  Y' = 2x + 2q - X'   (x, Y any 32-bit values)
-template <bool WS>
-__device__ __forceinline__ void fwd_pair(u32& X, u32& Y, u32 x, u32 w, u32 wp, u32 q, u32 q2) {
-  const u64 xp = pair_of(x), q2p = (u64)q2;
-  const u32 nq = 0u - q;
-  u64 Xn, Z, Yn, cy; u32 Q;
-#define LH_FWD_PAIR(WC)                                                                                     \
-  asm("v_mul_hi_u32 %[Q], %[wp], %[yl]\n\t"                                                                  \
-      "v_mad_u64_u32 %[Xn], %[cy], %[w], %[yl], %[X]\n\t"                                                    \
-      "v_lshl_add_u64 %[Z], %[X], 1, %[q2]\n\t"                                                              \
-      "v_mad_u64_u32 %[Xn], %[cy], %[Q], %[nq], %[Xn]"                                                        \
-      : [Q] "=&v"(Q), [Xn] "=&v"(Xn), [Z] "=&v"(Z), [cy] "=&s"(cy)                                            \
-      : [wp] WC(wp), [yl] "v"(Y), [w] WC(w), [X] "v"(xp), [q2] "s"(q2p), [nq] "s"(nq))
-  if constexpr (WS) { LH_FWD_PAIR("s"); } else { LH_FWD_PAIR("v"); }
-#undef LH_FWD_PAIR
-  asm("v_mad_u64_u32 %[Yn], %[cy], %[xl], -1, %[Z]" : [Yn] "=v"(Yn), [cy] "=s"(cy) : [xl] "v"((u32)Xn), [Z] "v"(Z));
-  X = (u32)Xn; Y = (u32)Yn;
-}
-// w d - Q q for any 32-bit d
-template <bool WS>
-__device__ __forceinline__ u32 shoup_pair(u32 d, u32 w, u32 wp, u32 q) {
-  const u32 nq = 0u - q;
-  const u32 Q = __umulhi(wp, d);
-  u64 T, Yn, cy;
-#define LH_SH_PAIR(WC)                                                                                      \
-  asm("v_mad_u64_u32 %[T], %[cy], %[w], %[d], 0\n\t"                                                         \
-      "v_mad_u64_u32 %[Yn], %[cy], %[Q], %[nq], %[T]"                                                         \
-      : [T] "=&v"(T), [Yn] "=&v"(Yn), [cy] "=&s"(cy) : [w] WC(w), [d] "v"(d), [Q] "v"(Q), [nq] "s"(nq))
-  if constexpr (WS) { LH_SH_PAIR("s"); } else { LH_SH_PAIR("v"); }
-#undef LH_SH_PAIR
-  return (u32)Yn;
-}
-
 // forward (Cooley-Tukey) butterfly:  X' = X + w*Y,  Y' = X - w*Y
 // WS: the twiddle is wave-uniform (SGPR operands in the 64-bit class's multiply chains, zq_dev.h)
 // L1: level 1 of the 64-bit class, whose X arrives in (0,2q) from from_i64_fwd: no conditional subtraction
@@ -253,32 +198,19 @@ __device__ __forceinline__ void bfly_fwd(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
     Y = x - t + k.q;                                  // (0,2q)
   } else if constexpr (AR == 2) {
     const u32 x = csub32(X, k.q2);                    // [0,4q) -> [0,2q)
-#if LOLHIP_PAIR_BFLY
-    fwd_pair<WS>(X, Y, x, w, wp, k.q, k.q2);
-#else
     const u32 t = shoup32(Y, w, wp, k.q);
     X = x + t;
     Y = x - t + k.q2;
-#endif
   } else if constexpr (AR == 4) {
-#if LOLHIP_PAIR_BFLY
-    fwd_pair<WS>(X, Y, X, w, wp, k.q, k.q2);
-#else
     const u32 t = shoup32(Y, w, wp, k.q);             // [0,2q) for ANY 32-bit Y
     const u32 x = X;                                  // < B: both outputs < B + 2q, never wrapping below 29 q
     X = x + t;
     Y = x - t + k.q2;
-#endif
   } else if constexpr (AR == 1) {
-#ifdef LH_ABL_NO_FWD_CSUB
-    const u64 x = X;                                  // timing-only ablation: results are garbage
-    const u64 xn = shoup_acc<WS>(Y, w, wp, k.nq, x);
-#else
     u64 x = X, xn;
     if constexpr (L1) xn = shoup_acc<WS>(Y, w, wp, k.nq, x);    // x + t, t in [0,4q)
     else if constexpr (trim_exec<decltype(k)>) xn = shoup_acc_csubx<WS, true>(Y, w, wp, k.nq, x, k.q4, k.nq4);   // the trim rides in the product's first block
     else { x = csubn(X, k.nq4); xn = shoup_acc<WS>(Y, w, wp, k.nq, x); }                     // [0,8q) -> [0,4q)
-#endif
     const u64 z = shl1_add64u(x, k.q4);                // 2x + 4q
     X = xn;
     Y = z - xn;                                       // x - t + 4q
@@ -301,11 +233,7 @@ __device__ __forceinline__ void bfly_inv(VT<AR>& X, VT<AR>& Y, VT<AR> w, VT<AR> 
     const u32 s = X + Y;
     const u32 d = X - Y + k.q2;
     X = csub32(s, k.q2);
-#if LOLHIP_PAIR_BFLY
-    Y = shoup_pair<WS>(d, w, wp, k.q);
-#else
     Y = shoup32(d, w, wp, k.q);
-#endif
   } else if constexpr (AR == 1) {
     const u64 s = add64(X, Y);                        // [0,8q)
     const u64 d = add64u(X, k.q4) - Y;                 // (0,8q)
@@ -403,9 +331,6 @@ template <int AR> __device__ __forceinline__ VT<AR> pmul(VT<AR> a, VT<AR> b, con
     if constexpr (AR == 3) return csub32(t, k.q);      // this class's inverse takes canonical values
     else return t;                                     // [0,2q): the inverse's lazy range
   } else if constexpr (AR == 1) {
-#ifdef LOLHIP_ABL_PMUL      // ablation: what the pointwise product costs (0.028 of 0.52 ms with the exact division)
-    return a + b;
-#endif
     // a < 2q, b < 8q, q < 2^61: T = a b < 16 q^2 < 2^126.  Montgomery: m = T (-q^-1) mod 2^64;
     // (T + m q) / 2^64 = hi(T) + hi(m q) + [lo(T) != 0]  <  16 q^2 / 2^64 + q + 1 < 3q + 1: inside the inverse's
     // lazy range [0,4q) as it stands.  The factor 2^-64 is taken back by the last inverse level, whose
@@ -435,26 +360,17 @@ __device__ __forceinline__ void load_tw(rsrc_t tw, u32 voff, u32 const_idx, u32&
   wp = r.y;
 }
 __device__ __forceinline__ u64 load_u64(rsrc_t r, u32 voff, u32 soff) {
-#ifdef LOLHIP_ABL_NO_IO       // ablation: compute-only timing, results are garbage
-  return (u64)voff * 0x9E3779B97F4A7C15ull + soff;
-#endif
   const u32x2 x = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
   return ((u64)x.y << 32) | x.x;
 }
 __device__ __forceinline__ void store_u64(rsrc_t r, u32 voff, u32 soff, u64 val) {
   u32x2 x;
   x.x = (u32)val; x.y = (u32)(val >> 32);
-#ifdef LOLHIP_ABL_NO_IO
-  if (val != 0x1234567ull) return;
-#endif
   __builtin_amdgcn_raw_buffer_store_b64(x, r, voff, soff, 0);
 }
 
 // 16 bytes per lane: coefficients x, x+1 of a single-modulus slab
 __device__ __forceinline__ void load_u64x2(rsrc_t r, u32 voff, u32 soff, u64& x0, u64& x1) {
-#ifdef LOLHIP_ABL_NO_IO
-  x0 = (u64)voff * 0x9E3779B97F4A7C15ull + soff; x1 = x0 ^ soff; return;
-#endif
   const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
   x0 = ((u64)x.y << 32) | x.x;
   x1 = ((u64)x.w << 32) | x.z;
@@ -467,9 +383,6 @@ __device__ __forceinline__ void load_u64x2(rsrc_t r, u32 voff, u32 soff, u64& x0
 __device__ __forceinline__ void store_u64x2(rsrc_t r, u32 voff, u32 coff, u64 x0, u64 x1) {
   u32x4 x;
   x.x = (u32)x0; x.y = (u32)(x0 >> 32); x.z = (u32)x1; x.w = (u32)(x1 >> 32);
-#ifdef LOLHIP_ABL_NO_IO
-  if (x0 != 0x1234567ull) return;
-#endif
   __builtin_amdgcn_raw_buffer_store_b128(x, r, voff + coff, 0, 0);
 }
 // whole-polynomial register I/O in layout A; element stride `ebytes` (= 8 T).  Layouts whose
@@ -563,18 +476,13 @@ template <typename V> struct LevelTwT { V w[8], wp[8]; };
 template <bool INV, Lay A, int K, int HALF = -1, typename V>
 __device__ __forceinline__ void tw_fetch(LevelTwT<V>& t, const TwCtxT<V>& tw, int xt) {
   constexpr int beta = A.reg[K];
-#ifdef LOLHIP_ABL_NO_TW       // ablation: no twiddle traffic
-#pragma unroll
-  for (int s = 0; s < 8; ++s) { t.w[s] = tw.sc0 + s; t.wp[s] = tw.sc1 + K; }
-  return;
-#endif
   const u32 voff = tw.comp + (u32)(xt & ((1 << beta) - 1)) * (u32)(2 * sizeof(V));
   const V* sp = INV ? tw.pi : tw.pf;
   int ord = 0;
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     if (e & (1 << K)) continue;
-    if (level_tab<A, K>.slot[e] == ord && (HALF < 0 || ord / (8 / LOLHIP_LEVEL_PARTS) == HALF)) {
+    if (level_tab<A, K>.slot[e] == ord && (HALF < 0 || ord / (8 / LEVEL_PARTS) == HALF)) {
       const int cidx = level_tab<A, K>.cidx[e];
       if constexpr (tw_uniform<A, K>()) {
         // through the CONSTANT address space: a uniform load from it is an s_load whatever else the kernel does.
@@ -612,26 +520,18 @@ __device__ __forceinline__ void tw_fill_lds(V* dst, rsrc_t src, u32 comp, int n,
     }
   }
 }
-#ifndef LOLHIP_WS
-#define LOLHIP_WS 1      // wave-uniform twiddles as SGPR operands (A/B switch)
-#endif
 template <int AR, bool INV, Lay A, int K, int HALF = -1>
 __device__ __forceinline__ void level(VT<AR> (&v)[E], const LevelTwT<VT<AR>>& t, const TwCtxT<VT<AR>>& tw, const auto& qk) {
   constexpr int beta = A.reg[K];
-#ifdef LOLHIP_ABL_NO_BFLY     // ablation: keep the twiddles live, skip the arithmetic
-#pragma unroll
-  for (int s = 0; s < 8; ++s) asm volatile("" :: "v"(t.w[s]), "v"(t.wp[s]));
-  return;
-#endif
   int ordb = -1;
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     if (e & (1 << K)) continue;
     ++ordb;
-    if (HALF >= 0 && ordb / (8 / LOLHIP_LEVEL_PARTS) != HALF) continue;
+    if (HALF >= 0 && ordb / (8 / LEVEL_PARTS) != HALF) continue;
     const int s = level_tab<A, K>.slot[e];
     // a wave holds one polynomial component (so per-component constants are wave-uniform) from n = 1024 up
-    constexpr bool WU = LOLHIP_WS && (A.ntb + R >= 10);
+    constexpr bool WU = A.ntb + R >= 10;
     if constexpr (!INV) bfly_fwd<AR, WU && tw_uniform<A, K>(), beta == 0>(v[e], v[e | (1 << K)], t.w[s], t.wp[s], qk);
     else if constexpr (beta == 0) bfly_inv_last<AR, WU>(v[e], v[e | (1 << K)], tw.l1w, tw.l1wp, tw.sc0, tw.sc1, qk);
     else bfly_inv<AR, WU && tw_uniform<A, K>()>(v[e], v[e | (1 << K)], t.w[s], t.wp[s], qk);
@@ -680,9 +580,6 @@ __device__ __forceinline__ void lane_swap(u64 (&v)[E]) {
 // the previous reads comes FIRST, when every wave has long finished them.
 template <Lay A, Lay B, bool CROSS_WAVE, typename V>
 __device__ __forceinline__ void transpose_put(V (&v)[E], V* lds, int tau) {
-#ifdef LOLHIP_ABL_NO_XPOSE
-  return;
-#endif
   if constexpr (!lay_eq(A, B)) {
     if constexpr (CROSS_WAVE) __syncthreads(); else __builtin_amdgcn_wave_barrier();
     V* wp = lds + lpad(xthr<A>(tau));
@@ -692,9 +589,6 @@ __device__ __forceinline__ void transpose_put(V (&v)[E], V* lds, int tau) {
 }
 template <Lay A, Lay B, bool CROSS_WAVE, typename V>
 __device__ __forceinline__ void transpose_get(V (&v)[E], V* lds, int tau) {
-#ifdef LOLHIP_ABL_NO_XPOSE
-  return;
-#endif
   if constexpr (!lay_eq(A, B)) {
     if constexpr (CROSS_WAVE) __syncthreads(); else __builtin_amdgcn_wave_barrier();
     const V* rp = lds + lpad(xthr<B>(tau));
@@ -776,10 +670,10 @@ template <int AR, bool INV, Lay A, int K>
 __device__ __forceinline__ void level_jit(VT<AR> (&v)[E], const TwCtxT<VT<AR>>& tw, int xt, const auto& qk) {
   using LevelTw = LevelTwT<VT<AR>>;
   if constexpr (tw_distinct(A, K) == 8 && sizeof(VT<AR>) == 8) {
-    // all eight twiddles distinct (32 VGPRs): LOLHIP_LEVEL_PARTS parts keep the live set small
+    // all eight twiddles distinct (32 VGPRs): LEVEL_PARTS parts keep the live set small
     [&]<int... PART>(std::integer_sequence<int, PART...>) {
       (([&] { LevelTw t; tw_fetch<INV, A, K, PART>(t, tw, xt); level<AR, INV, A, K, PART>(v, t, tw, qk); }()), ...);
-    }(std::make_integer_sequence<int, LOLHIP_LEVEL_PARTS>{});
+    }(std::make_integer_sequence<int, LEVEL_PARTS>{});
   } else {
     LevelTw t; tw_fetch<INV, A, K>(t, tw, xt); level<AR, INV, A, K>(v, t, tw, qk);
   }
@@ -826,7 +720,7 @@ __device__ __forceinline__ int fresh(int x) {
 // order: a kernel that keeps an LDS-DMA in flight under a transform (pow2_pipe.hip) fetches these BEFORE it
 // issues the DMA, or the first such twiddle waits for the whole DMA to land.
 struct NoTop {};
-template <int AR, int L, Lay PREV, int SB = 0, bool LEAN = false, bool W16 = false, typename TOP = NoTop, bool TRUNC = false>
+template <int AR, int L, Lay PREV, bool LEAN = false, bool W16 = false, typename TOP = NoTop, bool TRUNC = false>
 __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const TwCtxT<VT<AR>>& tw, int tau_in, const auto& qk,
                                               TOP* pre = nullptr) {
   constexpr bool PRE = !std::is_same_v<TOP, NoTop>;
@@ -848,9 +742,7 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       LevelTw t[R];
       fetch4<AR, false, A, 0>(t, tw, xthr<A>(tau));
       transpose_get<PREV, A, false>(v, lds, tau);
-      LH_STAMP(SB + 2);
       levels4<AR, false, A, 0>(v, t, tw, qk);
-      LH_STAMP(SB + 3);
     }
   }
   if constexpr (S::HAS_W1) {   // W1: levels 5..8 (or the window), then lane swaps for 9, 10
@@ -871,7 +763,6 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       transpose_put<S::w0(), A, false>(v, lds, tau);
       fetch4<AR, false, A, S::W1_K0>(t, tw, xthr<A>(tau));
       transpose_get<S::w0(), A, false>(v, lds, tau);
-      LH_STAMP(SB + 4);
       // levels 5..8, with the twiddles of the two lane-swap levels fetched as registers free up
       if constexpr (S::W1_K0 <= 0) level<AR, false, A, 0>(v, t[0], tw, qk);
       if constexpr (S::W1_K0 <= 1) level<AR, false, A, 1>(v, t[1], tw, qk);
@@ -879,7 +770,6 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       LevelTw ua, ub;
       if constexpr (S::NSWAP >= 1) tw_fetch<false, S::w1a(), 3>(ua, tw, xthr<S::w1a()>(tau));
       level<AR, false, A, 3>(v, t[3], tw, qk);
-      LH_STAMP(SB + 5);
       if constexpr (S::NSWAP >= 2 && !PRE && L10) tw_fetch<false, S::w1b(), 2>(ub, tw, xthr<S::w1b()>(tau));
       if constexpr (S::NSWAP >= 1) { lane_swap<4, 3>(v); level<AR, false, S::w1a(), 3>(v, ua, tw, qk); }
       if constexpr (S::NSWAP >= 2) {
@@ -887,7 +777,6 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
         if constexpr (PRE) { pre->wait_l10(); level<AR, false, S::w1b(), 2>(v, pre->l10, tw, qk); }
         else if constexpr (L10) level<AR, false, S::w1b(), 2>(v, ub, tw, qk);
       }
-      LH_STAMP(SB + 6);
     }
   }
   if constexpr (S::HAS_G) {    // the one cross-wave exchange, then levels 11..L
@@ -896,10 +785,8 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
     transpose_put<S::wave_end(), A, false>(v, lds, tau);   // writes stay inside the wave's own block
     if constexpr (PRE) {
       transpose_get<S::wave_end(), A, true>(v, lds, tau);  // barrier, then read across blocks
-      LH_STAMP(SB + 7);
       pre->wait_g();
       levels4<AR, false, A, S::G_K0>(v, pre->g, tw, qk);
-      LH_STAMP(SB + 8);
     } else if constexpr (LEAN) {
       transpose_get<S::wave_end(), A, true>(v, lds, tau);  // barrier, then read across blocks
       levels4_jit<AR, A, S::G_K0, GK1>(v, tw, xthr<A>(tau), qk);
@@ -907,9 +794,7 @@ __device__ __forceinline__ void fwd_transform(VT<AR> (&v)[E], VT<AR>* lds, const
       LevelTw t[R];
       fetch4<AR, false, A, S::G_K0, GK1>(t, tw, xthr<A>(tau));
       transpose_get<S::wave_end(), A, true>(v, lds, tau);
-      LH_STAMP(SB + 7);
       levels4<AR, false, A, S::G_K0, GK1>(v, t, tw, qk);
-      LH_STAMP(SB + 8);
     }
   }
 }
@@ -1134,21 +1019,10 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
   const u32 off_fin = pofs + (u32)xthr<LFIN>(tau) * uT8;
 
   V v[E];
-  LH_STAMP(0);
-#ifdef LOLHIP_STAMPS
-  if (g_stamp_buf && (threadIdx.x & 63) == 0) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g_stamp_buf[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32 + 30] = ((unsigned long long)xcc << 32) | hwid;
-  }
-#endif
   if constexpr (MODE == 0 || MODE == 2) {
     const rsrc_t src = (MODE == 2) ? ra : ry;
     load_poly<LIO, T1>(src, off_io, uT8, [&](int e, u64 x) { v[e] = from_i64_fwd<AR>((i64)x, qk); });
-    LH_STAMP(1);
-    fwd_transform<AR, L, LIO, 0, TIGHT, T1, NoTop, TR>(v, lds, tw, tau, qk);
-    if constexpr (MODE == 0) LH_STAMP(20);
+    fwd_transform<AR, L, LIO, TIGHT, T1, NoTop, TR>(v, lds, tw, tau, qk);
   }
   if constexpr (MODE == 2) {
     // a-hat stays in registers (canonical) while b is transformed with the register-lean
@@ -1162,7 +1036,6 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
       // holds both operands of each across b's transform (32 more VGPRs: spills)
       if constexpr (TR) asm volatile("" : "+v"(va[e]));
     }
-    LH_STAMP(9);
     const bool square = (a_in == b_in);
     if (!square) {
       // (issuing these with a's loads and holding the 32 raw registers across a's transform
@@ -1174,10 +1047,8 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int e = 0; e < E; ++e) v[e] = from_i64_fwd<AR>((i64)raw[e], qk);
-      LH_STAMP(11);
-      fwd_transform<AR, L, LIO, 10, true, T1, NoTop, TR>(v, lds, tw, tau, qk);
+      fwd_transform<AR, L, LIO, true, T1, NoTop, TR>(v, lds, tw, tau, qk);
     }
-    LH_STAMP(19);
     // TIGHT: from an opaque copy of t, so that no per-lane address is formed (and held) above this point
     const int tl = TIGHT ? fresh(t) : t;
     const ModCtx mc = mod[tl];    // re-read here: keeping it live across the transforms costs registers
@@ -1187,7 +1058,6 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
 #pragma unroll
       for (int e = 0; e < E; ++e) v[e] = pmul<AR>(va[e], (AR < 2 && square) ? va[e] : v[e], mc, qk);   // squaring: v still holds a-hat (lazy)
     }
-    LH_STAMP(22);
   }
   if constexpr (MODE == 2 && L >= TWL_MIN_L) {
     // every wave is past its last forward use of the LDS twiddles (the cross-wave barrier of
@@ -1200,9 +1070,7 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
   }
   if constexpr (MODE == 0) {
     store_poly<LFIN, T1>(ry, off_fin, uT8, [&](int e) { return (u64)canon_fwd<AR>(v[e], qk); });
-    LH_STAMP(21);
   } else {
-    LH_STAMP(23);
     if constexpr (TIGHT) {
       const int tl = fresh(t);      // as above: the addresses are formed here
       tw.pi = tw_inv + (size_t)tl * n * 2;
@@ -1213,9 +1081,7 @@ k_pow2(i64* y, const i64* a_in, const i64* b_in, i64 B, int T,
       tw.l1wp = sc[3];
     }
     inv_transform<AR, L, LIO, T1, TR>(v, lds, tw, tau, qk);
-    LH_STAMP(24);
     store_poly<LIO, T1>(ry, off_io, uT8, [&](int e) { return (u64)canon_inv<AR>(v[e], qk); });
-    LH_STAMP(25);
   }
 }
 

@@ -30,10 +30,11 @@
 // pieces; the level-10 twiddles are ready at vmcnt(14 + 16), the rest at vmcnt(16), the DMA at vmcnt(0).  Every
 // asm vector-memory statement opens with s_nop 4: its SGPR operands may just have been restored from a spill lane
 // by v_readlane, and hipcc pads nothing inside an asm string.
-// (LOLHIP_PAIR_BFLY=1: the pair/mad butterflies of pow2_impl.h — built and measured in this kernel: 16 % fewer VALU
-// instructions, but at its 113-123 VGPRs the doubled data registers spill 10 of them to scratch, whose vector-memory
-// traffic lands in the hand-counted vmcnt windows: 0.253 -> 0.264 ms at q < 2^27, no change at q < 2^30;
-// profiles/r03_ab_pair_bfly_negative.txt.  Off.)
+// (A pair/mad form of the 32-bit butterflies, a residue in the low half of a register pair so that v_mad_u64_u32
+// multiplies and adds, was built and measured in this kernel in round 3: 16 % fewer VALU instructions, but at its
+// 113-123 VGPRs the doubled data registers spill 10 of them to scratch, whose vector-memory traffic lands in the
+// hand-counted vmcnt windows: 0.253 -> 0.264 ms at q < 2^27, no change at q < 2^30.  Not kept; the figures are in
+// profiles/r03_ab_pair_bfly_negative.txt, the form itself in tools/microbench_bfly32.hip.)
 #include "pow2_impl.h"
 #include <cstdio>
 #include <cstdlib>
@@ -140,11 +141,9 @@ k_pow2_pipe(i64* __restrict__ c, const i64* a, const i64* b, i64 B, const u32* _
   const int wv = __builtin_amdgcn_readfirstlane(tau >> 6);
 
   QK32 qk(mod[0], std::true_type{});
-#ifndef LOLHIP_PIPE_Q2_SGPR
   // 2q is an operand of three additions per butterfly: in a VGPR they are plain VOP2 instructions (1.2 ns per
   // wave-instruction at 4 waves per SIMD against 1.96 with an SGPR operand, profiles/r02_microbench_ops.txt)
   asm volatile("" : "+v"(qk.q2));
-#endif
   TwCtxT<V> twf;
   twf.fwd = __builtin_amdgcn_make_buffer_rsrc((void*)tw_fwd, 0, (u32)n * 8u, 0x00020000);
   twf.inv = __builtin_amdgcn_make_buffer_rsrc((void*)tw_inv, 0, (u32)n * 8u, 0x00020000);
@@ -196,20 +195,9 @@ k_pow2_pipe(i64* __restrict__ c, const i64* a, const i64* b, i64 B, const u32* _
   i64 p = blockIdx.x;
   if (p < B) dma(a, p);
   __syncthreads();                                             // the twiddle copies are visible to every wave
-#ifdef LOLHIP_STAMPS      // in-kernel clock: shader cycles (s_memtime) against the 100 MHz counter (s_memrealtime)
-  LH_STAMP(26);
-  { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");
-    if (g_stamp_buf && (threadIdx.x & 63) == 0) g_stamp_buf[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32 + 28] = t_; }
-  unsigned long long* const stamp_all = g_stamp_buf;   // kernel-scope stamps record the FOURTH polynomial of every workgroup (steady state)
-#endif
   for (; p < B; p += G) {
     V v[E], va[E];
-#ifdef LOLHIP_STAMPS
-    unsigned long long* const g_stamp_buf = (p == (i64)blockIdx.x + 3 * G) ? stamp_all : nullptr;   // shadows the global for LH_STAMP below
-#endif
-    LH_STAMP(0);
     take(v);                                                   // waits until a_p has landed (this wave's own rows)
-    LH_STAMP(1);
     // this polynomial's vector-memory twiddles go out BEFORE the DMA (vmcnt retires in issue order); a and b share them
     PipeTop<L, 16> top;
     top.issue(tab_asm, tau);
@@ -217,35 +205,23 @@ k_pow2_pipe(i64* __restrict__ c, const i64* a, const i64* b, i64 B, const u32* _
     // nobody reads it), so that every iteration issues the same vector-memory sequence
     const i64 pn = (p + G < B) ? p + G : p;
     if constexpr (SQ) dma(a, pn); else dma(b, p);
-    fwd_transform<AR, L, S::w0(), 0, false, true, PipeTop<L, 16>>(v, lds, twf, tau, qk, &top);
+    fwd_transform<AR, L, S::w0(), false, true, PipeTop<L, 16>>(v, lds, twf, tau, qk, &top);
 #pragma unroll
     for (int e = 0; e < E; ++e) va[e] = park_fwd<AR>(v[e], qk);
-    LH_STAMP(9);
     if constexpr (!SQ) {
-      LH_STAMP(10);
       __syncthreads();                                         // every wave is past a's cross-wave reads (levels 11..L)
-      LH_STAMP(11);
       take(v);                                                 // waits until b_p has landed
       dma(a, pn);
-      fwd_transform<AR, L, S::w0(), 10, true, true, PipeTop<L, 16>>(v, lds, twf, tau, qk, &top);
+      fwd_transform<AR, L, S::w0(), true, true, PipeTop<L, 16>>(v, lds, twf, tau, qk, &top);
     }
-    LH_STAMP(19);
     const ModCtx mc = mod[0];
 #pragma unroll
     for (int e = 0; e < E; ++e) v[e] = pmul<AR>(va[e], v[e], mc, qk);     // squaring: v still holds a-hat (lazy)
-    LH_STAMP(22);
     inv_transform<AR, L, LIO, true>(v, lds, twi, tau, qk);
-    LH_STAMP(24);
     const rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)(c + p * n), 0, (u32)n * 8u, 0x00020000);
     store_poly<LIO, true>(rc, off_io, 8u, [&](int e) { return (u64)canon_inv<AR>(v[e], qk); });
-    LH_STAMP(25);
   }
   asm volatile("s_waitcnt vmcnt(0)");                         // no DMA may land in LDS after this workgroup has released it
-#ifdef LOLHIP_STAMPS
-  LH_STAMP(27);
-  { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");
-    if (g_stamp_buf && (threadIdx.x & 63) == 0) g_stamp_buf[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32 + 29] = t_; }
-#endif
 }
 
 template <int L, int AR, bool SQ>
@@ -310,8 +286,3 @@ template <bool SQ> static hipError_t launch_pipe_sq(const Pow2Launch& a) {
 hipError_t launch_pow2_pipe(const Pow2Launch& a) { return a.a == a.b ? launch_pipe_sq<true>(a) : launch_pipe_sq<false>(a); }
 
 }  // namespace lolhip
-#if defined(LOLHIP_STAMPS) && LOLHIP_STAMPS == 3      // diagnostic build only: phase stamps of the pipelined kernel
-extern "C" __attribute__((visibility("default"))) int lolhip_debug_set_stamps(unsigned long long* dev) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(lolhip::g_stamp_buf), &dev, sizeof(dev));
-}
-#endif

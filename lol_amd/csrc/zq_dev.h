@@ -97,17 +97,10 @@ LH_D u64 shoup_lazy(u64 y, u64 w, u64 wp, u64 q) {
 // v_mad_u64_u32 (32x32+64 -> 64) and v_lshl_add_u64 are the two 64-bit integer
 // workhorses on gfx950; spelling them out keeps hipcc from splitting the chains into
 // v_mul_lo_u32 + carry adds (each carry add needs a 2-wait-state hazard nop here).
-#ifndef LOLHIP_ASM_MAD
-#define LOLHIP_ASM_MAD 3
-#endif
 LH_D u64 mad64(u32 a, u32 b, u64 c) {
-#if LOLHIP_ASM_MAD
   u64 d, carry;
   asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "v"(c));
   return d;
-#else
-  return (u64)a * (u64)b + c;
-#endif
 }
 // 64-bit adds.  Plain C: hipcc selects v_lshl_add_u64 for these by itself — PROVIDED a uniform
 // addend is not a compile-time-visible negation (x + (0 - m) becomes a two-instruction
@@ -139,14 +132,7 @@ LH_D u64 csubn(u64 x, u64 negm) {
 #ifndef LOLHIP_CSUB_EXEC
 #define LOLHIP_CSUB_EXEC 1      // 0: the select form everywhere (A/B switch)
 #endif
-#ifndef LOLHIP_CSUBX_PAD
-#define LOLHIP_CSUBX_PAD 1      // 0: timing-only A/B of the unpadded tail
-#endif
-#if LOLHIP_CSUBX_PAD
 #define LH_CSUBX_TAIL "\n\ts_nop 1"
-#else
-#define LH_CSUBX_TAIL ""
-#endif
 // %[x] "+v", %[sv] "=&s" scratch pair, %[m] / %[nm] "s"
 #define LH_CSUBX(x, sv, m, nm)                                                                       \
   "s_mov_b64 %[" sv "], exec\n\t"                                                                     \
@@ -195,47 +181,10 @@ LH_D u64 csubx2(u64 x, u64 m1, u64 negm1, u64 m2, u64 negm2) {
 // one — instead of being copied to VGPRs first (450 v_mov per wave of the fused kernel).
 template <bool WS = false>
 LH_D u64 shoup_acc(u64 y, u64 w, u64 wp, u64 nq, u64 init) {
-#if LOLHIP_ASM_MAD == 4
-  // One block, 9 v_mad_u64_u32.  The quotient's cross terms are summed EXACTLY:
-  //   C = wp.hi*y.lo + wp.lo*y.hi  (65 bits: 64 in v[120:121], the carry in vcc)
-  //   Q = wp.hi*y.hi + (C >> 32)   in {floor(wp*y/2^64) - 1, same}
-  // and C >> 32 is assembled as the pair v[122:123] = {C.hi, carry} (VGPR pairs must be
-  // even-aligned, so it cannot simply overlap C).  Halves of a 64-bit asm operand cannot be
-  // named, hence the six hard-wired scratch VGPRs (every kernel using this has a 128-VGPR
-  // budget).  gfx950 needs 2 wait states between a VALU
-  // write of vcc and a VALU read of it; three independent mads sit in between, their junk
-  // carries go to another SGPR pair.
-  u64 t = init, h, sj;
-  asm("v_mad_u64_u32 v[120:121], vcc, %[wph], %[ylo], 0\n\t"
-      "v_mad_u64_u32 v[120:121], vcc, %[wpl], %[yhi], v[120:121]\n\t"
-      "v_mad_u64_u32 %[t], %[sj], %[wl], %[ylo], %[t]\n\t"
-      "v_mad_u64_u32 %[h], %[sj], %[wl], %[yhi], 0\n\t"
-      "v_mad_u64_u32 %[h], %[sj], %[wh], %[ylo], %[h]\n\t"
-      "v_mov_b32 v122, v121\n\t"
-      "v_cndmask_b32_e64 v123, 0, 1, vcc\n\t"
-      "v_mad_u64_u32 v[118:119], %[sj], %[wph], %[yhi], v[122:123]\n\t"
-      "v_mad_u64_u32 %[t], %[sj], v118, %[nql], %[t]\n\t"
-      "v_mad_u64_u32 %[h], %[sj], v118, %[nqh], %[h]\n\t"
-      "v_mad_u64_u32 %[h], %[sj], v119, %[nql], %[h]"
-      : [t] "+v"(t), [h] "=&v"(h), [sj] "=&s"(sj)
-      : [wph] "v"(hi32(wp)), [wpl] "v"(lo32(wp)), [ylo] "v"(lo32(y)), [yhi] "v"(hi32(y)),
-        [wl] "v"(lo32(w)), [wh] "v"(hi32(w)), [nql] "s"(lo32(nq)), [nqh] "s"(hi32(nq))
-      : "vcc", "v118", "v119", "v120", "v121", "v122", "v123");
-  u32 th = hi32(t) + lo32(h);
-  asm("" : "+v"(th));          // keeps it ONE v_add_u32 (else: t + (h << 32) as v_mov + v_lshl_add_u64)
-  return ((u64)th << 32) | lo32(t);
-#elif LOLHIP_ASM_MAD == 3
   // Two asm blocks per product (hipcc pads every separate asm statement that writes an SGPR
   // carry with s_nop; inside a block there is nothing to pad: VGPR RAW is interlocked).
   u64 Q, t, h;
   u32 ah, bh;
-#if defined(LH_ABL_PADN) && LH_ABL_PADN == 1      // timing-only ablations: what an s_nop costs in this kernel
-#define LH_ABL_PAD "\n\ts_nop 0"
-#elif defined(LH_ABL_PADN) && LH_ABL_PADN == 2
-#define LH_ABL_PAD "\n\ts_nop 1"
-#else
-#define LH_ABL_PAD ""
-#endif
 #define LH_SHOUP_BLOCKS(WC)                                                                          \
   asm("v_mul_hi_u32 %1, %3, %5\n\t"                                                                  \
       "v_mul_hi_u32 %2, %4, %6\n\t"                                                                  \
@@ -250,15 +199,13 @@ LH_D u64 shoup_acc(u64 y, u64 w, u64 wp, u64 nq, u64 init) {
       "v_mad_u64_u32 %0, vcc, %6, %8, %0\n\t"                                                        \
       "v_mad_u64_u32 %1, vcc, %3, %4, %1\n\t"                                                        \
       "v_mad_u64_u32 %1, vcc, %6, %9, %1\n\t"                                                        \
-      "v_mad_u64_u32 %1, vcc, %7, %8, %1" LH_ABL_PAD                                                 \
+      "v_mad_u64_u32 %1, vcc, %7, %8, %1"                                                            \
       : "=&v"(t), "=&v"(h)                                                                           \
       : WC(lo32(w)), WC(hi32(w)), "v"(lo32(y)), "v"(hi32(y)), "v"(lo32(Q)), "v"(hi32(Q)),            \
         "s"(lo32(nq)), "s"(hi32(nq)), "v"(init)      /* nq: wave-uniform, one SGPR operand per mad */ \
       : "vcc")
 #define LH_WC_V(x) "v"(x)
 #define LH_WC_S(x) "s"(x)
-  // Two asm blocks per product (hipcc pads every separate asm statement that writes an SGPR
-  // carry with s_nop; inside a block there is nothing to pad: VGPR RAW is interlocked).
   if constexpr (WS) { LH_SHOUP_BLOCKS(LH_WC_S); } else { LH_SHOUP_BLOCKS(LH_WC_V); }
 #undef LH_SHOUP_BLOCKS
 #undef LH_WC_V
@@ -266,20 +213,6 @@ LH_D u64 shoup_acc(u64 y, u64 w, u64 wp, u64 nq, u64 init) {
   u32 th = hi32(t) + lo32(h);
   asm("" : "+v"(th));          // keeps it ONE v_add_u32 (else: t + (h << 32) as v_mov + v_lshl_add_u64)
   return ((u64)th << 32) | lo32(t);
-#else
-  const u32 ah = __umulhi(hi32(wp), lo32(y));
-  const u32 bh = __umulhi(lo32(wp), hi32(y));
-  const u64 Q = mad64(bh, 1u, mad64(hi32(wp), hi32(y), (u64)ah));
-  u64 t = mad64(lo32(w), lo32(y), init);
-  t = mad64(lo32(Q), lo32(nq), t);
-  u64 h = mad64(lo32(w), hi32(y), 0);
-  h = mad64(hi32(w), lo32(y), h);
-  h = mad64(lo32(Q), hi32(nq), h);
-  h = mad64(hi32(Q), lo32(nq), h);
-  u32 th = hi32(t) + lo32(h);
-  asm("" : "+v"(th));          // keeps it ONE v_add_u32 (else: t + (h << 32) as v_mov + v_lshl_add_u64)
-  return ((u64)th << 32) | lo32(t);
-#endif
 }
 
 // shoup_acc with a trim of x (csubx(x, m, negm), wave-uniform m) at the head of its first asm statement: the trim
@@ -287,7 +220,6 @@ LH_D u64 shoup_acc(u64 y, u64 w, u64 wp, u64 nq, u64 init) {
 // (five multiplies follow it).  INIT_X: the trimmed x is also the product's addend (forward butterfly), else 0.
 template <bool WS, bool INIT_X>
 LH_D u64 shoup_acc_csubx(u64 y, u64 w, u64 wp, u64 nq, u64& x, u64 m, u64 negm) {
-#if LOLHIP_ASM_MAD == 3
   u64 Q, t, h, sv;
   u32 ah, bh;
 #define LH_SHOUP_BLOCKS_X(WC)                                                                        \
@@ -316,10 +248,6 @@ LH_D u64 shoup_acc_csubx(u64 y, u64 w, u64 wp, u64 nq, u64& x, u64 m, u64 negm) 
   u32 th = hi32(t) + lo32(h);
   asm("" : "+v"(th));
   return ((u64)th << 32) | lo32(t);
-#else
-  x = csubx(x, m, negm);
-  return shoup_acc<WS>(y, w, wp, nq, INIT_X ? x : (u64)0);
-#endif
 }
 
 // remainder of the 128-bit value (u1:u0) by c.q, requires (u1:u0) < q * 2^64

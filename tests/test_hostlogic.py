@@ -40,6 +40,26 @@ def test_no_oracle_or_cpu_fallback_in_product():
                 assert "cpu_ref" not in src and "libcpuref" not in src and "libctensor" not in src, f
 
 
+def test_device_code_has_one_build_configuration():
+    """The kernels exist in one shipped configuration: the only preprocessor conditionals in lol_amd/csrc are the
+    compiler's own fences and LOLHIP_CSUB_EXEC (the one build-time switch, tests/test_csub_exec_host.py)."""
+    allowed = {"__HIPCC__", "__HIP_DEVICE_COMPILE__", "LOLHIP_CSUB_EXEC"}
+    csrc = os.path.join(ROOT, "lol_amd", "csrc")
+    seen = 0
+    for f in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, f)
+        if not os.path.isfile(path):
+            continue
+        for no, line in enumerate(open(path, errors="replace"), 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            seen += 1
+            names = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+            assert names and names <= allowed, f"{f}:{no}: {line.strip()}"
+    assert seen >= 5      # zq_dev.h and rng_dev.h hold the surviving ones
+
+
 @pytest.mark.parametrize("m,qs", TENSOR1 + [(1024, [12289]), (2 ** 14, [1073872897]), (15015, [1073842771]),
                                              (64 * 27, [3457]), (64 * 81, [10369]), (64 * 9 * 25, [14401])])
 def test_plan_tables_follow_lol_rules(lolhip, m, qs):

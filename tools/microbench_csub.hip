@@ -242,7 +242,7 @@ int main() {
   (void)hipMemcpy(c.dtw, c.tw.data(), 16ull * c.N, hipMemcpyHostToDevice);
   (void)hipMalloc(&c.dout, (size_t)c.cus * 8 * 256 * 8);
   (void)hipEventCreate(&c.e0); (void)hipEventCreate(&c.e1);
-  printf("device %s CUs=%d q=%llu LOLHIP_CSUB_EXEC=%d LOLHIP_CSUBX_PAD=%d\n", pr.name, c.cus, (unsigned long long)q, LOLHIP_CSUB_EXEC, LOLHIP_CSUBX_PAD);
+  printf("device %s CUs=%d q=%llu LOLHIP_CSUB_EXEC=%d\n", pr.name, c.cus, (unsigned long long)q, LOLHIP_CSUB_EXEC);
   printf("# trims: every row also carries one v_lshl_add_u64 (x + inc) per op; row 0 is that add alone\n");
   run_trim<T_NONE>(c, "0  x + inc only (loop overhead)", 1);
   run_trim<T_SEL>(c, "a  csubn: add, v_cmp_gt_i64, 2 v_cndmask", 5);
