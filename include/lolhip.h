@@ -719,6 +719,58 @@ LOLHIP_API int64_t lolhip_pt_tunnel_work_len(const lolhip_pt_tunnel *c, int64_t 
 LOLHIP_API int lolhip_pt_tunnel_batch(const lolhip_pt_tunnel *c, void *stream, const int64_t *x_dec, int64_t *out_pow,
                                       int64_t *work, int64_t B);
 
+/* --- exact ring product over moduli without a CRT basis (ringmul_api.cpp, ringmul.hip) ----------------------------
+ * out = a * b in R_q = Z_q[zeta_m] for ANY moduli q_0 .. q_(T-1) in [2, 2^62): 2^e, p^e, odd composites, primes of the
+ * wrong residue class, where lolhip_polymul_batch answers LOLHIP_ERR_NO_CRT.  The exact counterpart of the reference's
+ * fallback through the CRT over C (Cyc (*), Cyc.hs:262-297; CRTExt, UCyc.hs:422-444), which is approximate once
+ * n q^2 leaves 53 bits.
+ *   pq: any plan of index m over the q_t, T <= 16, no CRT basis needed.  pQ: a plan of the SAME index (same prime
+ *   powers in the same order) over K <= 3 pairwise distinct NTT primes Q_0 .. Q_(K-1), CRT basis required.
+ *   Lift convention (that of k_relift above): an operand coefficient, any int64, is taken mod q_t; the residue r lifts
+ *   to r when 2 r < q_t, else to r - q_t, so |lift| <= H_t = floor(q_t / 2).
+ *   Exactness, certified at create in 256-bit arithmetic: a powerful-basis coefficient of the integer product is at
+ *   most C_m H^2 in absolute value, C_m the growth constant of the index (that of the lifted PRF and of crtSet above),
+ *   H = max_t H_t; the product over prod Q is exact iff   2 C_m H^2 < Q_0 ... Q_(K-1).
+ *   Way back: the centred lift of the K residues (mixed radix over pQ's own lift constants, lolhip_plan_table 12; the
+ *   sign from a most-significant-first digit comparison), reduced mod q_t into [0, q_t).
+ * lolhip_ringmul_moduli(pps, npps, qs, T, Qs): the default primes, by this rule.  bound = 2 C_m H^2.  For K = 1, 2, 3 in
+ *   this order: r = the smallest integer with r^K >= bound (exact); Q_0 = the smallest prime = 1 mod m above r
+ *   (lolhip_good_q(m, r)), Q_i = lolhip_good_q(m, Q_(i-1)); the first K whose primes all lie below 2^61 wins.  Every
+ *   prime exceeds r, so the product exceeds the bound (were it not to, the window of K consecutive primes would move up
+ *   one prime at a time).  Returns K and writes Qs[0..K), zero above; LOLHIP_ERR_MODULUS when no K <= 3 serves (the
+ *   growth constant saturates at 2^62, or the bound is beyond three primes) or a q_t lies outside [2, 2^62);
+ *   LOLHIP_ERR_INVALID for NULL pointers, T < 1, a list that is not ascending primes with exponents >= 1.
+ * lolhip_ringmul_create(pq, pQ, &h): validates, certifies the bound and precomputes per component P_i mod q_t
+ *   (P_i = Q_0 ... Q_(i-1)) and prod Q mod q_t; they travel by value in every launch (H_t = q_t >> 1 needs no table:
+ *   the kernels test 2 r < q_t).  pQ must outlive the handle; pq is not referenced after create.  Over host-only plans it validates only: the compute calls then return LOLHIP_ERR_NO_DEVICE.
+ * lolhip_ringmul_work_len(h, B): int64 words of device scratch, 16-byte aligned:  2 * even(B T n K)  — the lifted a
+ *   and b, each rounded up to an even word count.
+ * lolhip_ringmul_batch(h, stream, out, a, b, work, B): a, b, out [B][n][T], powerful basis; out in [0, q_t).  out may
+ *   alias a or b, a may equal b.  Launch plan: k_ring_lift a, k_ring_lift b (one launch when a == b),
+ *   lolhip_polymul_batch on pQ over B T polynomials, k_ring_fold.
+ * lolhip_ringmul_prepare(h, stream, bhat, b, work, Bb): bhat [Bb T][n][K] = crt over pQ of the lifted b [Bb][n][T]
+ *   (k_ring_lift, crt).  work is not used (NULL is accepted).
+ * lolhip_ringmul_prepared_batch(h, stream, out, a, bhat, Bb, work, B): the same product against a prepared operand,
+ *   Bb = B (one per item) or Bb = 1 (one public element against the batch).  Launch plan: k_ring_lift a, crt, pointwise
+ *   product with period Bb T n K, crtInv, k_ring_fold.  work as for lolhip_ringmul_batch (half of it is used).
+ * The compute calls neither allocate nor synchronise beyond what lolhip_polymul_batch / crt do on pQ.
+ * Status, all decided on the host before any launch (outputs are then not written): LOLHIP_ERR_INVALID for NULL
+ *   pointers, B < 0, B T >= 2^31, Bb not in {1, B}, a period T n K >= 2^31 with Bb = 1 < B, plans of different indices,
+ *   K > 3, T > 16; LOLHIP_ERR_MODULUS when the Q_i are not pairwise distinct or the bound fails; LOLHIP_ERR_NO_CRT
+ *   when pQ has no CRT basis; LOLHIP_ERR_NO_DEVICE from the compute calls over host-only plans; LOLHIP_ERR_DEVICE as
+ *   elsewhere.  B = 0 is a no-op that returns LOLHIP_OK. */
+typedef struct lolhip_ringmul lolhip_ringmul;
+LOLHIP_API int lolhip_ringmul_moduli(const lolhip_pp *pps, int npps, const int64_t *qs, int T, int64_t Qs[3]);
+LOLHIP_API int lolhip_ringmul_create(const lolhip_plan *pq, const lolhip_plan *pQ, lolhip_ringmul **out);
+LOLHIP_API void lolhip_ringmul_destroy(lolhip_ringmul *h);
+LOLHIP_API int64_t lolhip_ringmul_work_len(const lolhip_ringmul *h, int64_t B);
+LOLHIP_API int lolhip_ringmul_batch(const lolhip_ringmul *h, void *stream, int64_t *out, const int64_t *a,
+                                    const int64_t *b, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_ringmul_prepare(const lolhip_ringmul *h, void *stream, int64_t *bhat, const int64_t *b,
+                                      int64_t *work, int64_t Bb);
+LOLHIP_API int lolhip_ringmul_prepared_batch(const lolhip_ringmul *h, void *stream, int64_t *out, const int64_t *a,
+                                             const int64_t *bhat, int64_t Bb, int64_t *work, int64_t B);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

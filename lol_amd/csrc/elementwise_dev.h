@@ -1,6 +1,7 @@
 // lol_amd/csrc/elementwise_dev.h — the building blocks the element-wise passes share (pipeline.hip, decrypt.hip,
-// encrypt.hip, kshint.hip, khprf.hip, public.hip, modswitch.hip): the tile count of a launch, the
-// 16-byte store type and two scalar reductions.  Included by .hip files only.  A new pass adds here rather than copying.
+// encrypt.hip, kshint.hip, khprf.hip, public.hip, modswitch.hip, ringmul.hip): the tile count of a
+// launch, the 16-byte store type, two scalar reductions, the centred lift and the mixed-radix digits of an RNS value.
+// Included by .hip files only.  A new pass adds here rather than copying.
 #pragma once
 #include "zq_dev.h"
 
@@ -25,6 +26,40 @@ __device__ __forceinline__ u64 mod_any(i64 x, const ModCtx& mc) {
   const u64 a = x >= 0 ? (u64)x : 0 - (u64)x;
   const u64 r = rem128(0, a, mc);
   return (x < 0 && r != 0) ? mc.q - r : r;
+}
+
+// the centred lift of a residue r in [0, q): r when 2 r < q, else r - q; at most floor(q / 2) in absolute value
+__device__ __forceinline__ i64 centred(u64 r, u64 q) { return 2 * r < q ? (i64)r : (i64)r - (i64)q; }
+
+// Mixed-radix (Garner) digits of the X in [0, prod q_i) with X = x[i] mod q_i, x[i] in [0, q_i): X = sum_i v[i] P_i,
+// P_i = q_0 ... q_(i-1).  pinv[i] = P_i^-1 mod q_i, qmod[i * stride + j] = q_j mod q_i (plan.h lift_consts).
+template <int NT>
+__device__ __forceinline__ void garner_digits(u64 (&v)[NT], const u64 (&x)[NT], const ModCtx* mod, const u64* pinv,
+                                              const u64* qmod, int stride) {
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const ModCtx mc = mod[i];
+    u64 s = 0;                                // sum_{j<i} v_j P_j mod q_i, Horner from the top digit
+#pragma unroll
+    for (int j = i - 1; j >= 0; --j) {
+      const unsigned __int128 t = (unsigned __int128)s * qmod[i * stride + j] + v[j];   // < q_i^2 + 2^62 < q_i 2^64
+      s = rem128((u64)(t >> 64), (u64)t, mc);
+    }
+    v[i] = i == 0 ? x[0] : mulmod(submod(x[i], s, mc.q), pinv[i], mc);
+  }
+}
+
+// X > floor((Q - 1) / 2), i.e. X is negative as a centred value: most significant digit first against the digits
+// half[] of floor((Q - 1) / 2)
+template <int NT>
+__device__ __forceinline__ bool above_half(const u64 (&v)[NT], const u64* half) {
+  bool neg = false, decided = false;
+#pragma unroll
+  for (int i = NT - 1; i >= 0; --i) {
+    const u64 h = half[i];
+    if (!decided && v[i] != h) { neg = v[i] > h; decided = true; }
+  }
+  return neg;
 }
 
 }  // namespace lolhip

@@ -162,6 +162,15 @@ def lib():
     L.lolhip_pt_tunnel_work_len.argtypes = [vp, i64]
     L.lolhip_pt_tunnel_work_len.restype = i64
     L.lolhip_pt_tunnel_batch.argtypes = [vp, vp, vp, vp, vp, i64]
+    L.lolhip_ringmul_moduli.argtypes = [pp, ci, _i64p, ci, _i64p]
+    L.lolhip_ringmul_create.argtypes = [vp, vp, C.POINTER(vp)]
+    L.lolhip_ringmul_destroy.argtypes = [vp]
+    L.lolhip_ringmul_destroy.restype = None
+    L.lolhip_ringmul_work_len.argtypes = [vp, i64]
+    L.lolhip_ringmul_work_len.restype = i64
+    L.lolhip_ringmul_batch.argtypes = [vp, vp, vp, vp, vp, vp, i64]
+    L.lolhip_ringmul_prepare.argtypes = [vp, vp, vp, vp, vp, i64]
+    L.lolhip_ringmul_prepared_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64]
     L.lolhip_gsqnorm_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_gsqnorm_f64_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_rlwe_work_len.argtypes = [vp, ci, i64]
@@ -543,6 +552,7 @@ class Plan:
     def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None):
         self.pps = [(int(p), int(e)) for p, e in pps]
         self.qs = [int(q) for q in qs]
+        self.host_only = bool(host_only)
         arr = (_PP * max(1, len(self.pps)))()
         for i, (p, e) in enumerate(self.pps):
             arr[i].prime, arr[i].exponent = p, e
@@ -1409,6 +1419,81 @@ class PTTunnel:
         out = torch.empty((B, nS), dtype=torch.int64, device=x.device)
         _check(L.lolhip_pt_tunnel_batch(self._h, _stream(stream), _devptr(x), _devptr(out), _devptr(work), B))
         return out.cpu().numpy() if host else out
+
+
+class RingMul:
+    """The exact ring product a * b in R_q for moduli without a CRT basis (lolhip_ringmul_batch): q = 2^e, p^e, odd
+    composites, tuples of them.  plan_q: any Plan over the moduli; plan_Q: a Plan of the same index over K <= 3 distinct
+    NTT primes whose product exceeds 2 C_m floor(q/2)^2 (certified at creation), or None for the primes of
+    RingMul.moduli.  Operands and results [B][n][T], powerful basis, numpy or CUDA tensors; operands may be any int64
+    (taken mod q_t), results lie in [0, q_t)."""
+
+    def __init__(self, plan_q, plan_Q=None):
+        if plan_Q is None:
+            plan_Q = Plan(plan_q.pps, self.moduli(plan_q.pps, plan_q.qs), host_only=plan_q.host_only)
+        self.plan_q, self.plan_Q = plan_q, plan_Q
+        self.n, self.T, self.K = plan_q.n, plan_q.T, plan_Q.T
+        h = C.c_void_p()
+        _check(lib().lolhip_ringmul_create(plan_q._h, plan_Q._h, C.byref(h)), "ringmul_create")
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.lolhip_ringmul_destroy(h)
+
+    @staticmethod
+    def moduli(pps, qs):
+        """The default NTT primes for index `pps` (a prime-power list or m) and moduli qs: the fewest K <= 3 consecutive
+        primes = 1 mod m above the K-th root of 2 C_m floor(max q / 2)^2 (the rule of include/lolhip.h)."""
+        _, a, na = _pps(pps)
+        qa = (C.c_int64 * max(1, len(qs)))(*[int(q) for q in qs])
+        Qs = (C.c_int64 * 3)()
+        K = lib().lolhip_ringmul_moduli(a, na, qa, len(qs), Qs)
+        _check(min(K, 0), "ringmul_moduli")
+        return [int(Qs[i]) for i in range(K)]
+
+    def workLen(self, B):
+        w = lib().lolhip_ringmul_work_len(self._h, int(B))
+        _check(min(w, 0))
+        return w
+
+    def _batch(self, a):
+        per, size = self.n * self.T, self._size(a)
+        if size % per:
+            raise ValueError(f"not a whole number of [n={self.n}, T={self.T}] ring elements")
+        return size // per
+
+    @staticmethod
+    def _size(x):
+        return x.size if isinstance(x, np.ndarray) else x.numel()
+
+    def __call__(self, a, b, out=None, stream=None):
+        """out = a * b; out may be a or b (CUDA tensors), and a may be b."""
+        L, B = lib(), self._batch(a)
+        if self._batch(b) != B:
+            raise ValueError("a and b hold different batches")
+        same = b is a
+        call = lambda s, p, o, w, n: L.lolhip_ringmul_batch(self._h, s, o, p[0], p[0] if same else p[1], w, n)
+        return Plan._run_staged(call, stream, [a] if same else [a, b], B, lambda: self.workLen(B),
+                                lambda: (B, self.n, self.T), out=out)
+
+    def prepare(self, b, stream=None):
+        """bhat [Bb T][n][K]: the CRT over plan_Q of the lifted b [Bb][n][T], for mulPrepared."""
+        L, Bb = lib(), self._batch(b)
+        call = lambda s, p, o, w, n: L.lolhip_ringmul_prepare(self._h, s, o, p[0], w, n)
+        return Plan._run_staged(call, stream, [b], Bb, lambda: 0, lambda: (Bb * self.T, self.n, self.K))
+
+    def mulPrepared(self, a, bhat, out=None, stream=None):
+        """out = a * b for bhat = prepare(b) of one element (against every item of a) or of as many as a holds."""
+        L, B = lib(), self._batch(a)
+        per = self.T * self.n * self.K
+        size = self._size(bhat)
+        if size % per:
+            raise ValueError("bhat is not a whole number of prepared elements")
+        Bb = size // per
+        call = lambda s, p, o, w, n: L.lolhip_ringmul_prepared_batch(self._h, s, o, p[0], p[1], Bb, w, n)
+        return Plan._run_staged(call, stream, [a, bhat], B, lambda: self.workLen(B), lambda: (B, self.n, self.T), out=out)
 
 
 class PTRound:

@@ -5,8 +5,9 @@
 ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q = 2^k alone), of ciphertext modSwitch
 (`--modswitch`: that leg alone), of multi-hop tunnelling (`--tunnel-chain`: that leg alone), of homomorphic rounding
 (`--ptround`: that leg alone, also written to profiles/ptround_pipelines.jsonl) and of RLWE instance
-verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl).  Operands resident in HBM, HIP events on
-the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
+verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl) and of the exact ring
+product over moduli without a CRT basis (`--ringmul`: that leg alone, also written to profiles/ringmul_pipelines.jsonl).
+Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
 import os
@@ -672,8 +673,67 @@ def rlwe_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def ringmul_leg(gen):
+    """The exact ring product over q = 2^8 (one NTT prime, a 32-bit class) and q = 2^32 (two primes) at m = 16384,
+    B = 4096: lolhip_ringmul_batch beside lolhip_polymul_batch on the same plan_Q and batch in the same process, so the
+    difference is the two passes (k_ring_lift twice, k_ring_fold once: (3 + 3 K) 8 bytes per word of an operand), against
+    lolhip_copy_slab on a slab of the lifted operand's size.  Median of five rounds of ten calls.
+    Also written to profiles/ringmul_pipelines.jsonl."""
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    lines = []
+
+    def rep(name, cfg, ts, items, alg_bytes, note=None):
+        ms = statistics.median(ts)
+        d = {"op": name, "config": cfg, "ms": round(ms, 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
+             "items_per_s": round(items / ms * 1e3, 1), "alg_GBps": round(alg_bytes / ms / 1e6, 1)}
+        if note:
+            d["note"] = note
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+        return ms
+
+    m, B = 16384, 4096
+    for q in (2 ** 8, 2 ** 32):
+        rm = lol_amd.RingMul(lol_amd.Plan.for_index(m, [q]))
+        n, K, PQ = rm.n, rm.K, rm.plan_Q
+        words = B * n
+        cfg = f"m={m} q=2^{q.bit_length() - 1} Q={PQ.qs} B={B}"
+        a, b = (torch.randint(-2 ** 63, 2 ** 63 - 1, (B, n, 1), dtype=torch.int64, device="cuda", generator=gen) for _ in range(2))
+        out = torch.empty_like(a)
+        work = torch.empty((rm.workLen(B),), dtype=torch.int64, device="cuda")
+        la, lb = work[:words * K], work[words * K:2 * words * K]
+        bhat = rm.prepare(b)
+        rounds = lambda fn: [timeit(fn) for _ in range(5)]
+        t_ring = rep("ringmul", cfg, rounds(lambda: L.lolhip_ringmul_batch(rm._h, st, ptr(out), ptr(a), ptr(b), ptr(work), B)),
+                     B, 3 * words * 8, note="alg = a, b read and out written once")
+        t_pm = rep("  polymul(plan_Q)", cfg, rounds(lambda: L.lolhip_polymul_batch(PQ._h, st, ptr(la), ptr(la), ptr(lb), B)),
+                   B, 3 * words * K * 8, note="the lifted slabs of the call above, c = a as inside it")
+        t_copy = rep("  copy_slab", f"{words * K * 8 >> 20} MiB read + written",
+                     rounds(lambda: L.lolhip_copy_slab(st, ptr(lb), ptr(la), words * K * 8, 0)), B, 2 * words * K * 8,
+                     note="lolhip_copy_slab, the HBM yardstick")
+        pass_bytes = (3 + 3 * K) * words * 8
+        d = {"op": "  lift + lift + fold", "config": cfg, "ms": round(t_ring - t_pm, 4),
+             "alg_GBps": round(pass_bytes / (t_ring - t_pm) / 1e6, 1),
+             "copy_GBps": round(2 * words * K * 8 / t_copy / 1e6, 1), "note": "ringmul - polymul, medians; (3 + 3 K) 8 bytes per word"}
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+        rep("ringmul_prepared", cfg + " Bb=B", rounds(lambda: L.lolhip_ringmul_prepared_batch(rm._h, st, ptr(out), ptr(a), ptr(bhat), B, ptr(work), B)),
+            B, (2 + K) * words * 8, note="lift, crt, pointwise product, crtInv, fold")
+        del a, b, out, work, bhat, la, lb, rm
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "ringmul_pipelines.jsonl"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--ringmul" in sys.argv:          # the exact ring product leg alone
+        ringmul_leg(gen)
+        return
     if "--rlwe" in sys.argv:             # the RLWE verification / gSqNorm leg alone
         rlwe_leg(gen)
         return
