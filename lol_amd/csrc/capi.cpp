@@ -53,10 +53,9 @@ int device_count() {
 
 int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const int64_t* omega_pp,
               const int64_t* mhatinv, int host_only, lolhip_plan** out) {
-  if (!out || npps < 0 || T < 1 || !qs || (npps > 0 && !pps)) return LOLHIP_ERR_INVALID;
-  *out = nullptr;
   std::vector<PP> v;
-  for (int i = 0; i < npps; ++i) v.push_back(PP{pps[i].prime, pps[i].exponent});
+  if (!out || T < 1 || !qs || !to_pps(pps, npps, v)) return LOLHIP_ERR_INVALID;
+  *out = nullptr;
   std::vector<u64> q;
   for (int t = 0; t < T; ++t) {
     if (qs[t] < 2) return LOLHIP_ERR_MODULUS;
@@ -94,19 +93,30 @@ bool use_mixed(const Plan& P, const StageProgram& sp) {
 
 // the Z_q CRT programs the vector interpreter runs: the merged prime-power form where the plan has one (class 2)
 // big_ok: the caller launches kernels that take 18-/20-element vectors (lone transforms, the fused poly-mul)
-const StageProgram& zq_crt(const Plan& P, bool big_ok = true) {
-  if (sw(SW_GENERIC_SCALAR)) return P.prog_crt;
-  if (big_ok && !P.prog_crt_mg_big.stages.empty()) return P.prog_crt_mg_big;
-  return !P.prog_crt_mg.stages.empty() ? P.prog_crt_mg : P.prog_crt;
-}
-const StageProgram& zq_crtinv(const Plan& P, bool big_ok = true) {
-  if (sw(SW_GENERIC_SCALAR)) return P.prog_crtinv;
-  if (big_ok && !P.prog_crtinv_mg_big.stages.empty()) return P.prog_crtinv_mg_big;
-  return !P.prog_crtinv_mg.stages.empty() ? P.prog_crtinv_mg : P.prog_crtinv;
+const StageProgram& zq_crt(const Plan& P, bool inverse, bool big_ok = true) {
+  const StageProgram& plain = inverse ? P.prog_crtinv : P.prog_crt;
+  const StageProgram& mg = inverse ? P.prog_crtinv_mg : P.prog_crt_mg;
+  const StageProgram& mg_big = inverse ? P.prog_crtinv_mg_big : P.prog_crt_mg_big;
+  if (sw(SW_GENERIC_SCALAR)) return plain;
+  if (big_ok && !mg_big.stages.empty()) return mg_big;
+  return !mg.stages.empty() ? mg : plain;
 }
 // the one-launch programs of m = 2^e * odd (valid when use_fused2)
-const StageProgram& fused_crt(const Plan& P, bool big_ok = true) { return (big_ok && !P.prog_crt_fused_big.stages.empty()) ? P.prog_crt_fused_big : P.prog_crt_fused; }
-const StageProgram& fused_crtinv(const Plan& P, bool big_ok = true) { return (big_ok && !P.prog_crtinv_fused_big.stages.empty()) ? P.prog_crtinv_fused_big : P.prog_crtinv_fused; }
+const StageProgram& fused_crt(const Plan& P, bool inverse, bool big_ok = true) {
+  const StageProgram& big = inverse ? P.prog_crtinv_fused_big : P.prog_crt_fused_big;
+  return (big_ok && !big.stages.empty()) ? big : (inverse ? P.prog_crtinv_fused : P.prog_crt_fused);
+}
+
+// the launch of the vector interpreter that computes y = program sp of a over the plan's tables (the fused poly-mul
+// adds b and its second program)
+MixedLaunch mixed_launch(const Plan& P, hipStream_t s, int64_t* y, const int64_t* a, int64_t B, const StageProgram& sp) {
+  MixedLaunch m;
+  m.stream = s; m.y = y; m.a = a; m.b = nullptr; m.B = B; m.T = P.T; m.n = P.n;
+  m.st_a = sp.d_stages; m.n_a = sp.nstages; m.st_b = nullptr; m.n_b = 0; m.big = sp.big;
+  m.consts = P.d_consts_mont ? P.d_consts_mont : P.d_consts; m.consts32 = P.d_consts32; m.cpc = P.consts_per_comp;
+  m.mod = P.d_mod; m.cls = P.mixed_cls; m.fused = false;
+  return m;
+}
 
 bool q_below(const Plan& P, int bits) {
   for (u64 q : P.qs) if (q >> bits) return false;
@@ -149,13 +159,7 @@ int need_device(const Plan& P) {
 int need_device(const lolhip_plan* p) { return p ? need_device(p->P) : LOLHIP_ERR_INVALID; }
 
 int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
-  if (use_mixed(P, sp)) {
-    MixedLaunch m;
-    m.stream = s; m.y = y; m.a = src ? src : y; m.b = nullptr; m.B = B; m.T = P.T; m.n = P.n;
-    m.st_a = sp.d_stages; m.n_a = sp.nstages; m.st_b = nullptr; m.n_b = 0;
-    m.consts = P.d_consts_mont ? P.d_consts_mont : P.d_consts; m.consts32 = P.d_consts32; m.cpc = P.consts_per_comp; m.mod = P.d_mod; m.cls = P.mixed_cls; m.fused = false; m.big = sp.big;
-    return hip_status(launch_mixed(m));
-  }
+  if (use_mixed(P, sp)) return hip_status(launch_mixed(mixed_launch(P, s, y, src ? src : y, B, sp)));
   GenericLaunch a;
   a.stream = s; a.y = y; a.B = B; a.T = P.T; a.n = P.n;
   a.stages = sp.d_stages; a.nstages = sp.nstages;
@@ -184,7 +188,7 @@ int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, i
 //           the slab (measured at 58 bits: m = 11648 0.62 vs 0.55 ms, m = 14336 0.65 vs 0.52 ms; with the even/odd
 //           form of round 3 0.54 vs 0.48 and 0.62 vs 0.50, m = 14400 0.457 vs 0.448; at 26 bits fused wins everywhere);
 //   SPLIT   the 2-power factor through the m = 2^k kernels, the odd primes through prog_crt(inv)_odd;
-//   STAGES  the stage program alone (zq_crt / zq_crtinv).
+//   STAGES  the stage program alone (zq_crt).
 // The 2-power tiles exist in the vector interpreter only: a plan it refuses (mixed_ok) never takes FUSED2.
 enum CrtRoute { ROUTE_POW2, ROUTE_FUSED2, ROUTE_SPLIT, ROUTE_STAGES };
 CrtRoute crt_route(const Plan& P) {
@@ -197,9 +201,9 @@ CrtRoute crt_route(const Plan& P) {
 // the stage program of that route (POW2 launches none: the staged list, for inspection)
 const StageProgram& crt_route_prog(const Plan& P, CrtRoute r, bool inverse) {
   switch (r) {
-    case ROUTE_FUSED2: return inverse ? fused_crtinv(P) : fused_crt(P);
+    case ROUTE_FUSED2: return fused_crt(P, inverse);
     case ROUTE_SPLIT: return inverse ? P.prog_crtinv_odd : P.prog_crt_odd;
-    default: return inverse ? zq_crtinv(P) : zq_crt(P);
+    default: return zq_crt(P, inverse);
   }
 }
 // poly-mul as ONE launch of the vector interpreter (a-hat in registers, b through the same LDS buffer); otherwise it is
@@ -208,7 +212,12 @@ bool polymul_one_launch(const Plan& P) {
   if (P.is_pow2 || sw(SW_POLYMUL_UNFUSED)) return false;
   const bool fused2 = use_fused2(P);
   const bool split2 = !fused2 && P.pow2_part && !sw(SW_NO_POW2_PART);   // the 2-power factor has its own kernels
-  return !split2 && (fused2 || (use_mixed(P, zq_crt(P)) && use_mixed(P, zq_crtinv(P))));
+  return !split2 && (fused2 || (use_mixed(P, zq_crt(P, false)) && use_mixed(P, zq_crt(P, true))));
+}
+// the forward / inverse program of that one launch (valid when polymul_one_launch).  ONE choice for
+// lolhip_polymul_batch and for lolhip_plan_table 13 / 14
+const StageProgram& polymul_prog(const Plan& P, bool inverse) {
+  return use_fused2(P) ? fused_crt(P, inverse) : zq_crt(P, inverse);
 }
 
 // crt / crtInv of B polynomials through whichever path the plan has (crt_route)
@@ -318,7 +327,7 @@ int64_t lolhip_plan_table(const lolhip_plan* p, int which, int k, int64_t* out, 
       const bool inv = which == 11 || which == 14;
       const StageProgram* sp = nullptr;
       if (which <= 11) sp = &crt_route_prog(P, crt_route(P), inv);
-      else if (polymul_one_launch(P)) sp = use_fused2(P) ? (inv ? &fused_crtinv(P) : &fused_crt(P)) : (inv ? &zq_crtinv(P) : &zq_crt(P));
+      else if (polymul_one_launch(P)) sp = &polymul_prog(P, inv);
       if (sp) for (const Stage& st : sp->stages) { tmp.push_back(st.kind); tmp.push_back(st.p); tmp.push_back(st.d); tmp.push_back(st.rts); }
       src = &tmp;
       break;
@@ -368,16 +377,12 @@ int lolhip_polymul_batch(const lolhip_plan* p, void* stream, int64_t* c, const i
   const Plan& P = p->P;
   hipStream_t s = (hipStream_t)stream;
   if (P.is_pow2) return run_pow2(P, 2, s, c, a, b, B);
-  const bool fused2 = use_fused2(P);
   if (polymul_one_launch(P)) {
     // one launch: a-hat in registers, b through the same LDS buffer, 3 slab passes (mixed.hip)
-    const StageProgram& pf = fused2 ? fused_crt(P) : zq_crt(P);
-    const StageProgram& pi = fused2 ? fused_crtinv(P) : zq_crtinv(P);
-    MixedLaunch m;
-    m.stream = s; m.y = c; m.a = a; m.b = b; m.B = B; m.T = P.T; m.n = P.n;
-    m.st_a = pf.d_stages; m.n_a = pf.nstages;
-    m.st_b = pi.d_stages; m.n_b = pi.nstages;
-    m.consts = P.d_consts_mont ? P.d_consts_mont : P.d_consts; m.consts32 = P.d_consts32; m.cpc = P.consts_per_comp; m.mod = P.d_mod; m.cls = P.mixed_cls; m.fused = true; m.big = pf.big || pi.big;
+    const StageProgram& pf = polymul_prog(P, false);
+    const StageProgram& pi = polymul_prog(P, true);
+    MixedLaunch m = mixed_launch(P, s, c, a, B, pf);
+    m.b = b; m.st_b = pi.d_stages; m.n_b = pi.nstages; m.fused = true; m.big = pf.big || pi.big;
     return hip_status(launch_mixed(m));
   }
   // otherwise: crt(a) -> c, crt(b) -> temp, multiply, crtInv.  c may alias a or b.  The temp is a
@@ -390,8 +395,8 @@ int lolhip_polymul_batch(const lolhip_plan* p, void* stream, int64_t* c, const i
   rc = LOLHIP_OK;
   if (!P.pow2_part || sw(SW_NO_POW2_PART)) {
     // stage program alone: transform b into the temp first (c may alias b), then a into c
-    rc = run_prog(P, zq_crt(P), s, tmp, B, b);
-    if (!rc) rc = run_prog(P, zq_crt(P), s, c, B, c != a ? a : nullptr);
+    rc = run_prog(P, zq_crt(P, false), s, tmp, B, b);
+    if (!rc) rc = run_prog(P, zq_crt(P, false), s, c, B, c != a ? a : nullptr);
   } else {
     if (hipMemcpyAsync(tmp, b, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = LOLHIP_ERR_HIP;
     if (!rc && c != a && hipMemcpyAsync(c, a, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = LOLHIP_ERR_HIP;
@@ -547,7 +552,7 @@ int keyswitch_impl(const Plan& P, hipStream_t stream, const int64_t* c2_pow, int
     const bool split2 = !fused2 && P.pow2_part && !sw(SW_NO_POW2_PART);
     // the key-switch kernel holds two accumulator sets per coefficient: 20-element vectors only at <= 12 coefficients per thread
     const bool big_ok = mixed_keyswitch_big_ok(P.n);
-    const StageProgram& pf = fused2 ? fused_crt(P, big_ok) : zq_crt(P, big_ok);
+    const StageProgram& pf = fused2 ? fused_crt(P, false, big_ok) : zq_crt(P, false, big_ok);
     if (!split2 && (fused2 || use_mixed(P, pf))) {
       MixedKeySwitchLaunch l;
       l.stream = stream; l.c2 = c2_pow; l.hint = hint; l.addend = addend; l.out = out; l.B = B; l.T = P.T; l.n = P.n;

@@ -11,17 +11,7 @@ namespace {
 
 const i64 kInvalid = -1, kModulus = -2;
 
-// ascending primes with positive exponents, index below 2^31
-bool pps_ok(const std::vector<PP>& pps) {
-  unsigned __int128 m = 1;
-  int last = 1;
-  for (const PP& pe : pps) {
-    if (pe.p <= last || pe.e < 1 || !is_prime((u64)pe.p)) return false;
-    last = pe.p;
-    for (int i = 0; i < pe.e; ++i) { m *= (u64)pe.p; if (m >> 31) return false; }
-  }
-  return true;
-}
+const u64 kMaxIndex = ((u64)1 << 31) - 1;   // every index here is below 2^31
 
 // indexToPow (Tensor.hs:359-362)
 i64 index_to_pow(int p, int e, i64 j) { return ipow(p, e - 1) * (j % (p - 1)) + digit_rev(p, e - 1, j / (p - 1)); }
@@ -234,7 +224,7 @@ u64 pow_below62(u64 b, int e) {
 
 i64 crtset_count(const std::vector<PP>& pps, const std::vector<PP>& pps2, i64 p) {
   std::vector<MergedPP> mp;
-  if (!pps_ok(pps) || !pps_ok(pps2) || !merge_pps(pps, pps2, mp)) return kInvalid;
+  if (!valid_pps(pps, kMaxIndex) || !valid_pps(pps2, kMaxIndex) || !merge_pps(pps, pps2, mp)) return kInvalid;
   if (p < 2 || p >= ((i64)1 << 31) || !is_prime((u64)p)) return kInvalid;
   const u64 m = (u64)value_pps(pps), m2 = (u64)value_pps(pps2);
   if (m2 % (u64)p == 0) return kInvalid;
@@ -348,7 +338,7 @@ bool crtset_bound_ok(const std::vector<PP>& pps2bar, u64 p, u64 pe, u64 Q) {
 }
 
 i64 crtset_modulus(const std::vector<PP>& pps2, i64 p, int e) {
-  if (!pps_ok(pps2) || e < 1 || p < 2 || p >= ((i64)1 << 31) || !is_prime((u64)p)) return kInvalid;
+  if (!valid_pps(pps2, kMaxIndex) || e < 1 || p < 2 || p >= ((i64)1 << 31) || !is_prime((u64)p)) return kInvalid;
   const u64 pe = pow_below62((u64)p, e);
   if (!pe) return kModulus;
   const std::vector<PP> bar = strip_prime(pps2, p);
@@ -380,7 +370,7 @@ void host_l(const std::vector<PP>& pps, u64 mod, i64* y, i64 rows) {
 
 i64 crtset_host(const std::vector<PP>& pps, const std::vector<PP>& pps2, i64 p, int e, std::vector<i64>& out) {
   std::vector<MergedPP> mp;
-  if (e < 1 || !pps_ok(pps) || !pps_ok(pps2) || !merge_pps(pps, pps2, mp)) return kInvalid;
+  if (e < 1 || !valid_pps(pps, kMaxIndex) || !valid_pps(pps2, kMaxIndex) || !merge_pps(pps, pps2, mp)) return kInvalid;
   const std::vector<PP> bar = strip_prime(pps, p), bar2 = strip_prime(pps2, p);
   std::vector<i64> x;
   const i64 K = crtset_dec(bar, bar2, p, x);

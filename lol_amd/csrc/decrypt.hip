@@ -12,16 +12,14 @@
 //     v_i = (x_i - sum_{j<i} v_j P_j) * P_i^-1   mod q_i
 // where the inner sum is a Horner chain over the constants q_j mod q_i: i rem128 steps for digit i, O(T^2) per
 // coefficient, no wide integers.  X is negative as a centred value iff X > floor((Q-1)/2), which a most-significant
-// first comparison of the digits decides.  The constants that do not depend on p live in the plan (plan.h
-// lift_consts); the p-dependent ones travel by value in LiftParams.
+// first comparison of the digits decides (garner_digits and above_half, elementwise_dev.h).  The constants that do
+// not depend on p live in the plan (plan.h lift_consts); the p-dependent ones travel by value in LiftParams.
 #include <hip/hip_runtime.h>
 
 #include "elementwise_dev.h"
 #include "pipeline.h"
 
 namespace lolhip {
-
-typedef unsigned __int128 u128;
 
 namespace {
 constexpr int EPT = 2;                       // elements per thread (k_sk_eval, k_addmod)
@@ -113,26 +111,14 @@ k_lift(const i64* __restrict__ in, const i64* __restrict__ add, i64* __restrict_
   const i64 r = (i64)blockIdx.x * LIFT_TILE + threadIdx.x;
   if (r >= rows) return;
   u64 v[NT];
-#pragma unroll
-  for (int i = 0; i < NT; ++i) {
+  garner_digits<NT>(v, [&](int i) {
     const ModCtx mc = mod[i];
     u64 x = canon_in(in[r * NT + i], mc.q);
     if (add) x = addmod(x, canon_in(add[r * NT + i], mc.q), mc.q);
     if (p.msd) x = mulmod(x, p.scale[i], mc);
-    u64 s = 0;                                // sum_{j<i} v_j P_j mod q_i, Horner from the top digit
-#pragma unroll
-    for (int j = i - 1; j >= 0; --j) {
-      const u128 t = (u128)s * qmod[i * NT + j] + v[j];          // < q_i^2 + 2^62 < q_i 2^64
-      s = rem128((u64)(t >> 64), (u64)t, mc);
-    }
-    v[i] = i == 0 ? x : mulmod(submod(x, s, mc.q), pinv[i], mc);
-  }
-  bool neg = false, decided = false;          // X > floor((Q-1)/2), most significant digit first
-#pragma unroll
-  for (int i = NT - 1; i >= 0; --i) {
-    const u64 h = half[i];
-    if (!decided && v[i] != h) { neg = v[i] > h; decided = true; }
-  }
+    return x;
+  }, mod, pinv, qmod, NT);
+  const bool neg = above_half<NT>(v, half);
   if constexpr (PMODE) {
     u128 acc = 0;                             // sum v_i (P_i mod p): 16 terms below 2^124 each
 #pragma unroll

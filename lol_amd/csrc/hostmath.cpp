@@ -95,6 +95,27 @@ std::vector<PP> factor_pps(u64 m) {
   return out;
 }
 
+bool valid_pps(const std::vector<PP>& pps, u64 max_m) {
+  int last = 1;
+  u64 m = 1;
+  for (const PP& pe : pps) {
+    if (pe.p <= last || pe.e < 1 || !is_prime((u64)pe.p)) return false;
+    last = pe.p;
+    for (int e = 0; max_m && e < pe.e; ++e) {
+      if (m > max_m / (u64)pe.p) return false;
+      m *= (u64)pe.p;
+    }
+  }
+  return true;
+}
+
+bool to_pps(const lolhip_pp* pps, int npps, std::vector<PP>& out) {
+  out.clear();
+  if (npps < 0 || (npps > 0 && !pps)) return false;
+  for (int i = 0; i < npps; ++i) out.push_back(PP{pps[i].prime, pps[i].exponent});
+  return true;
+}
+
 i64 ipow(i64 b, int e) { i64 r = 1; while (e-- > 0) r *= b; return r; }
 i64 value_pps(const std::vector<PP>& pps) { i64 m = 1; for (auto& pe : pps) m *= ipow(pe.p, pe.e); return m; }
 i64 totient_pp(int p, int e) { return e == 0 ? 1 : (p - 1) * ipow(p, e - 1); }

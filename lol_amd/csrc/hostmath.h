@@ -14,6 +14,8 @@
 #include <utility>
 #include <vector>
 
+#include "lolhip.h"
+
 namespace lolhip {
 
 typedef uint64_t u64;
@@ -21,6 +23,18 @@ typedef int64_t i64;
 typedef unsigned __int128 u128;
 
 struct PP { int p; int e; };
+
+// a prime-power list as every entry point takes it: ascending primes, exponents >= 1 and, for max_m != 0, the index
+// prod p^e at most max_m
+bool valid_pps(const std::vector<PP>& pps, u64 max_m = 0);
+// the list behind a C array (not validated); false for a negative count or a null array with a positive one
+bool to_pps(const lolhip_pp* pps, int npps, std::vector<PP>& out);
+// the same prime powers in the same order
+inline bool same_pps(const std::vector<PP>& a, const std::vector<PP>& b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); ++i) if (a[i].p != b[i].p || a[i].e != b[i].e) return false;
+  return true;
+}
 
 inline u64 mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
 u64 powmod(u64 b, u64 e, u64 q);

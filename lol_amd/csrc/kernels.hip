@@ -14,6 +14,7 @@
 //   k_gather / k_twace_crt   twace*/embed* (Extension.hs:54-129)
 //
 // Layout at the boundary is the reference's: y[(b*n + j)*T + t] (tensor.h:69).
+#include "elementwise_dev.h"
 #include "pow2_impl.h"
 
 namespace lolhip {
@@ -482,7 +483,6 @@ k_pointwise_mul(i64* __restrict__ a, const i64* __restrict__ b, i64 total, i64 b
   }
 }
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 // the same, two consecutive elements (16 bytes) per lane and access: even total and period, 16-byte-aligned
 // slabs (whatever T: the two elements of a pair take their own modulus)
 constexpr int PW2_K = 4;                    // pairs per thread
@@ -521,7 +521,7 @@ k_pointwise_mul2(i64* __restrict__ a, const i64* __restrict__ b, i64 total, i64 
 
 hipError_t launch_pointwise_mul(hipStream_t s, i64* a, const i64* b, i64 total, i64 bperiod, int T, const ModCtx* mod) {
   if (total == 0) return hipSuccess;
-  if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0 && total % 2 == 0 && (bperiod >= total || bperiod % 2 == 0)) {
+  if (aligned16(a, b) && total % 2 == 0 && (bperiod >= total || bperiod % 2 == 0)) {
     const i64 blocks = (total + 512 * PW2_K - 1) / (512 * PW2_K);
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_pointwise_mul2, dim3((unsigned)blocks), dim3(256), 0, s, a, b, total, bperiod, T, mod);
@@ -555,7 +555,7 @@ k_copy16(u32x4* __restrict__ dst, const u32x4* __restrict__ src, u64 nvec) {
 }
 hipError_t launch_copy16(hipStream_t s, void* dst, const void* src, size_t bytes, int variant) {
   if (bytes == 0) return hipSuccess;
-  if ((((uintptr_t)dst | (uintptr_t)src) & 15) || bytes % 16) return hipErrorInvalidValue;
+  if (!aligned16(dst, src) || bytes % 16) return hipErrorInvalidValue;
   const u64 nvec = bytes / 16, ntiles = (nvec + 1023) / 1024;
   if (variant == 1) hipLaunchKernelGGL((k_copy16<true>), dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), 0, s, (u32x4*)dst, (const u32x4*)src, nvec);
   else if (ntiles > 0x7fffffff) return hipErrorInvalidValue;
@@ -585,7 +585,6 @@ static TileArgs tile_args(i64 n_out, int T, int TW, int K) {
   t.tiles = (u32)((chunks + 256 * K - 1) / (256 * K));
   return t;
 }
-static bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 // out[b][i][t] = +-in[b][idx[i]][t] or 0  (embedPow/Dec/CRT, twacePowDec; Extension.hs:54-101)
 constexpr int GA_K = 4;
@@ -742,7 +741,7 @@ k_twace_crt(i64* __restrict__ out, const i64* __restrict__ in, const int32_t* __
 hipError_t launch_twace_crt(hipStream_t s, i64* out, const i64* in, const int32_t* idx, const i64* tweak, i64 B,
                             i64 n_out, i64 n_in, int T, const ModCtx* mod) {
   if (B * n_out * T == 0) return hipSuccess;
-  const int TW = (T % 2 == 0 && aligned16(out, in) && aligned16(tweak, tweak)) ? 2 : 1;
+  const int TW = (T % 2 == 0 && aligned16(out, in, tweak)) ? 2 : 1;
   const TileArgs ta = tile_args(n_out, T, TW, TC_K);
   const i64 blocks = B * ta.tiles;
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;

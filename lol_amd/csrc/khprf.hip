@@ -32,17 +32,13 @@ constexpr int TPB = 256;
 constexpr int KG = 4;          // slots of v per thread that share one right slot
 constexpr int JG = 4;          // output entries per thread
 constexpr i64 MAX_BLOCKS = 1 << 20;
-typedef unsigned __int128 u128;
 
 __device__ __forceinline__ i64 child_slot(i64 w_v, const KhprfChild& ch) {
   const i64 w = w_v >> ch.shift;
   return ch.full ? (w & ch.mask) : w - ch.lo;
 }
 
-unsigned grid_for(i64 total) {
-  const i64 b = (total + TPB - 1) / TPB;
-  return (unsigned)(b < 1 ? 1 : (b < MAX_BLOCKS ? b : MAX_BLOCKS));
-}
+unsigned grid_for(i64 total) { return grid_stride_blocks(total, TPB, MAX_BLOCKS); }
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
@@ -200,8 +196,7 @@ __device__ __forceinline__ i64 lift_one(i64 x, const KhprfLift& c) {
   u64 r;
   if constexpr ((MODE & LIFT_FROM_Q) != 0) {
     const u64 xq = canon_in(x, c.Q);
-    const i64 v = 2 * xq < c.Q ? (i64)xq : (i64)xq - (i64)c.Q;
-    r = (u64)v & mask;
+    r = (u64)centred(xq, c.Q) & mask;
   } else {
     r = (u64)x & mask;
   }
@@ -240,7 +235,7 @@ hipError_t launch_khprf_lift(hipStream_t s, const i64* src, i64* dst, i64 total,
   if (total == 0) return hipSuccess;
   if (c.qbits < 1 || c.qbits > 62) return hipErrorInvalidValue;
   if ((mode & LIFT_ROUND) && ((mode & LIFT_TO_Q) || c.p < 2)) return hipErrorInvalidValue;
-  const bool v2 = ((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0;
+  const bool v2 = aligned16(src, dst);
   const unsigned grid = grid_for(v2 ? (total + 1) >> 1 : total);
 #define LOLHIP_LIFT(M)                                                                                      \
   do {                                                                                                       \

@@ -110,9 +110,8 @@ k_unit_rows(i64* __restrict__ out, const int32_t* __restrict__ coeffs, i64 rel, 
 hipError_t launch_unit_rows(hipStream_t s, i64* out, const int32_t* coeffs, i64 rel, i64 n, int T, i64 n_lo) {
   const i64 total = rel * n * T;
   if (total == 0) return hipSuccess;
-  const i64 blocks = (total + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_unit_rows, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(TPB), 0, s, out, coeffs, rel, n,
-                     T, n_lo);
+  hipLaunchKernelGGL(k_unit_rows, dim3(grid_stride_blocks(total, TPB, 2048)), dim3(TPB), 0, s, out, coeffs, rel, n, T,
+                     n_lo);
   return hipGetLastError();
 }
 

@@ -99,8 +99,8 @@ hipError_t launch_modswitch(hipStream_t s, const i64* in0, i64 rows0, const i64*
     return hipErrorInvalidValue;
   unsigned blocks;
   if (!tiles_for(rows, TPB, &blocks)) return hipErrorInvalidValue;
-  const bool vin = (p.T & 1) == 0 && ((((uintptr_t)in0) | ((uintptr_t)in)) & 15) == 0;
-  const bool vout = (To & 1) == 0 && (((uintptr_t)out) & 15) == 0;
+  const bool vin = (p.T & 1) == 0 && aligned16(in0, in);
+  const bool vout = (To & 1) == 0 && aligned16(out);
   const dim3 grid(blocks), block(TPB);
 #define LOLHIP_MS(SS)                                                                                             \
   case SS:                                                                                                        \

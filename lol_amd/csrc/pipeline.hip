@@ -20,7 +20,6 @@
 
 namespace lolhip {
 
-typedef unsigned __int128 u128;
 
 // Every kernel here walks a flat element index g.  A workgroup owns one tile of 256 * EPT
 // consecutive elements; whatever has to be divided out of g (position inside the polynomial,
@@ -142,7 +141,7 @@ hipError_t launch_decompose(hipStream_t s, const i64* c, i64* digits, i64 B, i64
   unsigned blocks;
   if (!tiles_for(rows, TILE, &blocks)) return hipErrorInvalidValue;
   const bool fast = q32 && p.base <= ((i64)1 << 31);
-  const bool v2 = p.T == 2 && (((uintptr_t)digits) & 15) == 0;
+  const bool v2 = p.T == 2 && aligned16(digits);
 #define LOLHIP_DEC(QQ, VV) hipLaunchKernelGGL((k_decompose<QQ, VV>), dim3(blocks), dim3(256), 0, s, c, digits, rows, p, mod)
   if (fast) { if (v2) LOLHIP_DEC(true, true); else LOLHIP_DEC(true, false); }
   else { if (v2) LOLHIP_DEC(false, true); else LOLHIP_DEC(false, false); }

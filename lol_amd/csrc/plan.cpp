@@ -105,15 +105,6 @@ struct RuView {
 
 }  // namespace
 
-static bool valid_pps(const std::vector<PP>& pps) {
-  int last = 1;
-  for (auto& pe : pps) {
-    if (pe.p <= last || pe.e < 1 || !is_prime((u64)pe.p)) return false;
-    last = pe.p;
-  }
-  return true;
-}
-
 // The CRT / CRT^-1 stage programs of index m = prod pps over ring R, constants appended to `pool`
 // (tensor.h:76-95 over crt.cpp:459-560).  The Stage lists depend on pps only; called once per
 // ring with pools that share a prefix, the offsets agree, so ONE stage list serves Z_q and C.

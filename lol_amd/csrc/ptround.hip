@@ -17,7 +17,6 @@
 namespace lolhip {
 
 namespace {
-typedef unsigned __int128 u128;
 
 constexpr int TPB = 256;
 constexpr int EPT = 2;                       // accesses per thread
@@ -121,8 +120,7 @@ hipError_t launch_ct_affine_mul(hipStream_t s, const i64* a, i64 a_pair, const i
   if (slab == 0 || npairs == 0) return hipSuccess;
   if (T < 1 || T > PIPE_MAX_T || per > 0x7fffffff || npairs < 0 || npairs > 65535 || a_pair < 0 || b_pair < 0)
     return hipErrorInvalidValue;
-  const uintptr_t ptrs = (uintptr_t)a | (uintptr_t)b | (uintptr_t)va | (uintptr_t)vb | (uintptr_t)out | (uintptr_t)gcrt;
-  const bool v2 = (per & 1) == 0 && ((a_pair | b_pair) & 1) == 0 && (ptrs & 15) == 0;
+  const bool v2 = (per & 1) == 0 && ((a_pair | b_pair) & 1) == 0 && aligned16(a, b, va, vb, out, gcrt);
   unsigned blocks;
   if (!tiles_for(slab, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
 #define LOLHIP_AM(VV, AA, BB)                                                                                     \

@@ -22,8 +22,6 @@ bool drops_first(const Plan& a, const Plan& b) {
   return true;
 }
 
-i64 even(i64 x) { return x + (x & 1); }
-
 constexpr int PTROUND_MAX_E = 16;                            // p <= 2^16: at most 2^13 pairs in one launch
 
 }  // namespace

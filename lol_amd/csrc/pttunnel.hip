@@ -14,18 +14,12 @@ namespace {
 constexpr int TPB = 256;
 constexpr i64 MAX_BLOCKS = 1 << 16;     // grid-stride above: 256 CUs x 8 waves are covered many times over
 
-unsigned grid_for(i64 total) {
-  const i64 b = (total + TPB - 1) / TPB;
-  return (unsigned)(b < 1 ? 1 : (b < MAX_BLOCKS ? b : MAX_BLOCKS));
-}
+unsigned grid_for(i64 total) { return grid_stride_blocks(total, TPB, MAX_BLOCKS); }
 
 template <bool FROMQ, bool POW2>
 __device__ __forceinline__ u64 relift_res(i64 x, const Relift& c) {
   i64 v = x;
-  if constexpr (FROMQ) {
-    const u64 xq = canon_in(x, c.Qin);
-    v = 2 * xq < c.Qin ? (i64)xq : (i64)xq - (i64)c.Qin;
-  }
+  if constexpr (FROMQ) v = centred(canon_in(x, c.Qin), c.Qin);
   if constexpr (POW2) return (u64)v & (c.pe.q - 1);
   return mod_any(v, c.pe);
 }
@@ -73,7 +67,7 @@ k_embed_rows(const i64* in, i64* out, const int32_t* idx, i64 rows, i64 n_in, i6
 hipError_t launch_relift(hipStream_t s, const i64* src, i64* res, i64* lift, i64 total, const Relift& c) {
   if (total == 0) return hipSuccess;
   if (total < 0 || !src || (!res && !lift) || c.pe.q < 2 || (lift && c.Qout < c.pe.q)) return hipErrorInvalidValue;
-  const bool v2 = ((((uintptr_t)src) | ((uintptr_t)res) | ((uintptr_t)lift)) & 15) == 0;
+  const bool v2 = aligned16(src, res, lift);
   const unsigned grid = grid_for(v2 ? (total + 1) >> 1 : total);
   const bool fromq = c.Qin != 0, pow2 = c.pebits != 0;
 #define LOLHIP_RELIFT(F, P)                                                                                     \

@@ -25,21 +25,6 @@ struct lolhip_pt_tunnel {
 
 namespace {
 
-typedef unsigned __int128 u128;
-
-bool to_pps(const lolhip_pp* pps, int npps, std::vector<PP>& out) {
-  out.clear();
-  if (npps < 0 || (npps > 0 && !pps)) return false;
-  for (int i = 0; i < npps; ++i) out.push_back(PP{pps[i].prime, pps[i].exponent});
-  return true;
-}
-
-bool same_pps(const std::vector<PP>& a, const std::vector<PP>& b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); ++i) if (a[i].p != b[i].p || a[i].e != b[i].e) return false;
-  return true;
-}
-
 // K rows of n words -> min(K, cap) rows of out
 int64_t copy_rows(const std::vector<i64>& src, int64_t K, int64_t* out, int64_t cap) {
   if (K > 0 && out && cap > 0) {
@@ -74,8 +59,6 @@ struct DevBuf {
   ~DevBuf() { if (p) (void)hipFree(p); }
   bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess; }
 };
-
-int64_t even(int64_t x) { return (x + 1) & ~(int64_t)1; }
 
 }  // namespace
 

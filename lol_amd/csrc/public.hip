@@ -79,7 +79,7 @@ hipError_t launch_ct_lincomb(hipStream_t s, const i64* a, int na, const i64* b, 
   const i64 total = (i64)nc * slab;
   if (total == 0) return hipSuccess;
   if (sc.T < 1 || sc.T > PIPE_MAX_T || slab % sc.T) return hipErrorInvalidValue;
-  const bool v2 = (slab & 1) == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out)) & 15) == 0;
+  const bool v2 = (slab & 1) == 0 && aligned16(a, b, out);
   unsigned blocks;
   if (!tiles_for(total, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
   const bool hb = b && nb > 0;
@@ -115,8 +115,7 @@ hipError_t launch_pub_lift(hipStream_t s, const i64* in, i64 stride, i64 items, 
   const i64 rows = items * n;
   if (rows == 0) return hipSuccess;
   if (T < 1 || mul >= mp.q) return hipErrorInvalidValue;
-  const i64 b = (rows + TPB - 1) / TPB;
-  const unsigned grid = (unsigned)(b < (1 << 20) ? b : (1 << 20));
+  const unsigned grid = grid_stride_blocks(rows, TPB, 1 << 20);
   hipLaunchKernelGGL(k_pub_lift, dim3(grid), dim3(TPB), 0, s, in, stride, n, out, rows, T, mod, mp, mul);
   return hipGetLastError();
 }
@@ -187,7 +186,7 @@ hipError_t launch_pub_apply(hipStream_t s, int mode, const i64* a, i64 a_item, c
   if (total == 0) return hipSuccess;
   if (T < 1 || T > PIPE_MAX_T || per > 0x7fffffff || (mode != PUB_MUL && mode != PUB_ADD)) return hipErrorInvalidValue;
   const i64 c_item = c_shared ? 0 : per, c_comp = c_shared ? per : B * per;
-  const bool v2 = (per & 1) == 0 && ((((uintptr_t)c) | ((uintptr_t)out)) & 15) == 0;
+  const bool v2 = (per & 1) == 0 && aligned16(c, out);
   unsigned blocks;
   if (!tiles_for(total, (i64)TPB * EPT * (v2 ? 2 : 1), &blocks)) return hipErrorInvalidValue;
 #define LOLHIP_PA(MM, VV)                                                                                       \

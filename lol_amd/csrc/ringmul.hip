@@ -49,7 +49,7 @@ __device__ __forceinline__ u64 fold_word(const u64* xs, const ModCtx& mc, int t,
   u64 x[K], v[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) x[k] = canon_in((i64)xs[k], c.Q[k].q);
-  garner_digits<K>(v, x, c.Q, c.pinv, c.qmod, RING_MAX_K);
+  garner_digits<K>(v, [&](int k) { return x[k]; }, c.Q, c.pinv, c.qmod, RING_MAX_K);
   const bool neg = above_half<K>(v, c.half);
   if constexpr (POW2) {
     u64 acc = v[0];                            // mod 2^64, of which q_t is a divisor
@@ -156,7 +156,7 @@ bool params_ok(const i64* in, const i64* out, i64 rows, i64 n, const RingMul& c)
 
 #define LOLHIP_RING_LAUNCH(KERNEL)                                                                                  \
   do {                                                                                                              \
-    const bool v2 = ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0 && n % 2 == 0;                                 \
+    const bool v2 = aligned16(in, out) && n % 2 == 0;                                                               \
     const Shape sh = shape_for(rows, v2 ? n / 2 : n);                                                               \
     const bool p2 = c.pow2 != 0;                                                                                    \
     switch (c.K * 4 + (p2 ? 2 : 0) + (v2 ? 1 : 0)) {                                                                \

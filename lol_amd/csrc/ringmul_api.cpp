@@ -44,6 +44,7 @@ bool operator<(const Wide& a, const Wide& b) {
 }
 
 const u64 PRIME_CAP = (u64)1 << 61;
+const u64 MAX_INDEX = (u64)1 << 30;          // the largest m lolhip_ringmul_moduli looks for primes at
 
 // 2 C_m H^2, H = max_t floor(q_t / 2); false when the growth constant saturates or a modulus is out of range
 bool product_bound(const std::vector<PP>& pps, const std::vector<u64>& qs, Wide& bound) {
@@ -78,22 +79,6 @@ u64 root_up(const Wide& bound, int k) {
   return hi;
 }
 
-bool valid_pps(const std::vector<PP>& pps) {
-  int last = 1;
-  i64 m = 1;
-  for (const PP& pe : pps) {
-    if (pe.p <= last || pe.e < 1 || !is_prime((u64)pe.p)) return false;
-    last = pe.p;
-    for (int e = 0; e < pe.e; ++e) {
-      if (m > ((i64)1 << 30) / pe.p) return false;
-      m *= pe.p;
-    }
-  }
-  return true;
-}
-
-int64_t even(int64_t x) { return (x + 1) & ~(int64_t)1; }
-
 int64_t slab(const lolhip_ringmul* h, int64_t B) { return B * h->rm.T * h->pQ->P.n * h->rm.K; }
 
 // INVALID for a batch whose rows or pointwise period leave 31 bits
@@ -104,10 +89,8 @@ bool batch_fits(const lolhip_ringmul* h, int64_t B) { return B <= 0x7fffffff / h
 extern "C" {
 
 int lolhip_ringmul_moduli(const lolhip_pp* pps, int npps, const int64_t* qs, int T, int64_t Qs[3]) {
-  if (npps < 0 || (npps > 0 && !pps) || !qs || T < 1 || !Qs) return LOLHIP_ERR_INVALID;
   std::vector<PP> f;
-  for (int i = 0; i < npps; ++i) f.push_back(PP{pps[i].prime, pps[i].exponent});
-  if (!valid_pps(f)) return LOLHIP_ERR_INVALID;
+  if (!to_pps(pps, npps, f) || !qs || T < 1 || !Qs || !valid_pps(f, MAX_INDEX)) return LOLHIP_ERR_INVALID;
   std::vector<u64> q;
   for (int t = 0; t < T; ++t) {
     if (qs[t] < 2 || qs[t] >= ((int64_t)1 << 62)) return LOLHIP_ERR_MODULUS;

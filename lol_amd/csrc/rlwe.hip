@@ -23,7 +23,6 @@
 
 namespace lolhip {
 
-typedef unsigned __int128 u128;
 typedef __int128 i128;
 
 namespace {

@@ -42,12 +42,10 @@ inline int run_prog_or_copy(const Plan& P, const StageProgram& sp, hipStream_t s
 }
 
 // the same index with the same tensor order: m and every (p, e)
-inline bool same_index(const Plan& a, const Plan& b) {
-  if (a.m != b.m || a.pps.size() != b.pps.size()) return false;
-  for (size_t i = 0; i < a.pps.size(); ++i)
-    if (a.pps[i].p != b.pps[i].p || a.pps[i].e != b.pps[i].e) return false;
-  return true;
-}
+inline bool same_index(const Plan& a, const Plan& b) { return a.m == b.m && same_pps(a.pps, b.pps); }
+
+// x rounded up to an even count of words: work-buffer regions keep the 16-byte alignment of the buffer
+inline int64_t even(int64_t x) { return (x + 1) & ~(int64_t)1; }
 
 // floor(2^32 (2^l - base) / base) + 1, l = ceil(log2 base): the 32-bit invariant-divisor constant of the fused key
 // switches (1 for TrivGad, base = 0)

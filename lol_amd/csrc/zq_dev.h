@@ -28,6 +28,7 @@ namespace lolhip {
 typedef uint64_t u64;
 typedef uint32_t u32;
 typedef int64_t i64;
+typedef unsigned __int128 u128;
 
 // Per-modulus context for exact (a*b) mod q with arbitrary operands.
 struct ModCtx {
@@ -51,14 +52,14 @@ inline ModCtx make_modctx(u64 q) {
   c.q = q;
   c.s = (u32)__builtin_clzll(q);
   c.d = q << c.s;
-  c.v = (u64)((~(unsigned __int128)0) / c.d - ((unsigned __int128)1 << 64));
+  c.v = (u64)((~(u128)0) / c.d - ((u128)1 << 64));
   c.pad = 0;
   c.r32 = c.r32p = 0;
   if (q < ((u64)1 << 32)) {
     c.r32 = (u32)((((u64)1) << 32) % q);
     c.r32p = (u32)((((u64)c.r32) << 32) / q);
   }
-  c.mu = (u64)((((unsigned __int128)1) << 64) / q);
+  c.mu = (u64)((((u128)1) << 64) / q);
   c.nqinv = 0;
   if (q & 1) {                       // Newton iteration: x <- x (2 - q x), doubling the correct low bits
     u64 x = q;                       // q * q = 1 mod 8: three correct bits
@@ -70,7 +71,7 @@ inline ModCtx make_modctx(u64 q) {
 inline ShoupW make_shoup(u64 w, u64 q) {
   ShoupW s;
   s.w = w;
-  s.wp = (u64)((((unsigned __int128)w) << 64) / q);
+  s.wp = (u64)((((u128)w) << 64) / q);
   return s;
 }
 
@@ -256,7 +257,7 @@ LH_D u64 rem128(u64 x1, u64 x0, const ModCtx& c) {
   u64 u1 = (x1 << c.s) | (x0 >> (64 - c.s));
   u64 u0 = x0 << c.s;
   // Moeller-Granlund 2-by-1 division step
-  unsigned __int128 qq = (unsigned __int128)c.v * u1 + (((unsigned __int128)u1 << 64) | u0);
+  u128 qq = (u128)c.v * u1 + (((u128)u1 << 64) | u0);
   u64 q1 = (u64)(qq >> 64) + 1, q0 = (u64)qq;
   u64 r = u0 - q1 * c.d;
   if (r > q0) r += c.d;
@@ -266,7 +267,7 @@ LH_D u64 rem128(u64 x1, u64 x0, const ModCtx& c) {
 
 // exact a*b mod q, a,b < q
 LH_D u64 mulmod(u64 a, u64 b, const ModCtx& c) {
-  unsigned __int128 z = (unsigned __int128)a * b;
+  u128 z = (u128)a * b;
   return rem128((u64)(z >> 64), (u64)z, c);
 }
 

@@ -47,7 +47,7 @@ def _centred(x, Q):
 # 1. the lift at its boundaries
 # ---------------------------------------------------------------------------------------------
 LIFT_CASES = [(2 ** 11, 1, 61), (2 ** 11, 2, 59), (2 ** 12, 4, 59), (64, 16, 61), (45, 3, 30), (45, 16, 20),
-              (11648, 2, 30), (15015, 4, 59), (2 ** 10, 3, 20)]
+              (11648, 2, 30), (15015, 4, 59), (2 ** 10, 3, 20)] + [(45, T, 20) for T in range(5, 16)]
 
 
 def _boundary_values(Q, rng, count):

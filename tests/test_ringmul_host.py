@@ -157,3 +157,52 @@ def test_work_len_and_compute_statuses_on_host_only_plans(lolhip):
         for call in (lambda: rm(a, a), lambda: rm.prepare(a), lambda: rm.mulPrepared(a, np.zeros((2 * T, n, K), dtype=np.int64))):
             with pytest.raises(lolhip.NoDeviceError):
                 call()
+
+
+# ---------------------------------------------------------------------------------------------
+# prime-power lists at every entry that validates one (valid_pps / to_pps, hostmath.h)
+# ---------------------------------------------------------------------------------------------
+_BELOW_2_30 = [(3, 2), (7, 1), (11, 1), (31, 1), (151, 1), (331, 1)]                  # 2^30 - 1
+_ABOVE_2_30 = [(5, 2), (13, 1), (41, 1), (61, 1), (1321, 1)]                          # 2^30 + 1
+# list -> the statuses of lolhip_plan_create (host_only, q = 257), lolhip_ringmul_moduli (q = 2),
+# lolhip_crtset_modulus (p = 2, e = 1) and lolhip_pt_tunnel_modulus (p = 2, e = 1) with the list as S (R empty, first
+# hop) and as R (S = [(7, 1)]).  The index caps: none for a plan (its own rule is n <= 2^24), m <= 2^30 for ringmul,
+# m < 2^31 for crtSet; the tunnel bound converts its lists without validating them.
+PPS_STATUSES = [
+    ("descending primes", [(3, 1), (2, 2)], (INVALID, INVALID, INVALID, 24, 264)),
+    ("a repeated prime", [(2, 1), (2, 1)], (INVALID, INVALID, INVALID, 2, 132)),
+    ("exponent 0", [(2, 2), (3, 0)], (INVALID, INVALID, INVALID, 8, 264)),
+    ("a composite prime", [(2, 1), (9, 1)], (INVALID, INVALID, INVALID, 240, 264)),
+    ("empty", [], (OK, 1, 3, 2, 132)),
+    ("valid", [(2, 2), (3, 1)], (OK, 1, 7, 24, 264)),
+    ("2^30 - 1", _BELOW_2_30, (INVALID, 1, 53687091151, MODULUS, 8448)),
+    ("2^30 + 1", _ABOVE_2_30, (INVALID, INVALID, 45097156651, MODULUS, 4224)),
+    ("2^31 - 2", [(2, 1)] + _BELOW_2_30, (INVALID, INVALID, 53687091151, MODULUS, 8448)),
+    ("2^31 + 2", [(2, 1)] + _ABOVE_2_30, (INVALID, INVALID, INVALID, MODULUS, 4224)),
+]
+
+
+@pytest.mark.parametrize("name,pps,want", PPS_STATUSES, ids=[c[0] for c in PPS_STATUSES])
+def test_prime_power_list_validation_at_every_entry(lolhip, name, pps, want):
+    L = lolhip.lib()
+    from lol_amd.tensor import _pps as arr
+    _, a, n = arr(pps)
+    q = lambda *v: (C.c_int64 * len(v))(*v)
+    assert math.prod(p ** e for p, e in _BELOW_2_30) == 2 ** 30 - 1 and math.prod(p ** e for p, e in _ABOVE_2_30) == 2 ** 30 + 1
+    h = C.c_void_p()
+    got = [L.lolhip_plan_create(a, n, q(257), 1, 1, C.byref(h))]
+    if h:
+        L.lolhip_plan_destroy(h)
+    got.append(L.lolhip_ringmul_moduli(a, n, q(2), 1, (C.c_int64 * 3)()))
+    got.append(L.lolhip_crtset_modulus(a, n, 2, 1))
+    (_, none, n0), (_, seven, n7) = arr([]), arr([(7, 1)])
+    got.append(L.lolhip_pt_tunnel_modulus(none, n0, a, n, 1, 1, 2, 1))
+    got.append(L.lolhip_pt_tunnel_modulus(a, n, seven, n7, 1, 0, 2, 1))
+    assert tuple(got) == want
+    # the conversion's own rules: a negative count, and no array behind a positive one
+    assert L.lolhip_plan_create(a, -1, q(257), 1, 1, C.byref(h)) == INVALID
+    assert L.lolhip_plan_create(None, 1, q(257), 1, 1, C.byref(h)) == INVALID
+    assert L.lolhip_ringmul_moduli(a, -1, q(2), 1, (C.c_int64 * 3)()) == INVALID
+    assert L.lolhip_crtset_modulus(a, -1, 2, 1) == INVALID and L.lolhip_crtset_modulus(None, 1, 2, 1) == INVALID
+    assert L.lolhip_pt_tunnel_modulus(a, -1, seven, n7, 1, 0, 2, 1) == INVALID
+    assert L.lolhip_pt_tunnel_modulus(none, n0, None, 1, 1, 1, 2, 1) == INVALID

@@ -327,10 +327,18 @@ def test_wide_encrypt_matches_restatement_and_decrypts(gpu, cpuref, m, m2, p, qs
     assert np.array_equal(pq.decrypt(out_crt, s_crt, pp, ext=x_p, cs_crt=True), want)
 
 
-@pytest.mark.parametrize("m,p,lower,T", [(64, 257, 2 ** 29, 8), (64, 257, 2 ** 20, 16), (45, 181, 2 ** 30, 8),
-                                         (45, 181, 2 ** 59, 16)])
+# every T in 1 .. 16 at m = 64, p = 257 (each k_lift<T, PMODE> instantiation decrypts once), with the smaller of
+# 2^20 / 2^29 as the moduli's lower bound at which the model itself decrypts every step it runs (checked on the host:
+# 2^20 from T = 2 on, 2^29 for the product at T = 1)
+WIDE_DEC = [(64, 257, 2 ** 29, 8), (64, 257, 2 ** 20, 16), (45, 181, 2 ** 30, 8), (45, 181, 2 ** 59, 16),
+            (64, 257, 2 ** 29, 1)] + [(64, 257, 2 ** 20, T) for T in range(2, 16) if T != 8]
+
+
+@pytest.mark.parametrize("m,p,lower,T", WIDE_DEC)
 def test_wide_decrypt_matches_model(gpu, cpuref, m, p, lower, T):
-    """the flow of test_decrypt_matches_model: fresh, MSD, ct x ct, keySwitchQuadCirc, modSwitch"""
+    """the flow of test_decrypt_matches_model: fresh, MSD, ct x ct, keySwitchQuadCirc, modSwitch.  One modulus ends
+    after ct x ct: its only (TrivGad) hint digit carries noise of the size of q, which the model cannot decrypt at
+    2^20 or at 2^29 either, and modSwitch needs a second modulus to drop."""
     pps = lm.factor_pps(m)
     qs = _qs(m, lower, T)
     rng = np.random.default_rng(5000 + m + T)
@@ -347,6 +355,8 @@ def test_wide_decrypt_matches_model(gpu, cpuref, m, p, lower, T):
     prod_ = she.mul(ct1, ct2)
     want = cpuref.polymul(Params(pps, [p]), pt1[..., None], pt2[..., None]).reshape(pt1.shape)
     _gpu_checks(she, pq, pp, prod_, want)
+    if T == 1:
+        return
     _gpu_checks(she, pq, pp, she.key_switch_quad(she.ks_quad_hint(0), 0, prod_), want)
     small, she2 = she.mod_switch_drop_first(ct1, eng(qs[1:]))
     _gpu_checks(she2, gpu.Plan(pps, qs[1:]), pp, small, pt1)

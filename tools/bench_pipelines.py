@@ -56,9 +56,11 @@ def decrypt_leg(gen):
     L = lol_amd.lib()
     st = torch.cuda.current_stream().cuda_stream
     ptr = lambda t: t.data_ptr()
-    # (label, m, m', moduli, p, B, ncs, k): config 3's product; the reference's decBenches shape (Default.hs:43-44)
+    # (label, m, m', moduli, p, B, ncs, k): config 3's product; the reference's decBenches shape (Default.hs:43-44); the
+    # widest lift (k_lift at PIPE_MAX_T moduli)
     for label, m, m2, qs, p, B, ncs, k in (("m'=2^15 T=4 59-bit", 2 ** 15, 2 ** 15, good_qs(2 ** 15, 2 ** 59, 4), 65537, 256, 3, 1),
-                                           ("m=16 in m'=2048 q=1017857", 16, 2048, [1017857], 16, 8192, 2, 0)):
+                                           ("m=16 in m'=2048 q=1017857", 16, 2048, [1017857], 16, 8192, 2, 0),
+                                           ("m'=2^13 T=16 30-bit", 2 ** 13, 2 ** 13, good_qs(2 ** 13, 2 ** 29, 16), 65537, 256, 2, 0)):
         pq = lol_amd.Plan.for_index(m2, qs)
         pp = lol_amd.Plan.for_index(m2, [p])
         x_p = None if m == m2 else lol_amd.Ext(lol_amd.Plan.for_index(m, [p]), pp)
