@@ -690,9 +690,8 @@ int lolhip_evallin_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* s
   if (B < 0 || (B > 0 && (!r_dec || !ys_crt || !out || !work))) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
   const i64 rel = ER.host.phi2 / ER.host.phi;
-  const int T = ER.lo->T;
-  int64_t* tmp_e = work;                                           // [rel][B][n_E][T]
-  int64_t* tmp_s = work + rel * B * ER.host.phi * T;               // [rel][B][n_S][T]
+  Work w(work);
+  const auto [tmp_e, tmp_s] = evallin_work(w, ER, ES, B);
   const Plan* PS = ES.hi;                                          // the S-side plan
   int rc = lolhip_coeffs_batch(x_er, s, tmp_e, r_dec, B);
   if (!rc) rc = lolhip_embed_dec_batch(x_es, s, tmp_s, tmp_e, rel * B);
@@ -706,10 +705,7 @@ int64_t lolhip_tunnel_work_len(const lolhip_ext* x_er, const lolhip_ext* x_es, i
   if (!x_er || !x_es || B < 0) return LOLHIP_ERR_INVALID;
   DecompParams d;
   int rc = make_decomp(*x_es->X.hi, base, d); if (rc) return rc;
-  const ExtPlan &ER = x_er->X, &ES = x_es->X;
-  const i64 rel = ER.host.phi2 / ER.host.phi;
-  const int T = ER.lo->T;
-  return rel * B * (ER.host.phi + ES.host.phi2) * T + (i64)d.L * B * ES.host.phi2 * T;
+  return measure(tunnel_work, x_er->X, x_es->X, d.L, B);
 }
 
 // tunnel (SymmSHE.hs:549-570), the body after toMSD . absorbGFactors: with [c0, c1] the linear
@@ -735,15 +731,15 @@ int lolhip_tunnel_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* st
   hipStream_t s = (hipStream_t)stream;
   const i64 rel = ER.host.phi2 / ER.host.phi;
   const int T = PS.T;
-  const i64 nS = ES.host.phi2, nE = ER.host.phi;
+  const i64 nS = ES.host.phi2;
   const size_t slabS = (size_t)B * nS * T;
-  // c0' into out[0]; out[1] starts at zero
-  rc = lolhip_evallin_batch(x_er, x_es, stream, c0_dec, ys_crt, out, work, B); if (rc) return rc;
+  Work w(work);
+  const TunnelWork tw = tunnel_work(w, ER, ES, d.L, B);
+  int64_t *tmp_e = tw.ev.tmp_e, *tmp_s = tw.ev.tmp_s, *ks_work = tw.dig;
+  // c0' into out[0] (evalLin carves tmp_e and tmp_s for itself first); out[1] starts at zero
+  rc = lolhip_evallin_batch(x_er, x_es, stream, c0_dec, ys_crt, out, tmp_e, B); if (rc) return rc;
   if (hipMemsetAsync(out + slabS, 0, slabS * sizeof(int64_t), s) != hipSuccess) return LOLHIP_ERR_HIP;
   // coefficient vectors of c1 over the relative powerful basis, embedded into S' (powerful basis)
-  int64_t* tmp_e = work;                                   // [rel][B][n_E][T]
-  int64_t* tmp_s = work + rel * B * nE * T;                // [rel][B][n_S][T]
-  int64_t* ks_work = tmp_s + rel * B * nS * T;             // [L][B][n_S][T]
   rc = lolhip_coeffs_batch(x_er, stream, tmp_e, c1_pow, B); if (rc) return rc;
   rc = lolhip_embed_pow_batch(x_es, stream, tmp_s, tmp_e, rel * B); if (rc) return rc;
   const size_t hint_i = (size_t)d.L * 2 * nS * T;          // one coefficient's hint: [L][2][n_S][T]

@@ -70,7 +70,11 @@ int eval_dec(const Plan& P, hipStream_t s, const int64_t* cs, int ncs, bool cs_c
   return run_prog(P, P.prog_linv, s, work, B, nullptr);
 }
 
-int64_t qside_len(const Plan& P, int ncs, int64_t B) { return (int64_t)(ncs > 2 ? ncs - 1 : 1) * B * P.n * P.T; }
+// work: the q side of eval_dec [max(ncs - 1, 1)][B][n'][T] | e [B][n'] residues mod p (decrypt only)
+struct DecWork { int64_t *q, *e; };
+DecWork dec_work(Work& w, const Plan& P, int ncs, int64_t B) {
+  return {w.take((int64_t)(ncs > 2 ? ncs - 1 : 1) * B * P.n * P.T), w.take(B * P.n)};
+}
 
 }  // namespace
 
@@ -78,7 +82,7 @@ extern "C" {
 
 int64_t lolhip_decrypt_work_len(const lolhip_plan* pq, int ncs, int64_t B) {
   if (!pq || ncs < 1 || B < 0) return LOLHIP_ERR_INVALID;
-  return qside_len(pq->P, ncs, B) + B * pq->P.n;
+  return measure(dec_work, pq->P, ncs, B);
 }
 
 int lolhip_error_term_batch(const lolhip_plan* pq, void* stream, const int64_t* cs, int ncs, int cs_crt,
@@ -91,7 +95,7 @@ int lolhip_error_term_batch(const lolhip_plan* pq, void* stream, const int64_t* 
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const int64_t *v, *add;
-  rc = eval_dec(P, s, cs, ncs, cs_crt != 0, s_crt, work, B, &v, &add); if (rc) return rc;
+  rc = eval_dec(P, s, cs, ncs, cs_crt != 0, s_crt, work, B, &v, &add); if (rc) return rc;       // work: the q side alone
   return hip_status(launch_lift(s, v, add, e_dec, B * P.n, lp, false, P.d_lift, P.d_mod));
 }
 
@@ -119,8 +123,9 @@ int lolhip_decrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const int64_t *v, *add;
-  rc = eval_dec(P, s, cs, ncs, cs_crt != 0, s_crt, work, B, &v, &add); if (rc) return rc;
-  int64_t* e = work + qside_len(P, ncs, B);                   // [B][n'] residues mod p
+  Work w(work);
+  const auto [q, e] = dec_work(w, P, ncs, B);
+  rc = eval_dec(P, s, cs, ncs, cs_crt != 0, s_crt, q, B, &v, &add); if (rc) return rc;
   if (launch_lift(s, v, add, e, B * P.n, lp, true, P.d_lift, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
   for (int64_t i = 0; i < k; ++i) {
     rc = run_prog(PP, PP.prog_ginvdec, s, e, B, nullptr); if (rc) return rc;

@@ -7,6 +7,16 @@
 
 using namespace lolhip;
 
+namespace {
+// work: rep [B][n'] | double slab [B][n'] | e residues [B][n'][T], the last two for an index that is not a 2-power
+struct EncWork { int64_t* rep; double* d; int64_t* e; };
+EncWork enc_work(Work& w, const Plan& P, int64_t B) {
+  EncWork r = {w.take(B * P.n), nullptr, nullptr};
+  if (!two_power(P)) { r.d = w.take_f64(B * P.n); r.e = w.take(B * P.n * P.T); }
+  return r;
+}
+}  // namespace
+
 extern "C" {
 
 void lolhip_chacha20_block(const uint8_t key[32], uint32_t counter, const uint32_t nonce[3], uint32_t out[16]) {
@@ -15,12 +25,10 @@ void lolhip_chacha20_block(const uint8_t key[32], uint32_t counter, const uint32
 
 int64_t lolhip_encrypt_work_len(const lolhip_plan* pq, int64_t B) {
   if (!pq || B < 0) return LOLHIP_ERR_INVALID;
-  const Plan& P = pq->P;
-  return two_power(P) ? B * P.n : B * P.n * (2 + P.T);
+  return measure(enc_work, pq->P, B);
 }
 
-// Launch plan (work: rep [B][n'] | double slab [B][n'] | e residues [B][n'][T], the last two for an index that is
-// not a 2-power).  rep = lInv (embedPow pt) over pp, read straight from pt_pow when both are identities.
+// Launch plan.  rep = lInv (embedPow pt) over pp, read straight from pt_pow when both are identities.
 //   CRT out:       error -> c0 slot (residues) -> l -> crt -> k_enc_combine (c^1, c^0 = e^ - c^1 s^)
 //   powerful out:  k_enc_uniform (c^1, -c^1 s^) -> one crtInv of 2B -> c0 += l (reduce e): in the fused pass for a
 //                  2-power, else the rounding pass into work, l, one add pass
@@ -49,9 +57,8 @@ int lolhip_encrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
   const double sigma = deviation(P, svar * ((double)p * (double)p));
   const bool pow2 = two_power(P);
   const int64_t n = P.n, slab = B * n * P.T;
-  int64_t* rep = work;
-  double* d = pow2 ? nullptr : reinterpret_cast<double*>(work + B * n);
-  int64_t* e = pow2 ? nullptr : work + 2 * B * n;
+  Work w(work);
+  const auto [rep, d, e] = enc_work(w, P, B);
   int64_t *c0 = cs_out, *c1 = cs_out + slab;
 
   // rep: the decoding-basis coefficients of embed pt over p

@@ -19,23 +19,38 @@ int hint_status(const Plan& P, double svar, int64_t base, int64_t B, DecompParam
   return LOLHIP_OK;
 }
 
-int64_t hint_work_len(const Plan& P, int64_t L, int64_t B) {
-  return B * L * P.n * (two_power(P) ? P.T : P.T + 1);
+// ksHint's work: e^ [B][L][n][T] | the double slab [B][L][n] of the Gaussian map (an index that is not a 2-power)
+struct HintWork { int64_t* e; double* dbl; };
+HintWork hint_work(Work& w, const Plan& P, int64_t L, int64_t B) {
+  return {w.take(B * L * P.n * P.T), two_power(P) ? nullptr : w.take_f64(B * L * P.n)};
 }
 
-// work: e^ [B][L][n][T] | the double slab [B][L][n] of the Gaussian map (an index that is not a 2-power)
-//   rounded Gaussians (domain 3) -> residues -> l -> one crt of B*L polynomials -> k_kshint_combine (domain 4)
+// rounded Gaussians (domain 3) -> residues -> l -> one crt of B*L polynomials -> k_kshint_combine (domain 4)
 int kshint_launch(const Plan& P, hipStream_t s, const int64_t* s_crt, const int64_t* vals_crt, double svar,
-                  const DecompParams& d, const uint8_t key[32], uint64_t ctr, int64_t* hints, int64_t* work, int64_t B) {
+                  const DecompParams& d, const uint8_t key[32], uint64_t ctr, int64_t* hints, HintWork hw, int64_t B) {
   const int64_t BL = B * d.L;
   const ChaChaKey k = make_key(key);
-  int64_t* e = work;
-  double* dbl = two_power(P) ? nullptr : reinterpret_cast<double*>(work + BL * P.n * P.T);
+  const auto [e, dbl] = hw;
   int rc = sample_error(P, s, dbl, nullptr, 1, e, ENC_WRITE, k, ctr, CHACHA_DOM_HINT_GAUSS, deviation(P, svar), BL);
   if (rc) return rc;
   rc = run_prog_or_copy(P, P.prog_l, s, e, BL); if (rc) return rc;
   rc = do_crt(P, s, e, BL, false); if (rc) return rc;
   return hip_status(launch_kshint_combine(s, e, vals_crt, s_crt, hints, B, P.n, d, P.d_mod, k, ctr));
+}
+
+// tunnelHint's work: comps [rel][n_S][T] | then either (p_i s_in [rel][n_R][T] | evalLin's regions at B = rel) or, once
+// evalLin is done, ksHint's regions of rel rows over the S' plan
+struct TunnelHintWork { int64_t *comps, *sp; EvalLinWork ev; HintWork ks; };
+TunnelHintWork tunnel_hint_work(Work& w, const ExtPlan& ER, const ExtPlan& ES, int64_t L) {
+  const int64_t rel = ER.host.phi2 / ER.host.phi, T = ER.lo->T;
+  TunnelHintWork r;
+  r.comps = w.take(rel * ES.host.phi2 * T);
+  const int64_t m = w.mark();
+  r.sp = w.take(rel * ER.host.phi2 * T);
+  r.ev = evallin_work(w, ER, ES, rel);
+  w.rewind(m);
+  r.ks = hint_work(w, *ES.hi, L, rel);
+  return r;
 }
 
 }  // namespace
@@ -46,7 +61,7 @@ int64_t lolhip_kshint_work_len(const lolhip_plan* pq, int64_t base, int64_t B) {
   if (!pq || B < 0) return LOLHIP_ERR_INVALID;
   DecompParams d;
   const int rc = make_decomp(pq->P, base, d); if (rc) return rc;
-  return hint_work_len(pq->P, d.L, B);
+  return measure(hint_work, pq->P, d.L, B);
 }
 
 int lolhip_kshint_batch(const lolhip_plan* pq, void* stream, const int64_t* s_crt, const int64_t* vals_crt, double svar,
@@ -56,20 +71,15 @@ int lolhip_kshint_batch(const lolhip_plan* pq, void* stream, const int64_t* s_cr
   rc = hint_status(pq->P, svar, base, B, d); if (rc) return rc;
   if (B > 0 && (!s_crt || !vals_crt || !key || !hints_out || !work)) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
-  return kshint_launch(pq->P, (hipStream_t)stream, s_crt, vals_crt, svar, d, key, ctr, hints_out, work, B);
+  Work w(work);
+  return kshint_launch(pq->P, (hipStream_t)stream, s_crt, vals_crt, svar, d, key, ctr, hints_out, hint_work(w, pq->P, d.L, B), B);
 }
 
-// work: comps [rel][n_S][T] | then either (p_i s_in [rel][n_R][T] | evalLin scratch rel * rel * (n_E + n_S) * T)
-// or, once evalLin is done, the ksHint scratch of rel rows over the S' plan
 int64_t lolhip_tunnel_hint_work_len(const lolhip_ext* x_er, const lolhip_ext* x_es, int64_t base) {
   if (!x_er || !x_es) return LOLHIP_ERR_INVALID;
-  const ExtPlan &ER = x_er->X, &ES = x_es->X;
   DecompParams d;
-  const int rc = make_decomp(*ES.hi, base, d); if (rc) return rc;
-  const int64_t rel = ER.host.phi2 / ER.host.phi, T = ER.lo->T, nE = ER.host.phi, nR = ER.host.phi2,
-                nS = ES.host.phi2;
-  const int64_t lin = rel * nR * T + rel * rel * (nE + nS) * T, ks = hint_work_len(*ES.hi, d.L, rel);
-  return rel * nS * T + (lin > ks ? lin : ks);
+  const int rc = make_decomp(*x_es->X.hi, base, d); if (rc) return rc;
+  return measure(tunnel_hint_work, x_er->X, x_es->X, d.L);
 }
 
 // tunnelHint f skout skin (SymmSHE.hs:531-545): comps_i = evalLin f' (s_in p_i) over the relative powerful basis p_i of
@@ -90,17 +100,15 @@ int lolhip_tunnel_hint_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, voi
   if (!ys_crt || !s_in_crt || !s_out_crt || !key || !hints_out || !work) return LOLHIP_ERR_INVALID;
 
   hipStream_t s = (hipStream_t)stream;
-  const int64_t rel = ER.host.phi2 / ER.host.phi, T = PS.T, nR = PR.n, nS = PS.n;
-  int64_t* comps = work;                                           // [rel][n_S][T]
-  int64_t* sp = comps + rel * nS * T;                              // [rel][n_R][T]
-  int64_t* ev = sp + rel * nR * T;                                 // evalLin scratch
-  int64_t* ks = sp;                                                // ksHint scratch, after evalLin
+  const int64_t rel = ER.host.phi2 / ER.host.phi, T = PS.T, nR = PR.n;
+  Work w(work);
+  const auto [comps, sp, ev, ks] = tunnel_hint_work(w, ER, ES, d.L);
   if (launch_unit_rows(s, sp, ER.d_coeffs, rel, nR, (int)T, ER.host.phi) != hipSuccess) return LOLHIP_ERR_HIP;
   rc = do_crt(PR, s, sp, rel, false); if (rc) return rc;
   if (launch_sk_eval(s, sp, 1, true, s_in_crt, sp, rel, nR, (int)T, PR.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
   rc = do_crt(PR, s, sp, rel, true); if (rc) return rc;
   rc = run_prog_or_copy(PR, PR.prog_linv, s, sp, rel); if (rc) return rc;
-  rc = lolhip_evallin_batch(x_er, x_es, stream, sp, ys_crt, comps, ev, rel); if (rc) return rc;
+  rc = lolhip_evallin_batch(x_er, x_es, stream, sp, ys_crt, comps, ev.tmp_e, rel); if (rc) return rc;
   return kshint_launch(PS, s, s_out_crt, comps, svar, d, key, ctr, hints_out, ks, rel);
 }
 

@@ -112,19 +112,39 @@ int need_both(const lolhip_plan* a, const lolhip_plan* b) {
   return rc ? rc : need_device(b);
 }
 
-i64 modswitch_words(const Plan& F, int ncs, int64_t B) { return (i64)ncs * B * F.n * F.T; }
-
 }  // namespace
 
 struct lolhip_tunnel_chain {
   int nhops = 0;
   std::vector<const lolhip_ext*> er, es;
   std::vector<const int64_t*> ys, hints;
+  std::vector<int> L;                                                // digits of the gadget over each S'
   int64_t base = 0;
   const lolhip_plan *p_in = nullptr, *p_out = nullptr;
   const Plan *first = nullptr, *last = nullptr;                      // R'_0 and the last S' over the up list
   i64 n_max = 0;
 };
+
+namespace {
+
+// work (nhops > 0): two ciphertext buffers [2][B][n_max][T_up], the hops ping-pong between them | sub: what the up
+// switch, each hop and the down switch carve in turn
+struct ChainWork { int64_t *buf[2], *sub; };
+ChainWork chain_work(Work& w, const lolhip_tunnel_chain& c, int64_t B) {
+  const i64 buf_words = 2 * B * c.n_max * c.first->T;
+  ChainWork r = {{w.take(buf_words), w.take(buf_words)}, nullptr};
+  const int64_t m = w.mark();
+  r.sub = modswitch_work(w, c.p_in->P, 2, B);
+  for (int i = 0; i < c.nhops; ++i) {
+    w.rewind(m);
+    tunnel_work(w, c.er[(size_t)i]->X, c.es[(size_t)i]->X, c.L[(size_t)i], B);
+  }
+  w.rewind(m);
+  modswitch_work(w, *c.last, 2, B);
+  return r;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -132,7 +152,7 @@ int64_t lolhip_modswitch_work_len(const lolhip_plan* from, const lolhip_plan* to
   if (!from || !to || ncs < 1 || B < 0) return LOLHIP_ERR_INVALID;
   int d, u;
   const int rc = relation(from->P, to->P, &d, &u); if (rc) return rc;
-  return modswitch_words(from->P, ncs, B);
+  return measure(modswitch_work, from->P, ncs, B);
 }
 
 int lolhip_modswitch_batch(const lolhip_plan* from, const lolhip_plan* to, void* stream, const int64_t* cs, int ncs,
@@ -173,6 +193,7 @@ int lolhip_tunnel_chain_create(int nhops, const lolhip_ext* const* x_er, const l
     DecompParams dp;
     const int rc = make_decomp(*ES.hi, base, dp); if (rc) return rc;
     c->er.push_back(x_er[i]); c->es.push_back(x_es[i]); c->ys.push_back(ys_crt[i]); c->hints.push_back(hints[i]);
+    c->L.push_back(dp.L);
     if (ES.hi->n > c->n_max) c->n_max = ES.hi->n;
   }
   c->first = x_er[0]->X.hi;
@@ -190,14 +211,7 @@ void lolhip_tunnel_chain_destroy(lolhip_tunnel_chain* c) { delete c; }
 
 int64_t lolhip_tunnel_chain_work_len(const lolhip_tunnel_chain* c, int64_t B) {
   if (!c || B < 0) return LOLHIP_ERR_INVALID;
-  if (c->nhops == 0) return modswitch_words(c->p_in->P, 2, B);
-  i64 sub = modswitch_words(c->p_in->P, 2, B);
-  for (int i = 0; i < c->nhops; ++i) {
-    const int64_t w = lolhip_tunnel_work_len(c->er[(size_t)i], c->es[(size_t)i], c->base, B);
-    if (w < 0) return w;
-    if (w > sub) sub = w;
-  }
-  return 4 * B * c->n_max * c->first->T + sub;
+  return c->nhops == 0 ? measure(modswitch_work, c->p_in->P, 2, B) : measure(chain_work, *c, B);
 }
 
 int lolhip_tunnel_chain_batch(const lolhip_tunnel_chain* c, void* stream, const int64_t* cs, int cs_crt, int enc,
@@ -220,9 +234,8 @@ int lolhip_tunnel_chain_batch(const lolhip_tunnel_chain* c, void* stream, const 
   if (!c->first->device) return LOLHIP_ERR_NO_DEVICE;
   if (B == 0) { *l_out = (int64_t)down.l2; return LOLHIP_OK; }
   hipStream_t s = (hipStream_t)stream;
-  const i64 buf_words = 2 * B * c->n_max * c->first->T;
-  int64_t* buf[2] = {work, work + buf_words};
-  int64_t* sub = work + 2 * buf_words;
+  Work w(work);
+  const auto [buf, sub] = chain_work(w, *c, B);
   rc = run(up, s, cs, 2, cs_crt ? B_CRT : B_POW, buf[0], B_MIXED, sub, B); if (rc) return rc;
   int cur = 0;
   for (int i = 0; i < c->nhops; ++i) {

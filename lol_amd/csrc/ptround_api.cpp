@@ -42,52 +42,45 @@ struct lolhip_ptround {
 
 namespace {
 
-// the regions of the work buffer, in words
-struct Layout {
-  i64 prod, cts, up, ks, dig, sub, cemb, clift, cpw, zero, total;
-};
-
-Layout layout(const lolhip_ptround& c, int64_t B) {
-  Layout w = Layout();
-  if (c.e < 2 || B == 0) return w;
+// work, every region rounded: a level's products | the ciphertexts it leaves the next level, ping-pong | one product over
+// U_i | its key switch's output | that key switch's digits | what either modSwitch of a level carves | the public constants
+// over Z_i | lifted at index m | mod p (public_lift) | the zero polynomial they are added to
+struct RoundWork { int64_t *prod, *cts[2], *up, *ks, *dig, *sub, *cemb, *clift, *cpw, *zero; };
+RoundWork round_work(Work& w, const lolhip_ptround& c, int64_t B) {
+  RoundWork r = RoundWork();
+  if (c.e < 2 || B == 0) return r;
   const Plan& P0 = c.lvl[0]->P;
   const i64 N = B * P0.n, T0 = P0.T, Tu = T0 + 1, np1 = c.e >= 3 ? c.p / 8 : 0, nc = c.p / 4 + 1;
-  w.prod = even(std::max(3 * N * T0, 3 * np1 * N * (T0 - 1)));
-  w.cts = even(std::max(2 * N * T0, 2 * np1 * N * (T0 - 2)));
-  w.up = even(3 * N * Tu);
-  w.ks = even(2 * N * Tu);
+  r.prod = w.take(even(std::max(3 * N * T0, 3 * np1 * N * (T0 - 1))));
+  for (int64_t*& ct : r.cts) ct = w.take(even(std::max(2 * N * T0, 2 * np1 * N * (T0 - 2))));
+  r.up = w.take(even(3 * N * Tu));
+  r.ks = w.take(even(2 * N * Tu));
   i64 Lmax = 0;
   for (int L : c.L) Lmax = std::max<i64>(Lmax, L);
-  w.dig = even(Lmax * N * Tu);
-  w.sub = even(std::max(3 * N * T0, 2 * N * Tu));
-  w.cemb = even(nc * P0.n * T0);
-  w.clift = even(nc * c.n_m * T0);
-  w.cpw = even(nc * c.n_m);
-  w.zero = even(P0.n * T0);
-  w.total = w.prod + 2 * w.cts + w.up + w.ks + w.dig + w.sub + w.cemb + w.clift + w.cpw + w.zero;
-  return w;
+  r.dig = w.take(even(measure(ks_digits, Lmax, B, P0.n, Tu)));
+  r.sub = w.take(even(measure([&](Work& m) {
+    for (size_t i = 0; i < c.up.size(); ++i) {
+      modswitch_work(m, c.lvl[i]->P, 3, B);
+      m.rewind(0);
+      modswitch_work(m, c.up[i]->P, 2, B);
+      m.rewind(0);
+    }
+  })));
+  r.cemb = w.take(even(nc * P0.n * T0));
+  r.clift = w.take(even(nc * c.n_m * T0));
+  r.cpw = w.take(even(nc * c.n_m));
+  r.zero = w.take(even(P0.n * T0));
+  return r;
 }
 
 // emb [items][n'][T] = embed (reduce (decode' (linv g_m^k v))) in the CRT basis of P, v = src [items][n_m] in R_m mod p:
 // the passes of lolhip_add_public_batch onto a zero polynomial
 int public_consts(const Plan& P, const Plan& lo, const lolhip_ext* x_q, const Plan& PP, hipStream_t s, const int64_t* src,
                   i64 items, int64_t k, u64 linv, u64 p, int64_t* pw, int64_t* lifted, const int64_t* zero, int64_t* emb) {
-  const ModCtx mp = make_modctx(p);
-  const i64 n_m = lo.n;
-  int rc;
-  if (k > 0) {
-    if (launch_pub_lift(s, src, n_m, items, n_m, pw, 1, PP.d_mod, mp, 1) != hipSuccess) return LOLHIP_ERR_HIP;
-    for (int64_t i = 0; i < k; ++i) {
-      rc = run_prog_or_copy(PP, PP.prog_gpow, s, pw, items); if (rc) return rc;
-    }
-    if (launch_pub_lift(s, pw, n_m, items, n_m, lifted, P.T, lo.d_mod, mp, linv) != hipSuccess) return LOLHIP_ERR_HIP;
-  } else if (launch_pub_lift(s, src, n_m, items, n_m, lifted, P.T, lo.d_mod, mp, linv) != hipSuccess) {
-    return LOLHIP_ERR_HIP;
-  }
-  rc = do_crt(lo, s, lifted, items, false); if (rc) return rc;
+  const int rc = public_lift(P, lo, &PP, s, src, lo.n, items, k, linv, p, true, pw, lifted); if (rc) return rc;
   PubScales one;
   set_scale(one, P, nullptr, nullptr);
-  return hip_status(launch_pub_apply(s, PUB_ADD, lifted, n_m * P.T, x_q ? x_q->X.d_embed_crt : nullptr, zero, true, emb, 1,
+  return hip_status(launch_pub_apply(s, PUB_ADD, lifted, lo.n * P.T, x_q ? x_q->X.d_embed_crt : nullptr, zero, true, emb, 1,
                                      items, P.n, one, P.d_mod));
 }
 
@@ -188,7 +181,7 @@ void lolhip_ptround_destroy(lolhip_ptround* c) { delete c; }
 
 int64_t lolhip_ptround_work_len(const lolhip_ptround* c, int64_t B) {
   if (!c || B < 0) return LOLHIP_ERR_INVALID;
-  return layout(*c, B).total;
+  return measure(round_work, *c, B);
 }
 
 int lolhip_ptround_batch(const lolhip_ptround* c, void* stream, const int64_t* cs, int cs_crt, int enc, int64_t k,
@@ -280,17 +273,8 @@ int lolhip_ptround_batch(const lolhip_ptround* c, void* stream, const int64_t* c
   if (B == 0) { *k_out = k_fin; *l_out = l_fin; return LOLHIP_OK; }
 
   // ---- launches ---------------------------------------------------------------------------------------------------------
-  const Layout w = layout(*c, B);
-  int64_t* prod = work;
-  int64_t* cts[2] = {prod + w.prod, prod + w.prod + w.cts};
-  int64_t* up = cts[1] + w.cts;
-  int64_t* ks = up + w.up;
-  int64_t* dig = ks + w.ks;
-  int64_t* sub = dig + w.dig;
-  int64_t* cemb = sub + w.sub;
-  int64_t* clift = cemb + w.cemb;
-  int64_t* cpw = clift + w.clift;
-  int64_t* zero = cpw + w.cpw;
+  Work w(work);
+  const auto [prod, cts, up, ks, dig, sub, cemb, clift, cpw, zero] = round_work(w, *c, B);
   const i64 N = B * P0.n;
   const Plan& PP = c->pp_m->P;
   if (hipMemsetAsync(zero, 0, sizeof(int64_t) * (size_t)(P0.n * P0.T), s) != hipSuccess) return LOLHIP_ERR_HIP;

@@ -25,6 +25,18 @@ struct lolhip_pt_tunnel {
 
 namespace {
 
+// work: a hop's input and its output [B][n_max], rounded, swapped hop by hop | what each hop's evalLin carves
+struct PtTunnelWork { int64_t *a, *b, *ev; };
+PtTunnelWork pt_tunnel_work(Work& w, const lolhip_pt_tunnel& c, int64_t B) {
+  PtTunnelWork r = {w.take(even(B * c.n_max)), w.take(even(B * c.n_max)), nullptr};
+  const int64_t m = w.mark();
+  for (int h = 0; h < c.nhops; ++h) {
+    w.rewind(m);
+    r.ev = evallin_work(w, c.er[(size_t)h]->X, c.es[(size_t)h]->X, B).tmp_e;
+  }
+  return r;
+}
+
 // K rows of n words -> min(K, cap) rows of out
 int64_t copy_rows(const std::vector<i64>& src, int64_t K, int64_t* out, int64_t cap) {
   if (K > 0 && out && cap > 0) {
@@ -219,12 +231,7 @@ int lolhip_pt_tunnel_create(int nhops, const lolhip_ext* const* x_er, const lolh
 
 int64_t lolhip_pt_tunnel_work_len(const lolhip_pt_tunnel* c, int64_t B) {
   if (!c || B < 0) return LOLHIP_ERR_INVALID;
-  int64_t ev = 0;
-  for (int h = 0; h < c->nhops; ++h) {
-    const ExtPlan &ER = c->er[(size_t)h]->X, &ES = c->es[(size_t)h]->X;
-    ev = std::max(ev, (int64_t)(ER.host.phi2 / ER.host.phi) * B * (int64_t)(ER.host.phi + ES.host.phi2));
-  }
-  return 2 * even(B * c->n_max) + ev;
+  return measure(pt_tunnel_work, *c, B);
 }
 
 int lolhip_pt_tunnel_batch(const lolhip_pt_tunnel* c, void* stream, const int64_t* x_dec, int64_t* out_pow, int64_t* work,
@@ -235,9 +242,8 @@ int lolhip_pt_tunnel_batch(const lolhip_pt_tunnel* c, void* stream, const int64_
   if (B > 0 && (!x_dec || !out_pow || !work)) return LOLHIP_ERR_INVALID;
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
-  int64_t* a = work;                                                // the hop's input, decoding basis of R_h mod Q_h
-  int64_t* b = work + even(B * c->n_max);                           // its output
-  int64_t* ev = b + even(B * c->n_max);
+  Work w(work);
+  auto [a, b, ev] = pt_tunnel_work(w, *c, B);                       // a: the hop's input, decoding basis of R_h mod Q_h
   Relift rl = c->rl;
   rl.Qin = 0;
   rl.Qout = c->es[0]->X.hi->qs[0];

@@ -32,7 +32,31 @@ int public_device(const lolhip_plan* pq, const lolhip_ext* x_q) {
   return LOLHIP_OK;
 }
 
+// work: the lifted public values [items][n_m][T] | their residues mod p [items][n_m] (addPublic with k > 0)
+struct PubWork { int64_t *lifted, *pw; };
+PubWork pub_work(Work& w, const Plan& P, const Plan& lo, int64_t items) {
+  return {w.take(items * lo.n * P.T), w.take(items * lo.n)};
+}
+
 }  // namespace
+
+// k = 0: k_pub_lift (b -> the T moduli at index m, linv folded in);  k > 0: k_pub_lift (b mod p) -> mulgpow k times on pp
+// -> k_pub_lift (-> the T moduli, linv folded in);  then crt at index m
+int lolhip::public_lift(const Plan& P, const Plan& lo, const Plan* pp, hipStream_t s, const int64_t* b, int64_t stride,
+                        int64_t items, int64_t k, u64 linv, u64 p, bool crt, int64_t* pw, int64_t* lifted) {
+  const ModCtx mp = make_modctx(p);
+  const i64 n_m = lo.n;
+  if (k > 0) {
+    if (launch_pub_lift(s, b, stride, items, n_m, pw, 1, pp->d_mod, mp, 1) != hipSuccess) return LOLHIP_ERR_HIP;
+    for (int64_t i = 0; i < k; ++i) {
+      const int rc = run_prog_or_copy(*pp, pp->prog_gpow, s, pw, items); if (rc) return rc;
+    }
+    if (launch_pub_lift(s, pw, n_m, items, n_m, lifted, P.T, lo.d_mod, mp, linv) != hipSuccess) return LOLHIP_ERR_HIP;
+  } else if (launch_pub_lift(s, b, stride, items, n_m, lifted, P.T, lo.d_mod, mp, linv) != hipSuccess) {
+    return LOLHIP_ERR_HIP;
+  }
+  return crt ? do_crt(lo, s, lifted, items, false) : LOLHIP_OK;
+}
 
 extern "C" {
 
@@ -69,14 +93,12 @@ int64_t lolhip_public_work_len(const lolhip_plan* pq, const lolhip_ext* x_q, int
   if (!pq || B < 0) return LOLHIP_ERR_INVALID;
   const Plan* lo = lo_plan(pq->P, x_q);
   if (!lo) return LOLHIP_ERR_INVALID;
-  return B * lo->n * (pq->P.T + 1);
+  return measure(pub_work, pq->P, *lo, B);
 }
 
-// addPublic (SymmSHE.hs:381-390): toLSD, then c_0 + embed (reduce (decode' (l^-1 g^k b))).  Launch plan:
-//   k = 0   k_pub_lift (b -> the T moduli at index m, l^-1 folded in)
-//   k > 0   k_pub_lift (b mod p) -> mulgpow k times on pp_m -> k_pub_lift (-> the T moduli, l^-1 folded in)
-//   then    crt at index m (CRT-basis ciphertexts) -> k_pub_apply (the MSD -> LSD factor p mod q_t on every component,
-//           the embed gather: baseIndicesCRT or embedPow)
+// addPublic (SymmSHE.hs:381-390): toLSD, then c_0 + embed (reduce (decode' (l^-1 g^k b))).  Launch plan: public_lift
+// (into the CRT basis for CRT-basis ciphertexts) -> k_pub_apply (the MSD -> LSD factor p mod q_t on every component, the
+// embed gather: baseIndicesCRT or embedPow)
 int lolhip_add_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, const lolhip_plan* pp_m, void* stream,
                             const int64_t* b_pow, int64_t b_stride, const int64_t* cs, int ncs, int cs_shared,
                             int cs_crt, int enc, int64_t k, int64_t l, int64_t p, int64_t* out, int64_t* l_out,
@@ -100,20 +122,10 @@ int lolhip_add_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, const 
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const i64 n_m = lo->n, items = b_stride == 0 ? 1 : B;
-  const ModCtx mp = make_modctx(up);
-  int64_t* lifted = work;                                            // [items][n_m][T]
-  if (k > 0) {
-    const Plan& PP = pp_m->P;
-    int64_t* pw = work + items * n_m * P.T;                          // [items][n_m] residues mod p
-    if (launch_pub_lift(s, b_pow, b_stride, items, n_m, pw, 1, PP.d_mod, mp, 1) != hipSuccess) return LOLHIP_ERR_HIP;
-    for (int64_t i = 0; i < k; ++i) {
-      rc = run_prog_or_copy(PP, PP.prog_gpow, s, pw, items); if (rc) return rc;
-    }
-    if (launch_pub_lift(s, pw, n_m, items, n_m, lifted, P.T, lo->d_mod, mp, linv) != hipSuccess) return LOLHIP_ERR_HIP;
-  } else if (launch_pub_lift(s, b_pow, b_stride, items, n_m, lifted, P.T, lo->d_mod, mp, linv) != hipSuccess) {
-    return LOLHIP_ERR_HIP;
-  }
-  if (cs_crt) { rc = do_crt(*lo, s, lifted, items, false); if (rc) return rc; }
+  Work w(work);
+  const auto [lifted, pw] = pub_work(w, P, *lo, items);
+  rc = public_lift(P, *lo, k > 0 ? &pp_m->P : nullptr, s, b_pow, b_stride, items, k, linv, up, cs_crt != 0, pw, lifted);
+  if (rc) return rc;
   const int32_t* idx = x_q ? (cs_crt ? x_q->X.d_embed_crt : x_q->X.d_embed_pow) : nullptr;
   PubScales sc;
   set_scale(sc, P, enc == 1 ? zq : nullptr, nullptr);
@@ -121,8 +133,8 @@ int lolhip_add_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, const 
                                      ncs, B, P.n, sc, P.d_mod));
 }
 
-// mulPublic (SymmSHE.hs:405-411): every c_i times embed (reduce (decode' a)), CRT basis.  Launch plan: k_pub_lift (a ->
-// the T moduli at index m) -> crt at index m -> k_pub_apply (the baseIndicesCRT gather folded into the product)
+// mulPublic (SymmSHE.hs:405-411): every c_i times embed (reduce (decode' a)), CRT basis.  Launch plan: public_lift (k = 0,
+// no factor) -> k_pub_apply (the baseIndicesCRT gather folded into the product)
 int lolhip_mul_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, void* stream, const int64_t* a_pow,
                             int64_t a_stride, int64_t p, const int64_t* cs, int ncs, int cs_shared, int64_t* out,
                             int64_t* work, int64_t B) {
@@ -135,9 +147,7 @@ int lolhip_mul_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, void* 
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const i64 n_m = lo->n, items = a_stride == 0 ? 1 : B;
-  if (launch_pub_lift(s, a_pow, a_stride, items, n_m, work, P.T, lo->d_mod, make_modctx((u64)p), 1) != hipSuccess)
-    return LOLHIP_ERR_HIP;
-  rc = do_crt(*lo, s, work, items, false); if (rc) return rc;
+  rc = public_lift(P, *lo, nullptr, s, a_pow, a_stride, items, 0, 1, (u64)p, true, nullptr, work); if (rc) return rc;
   PubScales sc;
   set_scale(sc, P, nullptr, nullptr);
   return hip_status(launch_pub_apply(s, PUB_MUL, work, a_stride == 0 ? 0 : n_m * P.T,

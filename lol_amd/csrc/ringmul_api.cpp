@@ -81,6 +81,12 @@ u64 root_up(const Wide& bound, int k) {
 
 int64_t slab(const lolhip_ringmul* h, int64_t B) { return B * h->rm.T * h->pQ->P.n * h->rm.K; }
 
+// work: the lifted a, then the lifted b, [B T][n][K] each and rounded
+struct RingWork { int64_t *la, *lb; };
+RingWork ring_work(Work& w, const lolhip_ringmul* h, int64_t B) {
+  return {w.take(even(slab(h, B))), w.take(even(slab(h, B)))};
+}
+
 // INVALID for a batch whose rows or pointwise period leave 31 bits
 bool batch_fits(const lolhip_ringmul* h, int64_t B) { return B <= 0x7fffffff / h->rm.T; }
 
@@ -176,7 +182,7 @@ int lolhip_ringmul_create(const lolhip_plan* pq, const lolhip_plan* pQ, lolhip_r
 
 int64_t lolhip_ringmul_work_len(const lolhip_ringmul* h, int64_t B) {
   if (!h || B < 0 || !batch_fits(h, B)) return LOLHIP_ERR_INVALID;
-  return 2 * even(slab(h, B));
+  return measure(ring_work, h, B);
 }
 
 int lolhip_ringmul_batch(const lolhip_ringmul* h, void* stream, int64_t* out, const int64_t* a, const int64_t* b,
@@ -188,8 +194,9 @@ int lolhip_ringmul_batch(const lolhip_ringmul* h, void* stream, int64_t* out, co
   if (B == 0) return LOLHIP_OK;
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = h->pQ->P.n;
-  int64_t* la = work;
-  int64_t* lb = a == b ? la : work + even(slab(h, B));
+  Work w(work);
+  const RingWork rw = ring_work(w, h, B);
+  int64_t *la = rw.la, *lb = a == b ? la : rw.lb;
   if (launch_ring_lift(s, a, la, B, n, h->rm) != hipSuccess) return LOLHIP_ERR_HIP;
   if (a != b && launch_ring_lift(s, b, lb, B, n, h->rm) != hipSuccess) return LOLHIP_ERR_HIP;
   rc = lolhip_polymul_batch(h->pQ, stream, la, la, lb, B * h->rm.T); if (rc) return rc;
@@ -221,7 +228,7 @@ int lolhip_ringmul_prepared_batch(const lolhip_ringmul* h, void* stream, int64_t
   hipStream_t s = (hipStream_t)stream;
   const Plan& R = h->pQ->P;
   const int64_t total = slab(h, B), polys = B * h->rm.T;
-  if (launch_ring_lift(s, a, work, B, R.n, h->rm) != hipSuccess) return LOLHIP_ERR_HIP;
+  if (launch_ring_lift(s, a, work, B, R.n, h->rm) != hipSuccess) return LOLHIP_ERR_HIP;       // work: the lifted a alone
   rc = do_crt(R, s, work, polys, false); if (rc) return rc;
   if (launch_pointwise_mul(s, work, bhat, total, Bb == B ? total : period, R.T, R.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
   rc = do_crt(R, s, work, polys, true); if (rc) return rc;

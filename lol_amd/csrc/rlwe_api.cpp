@@ -58,6 +58,13 @@ int rlwr_setup(const lolhip_plan* pq, int64_t p, int64_t B) {
 }
 
 // stabilize (Continuous.hs:81-83, Discrete.hs:73-75): x' = (1/2 + log(2 pi x)/2 - c)/pi from 1/(2 pi) until x' - x < 1e-4
+// work: v, then e.  Disc: v the residues of b - a s [B][n][T] (error; sample keeps the double slab of the Gaussian map
+// [B][n] there) and e the lifted error [B][n];  Cont: v = a s [B][n] and e the Gaussians / the error [B][n];  RLWR: v = a s
+struct RlweWork { int64_t *v, *e; };
+RlweWork rlwe_work(Work& w, const Plan& P, int kind, int64_t B) {
+  return {w.take(B * P.n * (kind == KIND_DISC ? P.T : 1)), kind == KIND_RLWR ? nullptr : w.take(B * P.n)};
+}
+
 bool stabilize(double c, double* out) {
   const double pi = 3.141592653589793;
   double x = 1 / (2 * pi);
@@ -91,12 +98,9 @@ int lolhip_gsqnorm_f64_batch(const lolhip_plan* p, void* stream, const double* e
 }
 
 // ---- samplers (Generate.hs:192-218) -------------------------------------------------------------------------------
-// work, in int64 words.  Disc: the double slab of the Gaussian map [B][n] (sample), the residues of b - a s [B][n][T]
-// and the lifted e [B][n] (error);  Cont: a s [B][n] and the Gaussians / e [B][n];  RLWR: a s [B][n]
 int64_t lolhip_rlwe_work_len(const lolhip_plan* pq, int kind, int64_t B) {
   if (!pq || B < 0 || kind < KIND_DISC || kind > KIND_RLWR) return LOLHIP_ERR_INVALID;
-  const Plan& P = pq->P;
-  return kind == KIND_DISC ? B * P.n * (P.T + 1) : kind == KIND_CONT ? 2 * B * P.n : B * P.n;
+  return measure(rlwe_work, pq->P, kind, B);
 }
 
 int lolhip_rlwe_secret(const lolhip_plan* pq, void* stream, const uint8_t key[32], uint64_t ctr, int64_t* s_crt) {
@@ -133,9 +137,11 @@ int lolhip_rlwe_sample_batch(const lolhip_plan* pq, void* stream, int kind, int6
   hipStream_t s = (hipStream_t)stream;
   const ChaChaKey k = make_key(key);
   const int64_t n = P.n;
+  Work w(work);
+  const auto [x, e] = rlwe_work(w, P, kind, B);
   if (kind == KIND_DISC) {
     int64_t* b = static_cast<int64_t*>(b_out);
-    rc = sample_error(P, s, reinterpret_cast<double*>(work), nullptr, 1, b, ENC_WRITE, k, ctr, CHACHA_DOM_RLWE_GAUSS,
+    rc = sample_error(P, s, reinterpret_cast<double*>(x), nullptr, 1, b, ENC_WRITE, k, ctr, CHACHA_DOM_RLWE_GAUSS,
                       deviation(P, svar), B);
     if (rc) return rc;
     rc = run_prog_or_copy(P, P.prog_l, s, b, B); if (rc) return rc;
@@ -143,14 +149,13 @@ int lolhip_rlwe_sample_batch(const lolhip_plan* pq, void* stream, int kind, int6
     return hip_status(launch_rlwe_uniform(s, RLWE_U_ADD, a_crt, s_crt, b, B, n, P.T, P.d_mod, k, ctr,
                                           CHACHA_DOM_RLWE_UNIFORM));
   }
-  int64_t* x = work;
   if (launch_rlwe_uniform(s, RLWE_U_PROD, a_crt, s_crt, x, B, n, 1, P.d_mod, k, ctr, CHACHA_DOM_RLWE_UNIFORM) != hipSuccess)
     return LOLHIP_ERR_HIP;
   rc = do_crt(P, s, x, B, true); if (rc) return rc;
   rc = run_prog_or_copy(P, P.prog_linv, s, x, B, nullptr); if (rc) return rc;
   if (kind == KIND_RLWR)
     return hip_status(launch_rlwr_round(s, x, static_cast<int64_t*>(b_out), B * n, P.qs[0], (u64)p));
-  double* g = reinterpret_cast<double*>(work + B * n);
+  double* g = reinterpret_cast<double*>(e);
   if (launch_enc_gauss(s, g, B, n, k, ctr, CHACHA_DOM_RLWE_GAUSS, deviation(P, svar)) != hipSuccess) return LOLHIP_ERR_HIP;
   if (!two_power(P) &&
       launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
@@ -175,18 +180,20 @@ int lolhip_rlwe_error_batch(const lolhip_plan* pq, void* stream, int kind, const
 
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = P.n;
+  Work w(work);
+  const auto [v, ew] = rlwe_work(w, P, kind, B);
   if (kind == KIND_DISC) {
-    rc = as_dec(P, s, a_crt, static_cast<const int64_t*>(b), s_crt, work, B); if (rc) return rc;
-    int64_t* e = e_out ? static_cast<int64_t*>(e_out) : work + B * n * P.T;
+    rc = as_dec(P, s, a_crt, static_cast<const int64_t*>(b), s_crt, v, B); if (rc) return rc;
+    int64_t* e = e_out ? static_cast<int64_t*>(e_out) : ew;
     LiftParams lp = LiftParams();
     lp.T = P.T;
-    if (launch_lift(s, work, nullptr, e, B * n, lp, false, P.d_lift, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
+    if (launch_lift(s, v, nullptr, e, B * n, lp, false, P.d_lift, P.d_mod) != hipSuccess) return LOLHIP_ERR_HIP;
     if (!norm_out) return LOLHIP_OK;
     return hip_status(launch_gsqnorm_i64(s, e, static_cast<int64_t*>(norm_out), B, n, norm_dims(P)));
   }
-  rc = as_dec(P, s, a_crt, nullptr, s_crt, work, B); if (rc) return rc;
-  double* e = e_out ? static_cast<double*>(e_out) : reinterpret_cast<double*>(work + B * n);
-  if (launch_rlwe_cont_error(s, work, static_cast<const double*>(b), e, B * n, (double)P.qs[0]) != hipSuccess)
+  rc = as_dec(P, s, a_crt, nullptr, s_crt, v, B); if (rc) return rc;
+  double* e = e_out ? static_cast<double*>(e_out) : reinterpret_cast<double*>(ew);
+  if (launch_rlwe_cont_error(s, v, static_cast<const double*>(b), e, B * n, (double)P.qs[0]) != hipSuccess)
     return LOLHIP_ERR_HIP;
   if (!norm_out) return LOLHIP_OK;
   return hip_status(launch_gsqnorm_f64(s, e, static_cast<double*>(norm_out), B, n, norm_dims(P)));

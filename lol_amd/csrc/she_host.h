@@ -1,7 +1,7 @@
 // lol_amd/csrc/she_host.h — what the host translation units of the C ABI share: the handle types behind
 // include/lolhip.h, the launch helpers capi.cpp owns (defined there) and the one definition of every small piece of
-// SymmSHE host arithmetic and glue the *_api.cpp files need.  Pure host C++; not part of the public
-// interface.  A new feature adds here rather than copying.
+// SymmSHE host arithmetic, glue and shared work-buffer layout the *_api.cpp files need.  Pure host
+// C++; not part of the public interface.  A new feature adds here rather than copying.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -10,6 +10,7 @@
 #include "pipeline.h"
 #include "plan.h"
 #include "public.h"
+#include "work.h"
 
 struct lolhip_plan { lolhip::Plan P; };
 struct lolhip_ext { lolhip::ExtPlan X; };
@@ -28,6 +29,29 @@ int do_crt(const Plan& P, hipStream_t s, int64_t* y, int64_t B, bool inverse);
 int divg_ok(const Plan& P);
 // digit counts (gadlen, ZqBasic.hs:238-240) and the invariant-divisor constants of `base` over the plan's moduli
 int make_decomp(const Plan& P, int64_t base, DecompParams& d);
+
+// ---- defined in public_api.cpp --------------------------------------------------------------------------------------
+// lifted [items][n_m][T] = linv g_m^k b over P's moduli at index m = lo, in the CRT basis when crt: the passes addPublic
+// and ptRound's constants share.  pp: the plan of index m over p, pw [items][n_m]: its scratch (both for k > 0 only)
+int public_lift(const Plan& P, const Plan& lo, const Plan* pp, hipStream_t s, const int64_t* b, int64_t stride, int64_t items,
+                int64_t k, u64 linv, u64 p, bool crt, int64_t* pw, int64_t* lifted);
+
+// ---- the work-buffer layouts more than one entry carves (work.h) -------------------------------------------------------
+// evalLin over B elements: the coefficient vectors [rel][B][n_E][T] | their embeddings into S [rel][B][n_S][T]
+struct EvalLinWork { int64_t *tmp_e, *tmp_s; };
+inline EvalLinWork evallin_work(Work& w, const ExtPlan& ER, const ExtPlan& ES, int64_t B) {
+  const int64_t rel = ER.host.phi2 / ER.host.phi, T = ER.lo->T;
+  return {w.take(rel * B * ER.host.phi * T), w.take(rel * B * ES.host.phi2 * T)};
+}
+// the digit polynomials of one key switch: [L][B][n][T]
+inline int64_t* ks_digits(Work& w, int64_t L, int64_t B, int64_t n, int64_t T) { return w.take(L * B * n * T); }
+// one tunnel hop: evalLin's regions (used twice: c_0, then c_1's coefficient vectors) | its key switches' digits
+struct TunnelWork { EvalLinWork ev; int64_t* dig; };
+inline TunnelWork tunnel_work(Work& w, const ExtPlan& ER, const ExtPlan& ES, int64_t L, int64_t B) {
+  return {evallin_work(w, ER, ES, B), ks_digits(w, L, B, ES.host.phi2, ER.lo->T)};
+}
+// one modSwitch out of plan F: [ncs][B][n][T(F)]
+inline int64_t* modswitch_work(Work& w, const Plan& F, int ncs, int64_t B) { return w.take((int64_t)ncs * B * F.n * F.T); }
 
 // ---- glue --------------------------------------------------------------------------------------------------------
 inline int hip_status(hipError_t e) { return e == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP; }

@@ -3,6 +3,7 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (sanitizers on the
 // CPU build only; GPU ASan is not available on this pool).  Built and run by
 // tests/test_sanitize.py with -fsanitize=address,undefined -fno-sanitize-recover.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "lolhip.h"
+#include "she_host.h"
 
 #define CHECK(c) do { if (!(c)) { std::printf("CHECK failed line %d: %s\n", __LINE__, #c); std::exit(1); } } while (0)
 
@@ -100,6 +102,82 @@ int main() {
     }
   }
   for (lolhip_plan* P : plans) lolhip_plan_destroy(P);
+
+  // ---- the work-buffer arena (work.h): measuring and carving agree, over an array of len() words and a canary ----------
+  for (int64_t B : {0, 1, 3, 8}) {
+    for (int first_wins = 0; first_wins < 2; ++first_wins) {
+      // a | f (doubles) | then either alt1, or alt2 | z (empty) | last
+      struct Regions { int64_t *a; double* f; int64_t *alt1, *alt2, *z, *last; };
+      const int64_t n1 = first_wins ? 11 * B : 5 * B;
+      auto carve = [&](lolhip::Work& w) {
+        Regions r;
+        r.a = w.take(3 * B);
+        r.f = w.take_f64(B);
+        const int64_t m = w.mark();
+        CHECK(m == 4 * B);
+        r.alt1 = w.take(n1);
+        w.rewind(m);
+        r.alt2 = w.take(2 * B);
+        r.z = w.take(0);
+        r.last = w.take(7 * B);
+        return r;
+      };
+      lolhip::Work dry(nullptr);
+      const Regions none = carve(dry);
+      const int64_t len = dry.len();
+      CHECK(len == 4 * B + std::max<int64_t>(n1, 9 * B) && lolhip::measure(carve) == len);
+      CHECK(!none.a && !none.f && !none.alt1 && !none.alt2 && !none.z && !none.last);
+      std::vector<int64_t> buf((size_t)len + 1);                  // one spare word, so base is never null at B = 0
+      int64_t* base = buf.data();
+      buf[(size_t)len] = 0x5A;
+      lolhip::Work w(base);
+      const Regions r = carve(w);
+      CHECK(w.len() == len);
+      CHECK(r.a == base && (int64_t*)r.f == base + 3 * B && r.alt1 == base + 4 * B && r.alt2 == r.alt1);
+      CHECK(r.z == r.alt2 + 2 * B && r.last == r.z);
+      CHECK(first_wins ? r.alt1 + n1 == base + len : r.last + 7 * B == base + len);  // the longer alternative ends at len()
+      for (int64_t i = 0; i < 3 * B; ++i) r.a[i] = i;             // every word of every region: an overrun traps
+      for (int64_t i = 0; i < B; ++i) r.f[i] = 0.5;
+      for (int64_t i = 0; i < n1; ++i) r.alt1[i] = i;
+      for (int64_t i = 0; i < 2 * B; ++i) r.alt2[i] = i;
+      for (int64_t i = 0; i < 7 * B; ++i) r.last[i] = i;
+      CHECK(buf[(size_t)len] == 0x5A);
+    }
+  }
+  {  // the shared layouts of she_host.h over real exts 4 | 12 and 4 | 20: the tunnel's regions fill lolhip_tunnel_work_len
+    int64_t qs[2];
+    qs[0] = lolhip_good_q(60, (int64_t)1 << 29);
+    qs[1] = lolhip_good_q(60, qs[0] + 1);
+    lolhip_plan* pl[3];
+    const long idx[3] = {4, 12, 20};
+    for (int i = 0; i < 3; ++i) {
+      auto pps = factor(idx[i]);
+      CHECK(lolhip_plan_create(pps.data(), (int)pps.size(), qs, 2, 1, &pl[i]) == LOLHIP_OK);
+    }
+    lolhip_ext *XR = nullptr, *XS = nullptr;
+    CHECK(lolhip_ext_create(pl[0], pl[1], &XR) == LOLHIP_OK && lolhip_ext_create(pl[0], pl[2], &XS) == LOLHIP_OK);
+    for (int64_t base : {(int64_t)0, (int64_t)2, (int64_t)256}) {
+      const int64_t L = lolhip_decompose_len(pl[2], base), nS = lolhip_plan_n(pl[2]), nE = lolhip_plan_n(pl[0]);
+      const int64_t rel = lolhip_plan_n(pl[1]) / nE;
+      for (int64_t B : {0, 1, 3, 8}) {
+        const int64_t len = lolhip_tunnel_work_len(XR, XS, base, B);
+        CHECK(len == lolhip::measure(lolhip::tunnel_work, XR->X, XS->X, L, B));
+        CHECK(len == rel * B * (nE + nS) * 2 + L * B * nS * 2 && (B > 0 || len == 0));
+        std::vector<int64_t> buf((size_t)len + 1);
+        lolhip::Work w(buf.data());
+        const lolhip::TunnelWork t = lolhip::tunnel_work(w, XR->X, XS->X, L, B);
+        CHECK(w.len() == len && t.ev.tmp_e == buf.data() && t.ev.tmp_s == t.ev.tmp_e + rel * B * nE * 2);
+        CHECK(t.dig == t.ev.tmp_s + rel * B * nS * 2 && t.dig + L * B * nS * 2 == buf.data() + len);
+        for (int64_t* p = t.ev.tmp_e; p < buf.data() + len; ++p) *p = 1;
+        // evalLin alone carves the same first two regions
+        lolhip::Work w2(buf.data());
+        const lolhip::EvalLinWork ev = lolhip::evallin_work(w2, XR->X, XS->X, B);
+        CHECK(ev.tmp_e == t.ev.tmp_e && ev.tmp_s == t.ev.tmp_s && buf.data() + w2.len() == t.dig);
+      }
+    }
+    lolhip_ext_destroy(XR); lolhip_ext_destroy(XS);
+    for (lolhip_plan* P : pl) lolhip_plan_destroy(P);
+  }
 
   // ---- wire format: round trips, every truncation, random mutations ----------------------------
   const int64_t qs[] = {97, ((int64_t)1 << 40) + 15, 12289};
