@@ -71,21 +71,11 @@ int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const in
   if (rc != LOLHIP_OK) return rc;
   if (!host_only) {
     rc = plan_upload(p->P);
-    if (rc != LOLHIP_OK) { plan_free_device(p->P); return rc; }
+    if (rc != LOLHIP_OK) return rc;
   }
   *out = p.release();
   return LOLHIP_OK;
 }
-
-// stream-ordered workspace: allocated and released on the caller's stream, so concurrent calls on
-// one plan (other host threads, other streams) never share it and nothing synchronises the device
-struct StreamBuf {
-  void* p = nullptr;
-  hipStream_t s;
-  explicit StreamBuf(hipStream_t s_) : s(s_) {}
-  ~StreamBuf() { if (p) (void)hipFreeAsync(p, s); }
-  bool alloc(size_t bytes) { return hipMallocAsync(&p, bytes ? bytes : 8, s) == hipSuccess; }
-};
 
 bool use_mixed(const Plan& P, const StageProgram& sp) {
   return !sw(SW_GENERIC_SCALAR) && mixed_ok(P.n, sp.stages.data(), (int)sp.stages.size(), P.qs.data(), P.T);
@@ -300,11 +290,7 @@ int lolhip_plan_create_roots(const lolhip_pp* pps, int npps, const int64_t* qs, 
                              const int64_t* mhatinv, int host_only, lolhip_plan** out) {
   return make_plan(pps, npps, qs, T, omega_pp, mhatinv, host_only, out);
 }
-void lolhip_plan_destroy(lolhip_plan* p) {
-  if (!p) return;
-  plan_free_device(p->P);
-  delete p;
-}
+void lolhip_plan_destroy(lolhip_plan* p) { delete p; }
 int64_t lolhip_plan_n(const lolhip_plan* p) { return p ? p->P.n : 0; }
 int64_t lolhip_plan_m(const lolhip_plan* p) { return p ? p->P.m : 0; }
 int lolhip_plan_T(const lolhip_plan* p) { return p ? p->P.T : 0; }
@@ -616,28 +602,15 @@ int lolhip_ext_create(const lolhip_plan* lo, const lolhip_plan* hi, lolhip_ext**
     }
   }
   if (lo->P.device && hi->P.device) {
-    auto up32 = [](int32_t** d, const std::vector<int32_t>& h) {
-      if (hipMalloc((void**)d, h.size() * sizeof(int32_t)) != hipSuccess) return false;
-      return hipMemcpy(*d, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-    };
-    bool ok = up32(&X.d_twace_powdec, X.host.twace_powdec) && up32(&X.d_ext_crt, X.host.ext_crt) &&
-              up32(&X.d_embed_pow, X.host.embed_pow) && up32(&X.d_embed_dec, X.host.embed_dec) &&
-              up32(&X.d_embed_crt, X.host.embed_crt) && up32(&X.d_coeffs, X.host.coeffs);
-    if (ok && !X.tweak.empty()) {
-      ok = hipMalloc((void**)&X.d_tweak, X.tweak.size() * sizeof(i64)) == hipSuccess &&
-           hipMemcpy(X.d_tweak, X.tweak.data(), X.tweak.size() * sizeof(i64), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) { lolhip_ext_destroy(x.release()); return LOLHIP_ERR_HIP; }
+    if (X.d_twace_powdec.upload(X.host.twace_powdec) || X.d_ext_crt.upload(X.host.ext_crt) ||
+        X.d_embed_pow.upload(X.host.embed_pow) || X.d_embed_dec.upload(X.host.embed_dec) ||
+        X.d_embed_crt.upload(X.host.embed_crt) || X.d_coeffs.upload(X.host.coeffs) || X.d_tweak.upload(X.tweak))
+      return LOLHIP_ERR_HIP;
   }
   *out = x.release();
   return LOLHIP_OK;
 }
-void lolhip_ext_destroy(lolhip_ext* x) {
-  if (!x) return;
-  void* ptrs[] = {x->X.d_twace_powdec, x->X.d_ext_crt, x->X.d_embed_pow, x->X.d_embed_dec, x->X.d_embed_crt, x->X.d_coeffs, x->X.d_tweak};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  delete x;
-}
+void lolhip_ext_destroy(lolhip_ext* x) { delete x; }
 int64_t lolhip_ext_table(const lolhip_ext* x, int which, int32_t* out, int64_t len) {
   if (!x) return 0;
   const std::vector<int32_t>* src = nullptr;
@@ -668,7 +641,7 @@ static int ext_gather(const lolhip_ext* x, void* stream, int64_t* out, const int
                                   replicating));
 }
 int lolhip_twace_powdec_batch(const lolhip_ext* x, void* s, int64_t* lo_out, const int64_t* hi_in, int64_t B) {
-  return ext_gather(x, s, lo_out, hi_in, B, x ? x->X.d_twace_powdec : nullptr, false);
+  return ext_gather(x, s, lo_out, hi_in, B, x ? x->X.d_twace_powdec.get() : nullptr, false);
 }
 int lolhip_coeffs_batch(const lolhip_ext* x, void* s, int64_t* lo_out, const int64_t* hi_in, int64_t B) {
   if (!x) return LOLHIP_ERR_INVALID;
@@ -751,14 +724,14 @@ int lolhip_tunnel_batch(const lolhip_ext* x_er, const lolhip_ext* x_es, void* st
 }
 
 int lolhip_embed_pow_batch(const lolhip_ext* x, void* s, int64_t* hi_out, const int64_t* lo_in, int64_t B) {
-  return ext_gather(x, s, hi_out, lo_in, B, x ? x->X.d_embed_pow : nullptr, true);
+  return ext_gather(x, s, hi_out, lo_in, B, x ? x->X.d_embed_pow.get() : nullptr, true);
 }
 int lolhip_embed_dec_batch(const lolhip_ext* x, void* s, int64_t* hi_out, const int64_t* lo_in, int64_t B) {
-  return ext_gather(x, s, hi_out, lo_in, B, x ? x->X.d_embed_dec : nullptr, true);
+  return ext_gather(x, s, hi_out, lo_in, B, x ? x->X.d_embed_dec.get() : nullptr, true);
 }
 int lolhip_embed_crt_batch(const lolhip_ext* x, void* s, int64_t* hi_out, const int64_t* lo_in, int64_t B) {
   if (x && !(x->X.lo->has_crt && x->X.hi->has_crt)) return LOLHIP_ERR_NO_CRT;   // Extension.hs:81-85 demands crtInfo m'
-  return ext_gather(x, s, hi_out, lo_in, B, x ? x->X.d_embed_crt : nullptr, true, true);
+  return ext_gather(x, s, hi_out, lo_in, B, x ? x->X.d_embed_crt.get() : nullptr, true, true);
 }
 int lolhip_twace_crt_batch(const lolhip_ext* x, void* s, int64_t* lo_out, const int64_t* hi_in, int64_t B) {
   if (!x) return LOLHIP_ERR_INVALID;
@@ -788,7 +761,7 @@ struct HostStage {
   int dev = -1;
   hipStream_t stream = nullptr;
   char* pinned = nullptr; size_t pinned_bytes = 0;
-  char* d[2] = {nullptr, nullptr}; size_t d_bytes[2] = {0, 0};
+  DevBuf<char> d[2]; size_t d_bytes[2] = {0, 0};
   bool grow_pinned(size_t bytes) {
     if (bytes <= pinned_bytes) return true;
     if (pinned) (void)hipHostFree(pinned);
@@ -802,19 +775,17 @@ struct HostStage {
   bool grow_dev(int i, size_t bytes) {
     if (bytes <= d_bytes[i]) return true;
     if (stream && hipStreamSynchronize(stream) != hipSuccess) return false;
-    if (d[i]) (void)hipFree(d[i]);
-    d[i] = nullptr; d_bytes[i] = 0;
+    d[i].reset(); d_bytes[i] = 0;
     size_t cap = 1 << 16;
     while (cap < bytes) cap <<= 1;
-    if (hipMalloc((void**)&d[i], cap) != hipSuccess) return false;
+    if (d[i].alloc(cap)) return false;
     d_bytes[i] = cap;
     return true;
   }
   void release() {
     if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
     if (pinned) (void)hipHostFree(pinned);
-    for (char* q : d) if (q) (void)hipFree(q);
-    *this = HostStage();
+    *this = HostStage();                          // frees d[]
   }
 };
 struct StagePool {
@@ -881,8 +852,8 @@ int lolhip_op_host(const lolhip_plan* p, int op, int64_t* y, const int64_t* b, i
   if (!h) return LOLHIP_ERR_HIP;
   if (!h->grow_pinned(two ? 2 * bytes : bytes) || !h->grow_dev(0, bytes) || (two && !h->grow_dev(1, bytes))) return LOLHIP_ERR_HIP;
   hipStream_t s = h->stream;
-  int64_t* dy = (int64_t*)h->d[0];
-  int64_t* db = (int64_t*)h->d[1];
+  int64_t* dy = (int64_t*)h->d[0].get();
+  int64_t* db = (int64_t*)h->d[1].get();
   std::memcpy(h->pinned, y, bytes);
   lease.enqueued = true;                       // from here on every return waits for the stream (StageLease)
   if (hipMemcpyAsync(dy, h->pinned, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return LOLHIP_ERR_HIP;
@@ -927,8 +898,8 @@ int lolhip_ext_host(const lolhip_ext* x, int op, int64_t* out, const int64_t* in
   if (!h) return LOLHIP_ERR_HIP;
   if (!h->grow_pinned(bin > bout ? bin : bout) || !h->grow_dev(0, bin) || !h->grow_dev(1, bout)) return LOLHIP_ERR_HIP;
   hipStream_t s = h->stream;
-  int64_t* di = (int64_t*)h->d[0];
-  int64_t* dout = (int64_t*)h->d[1];
+  int64_t* di = (int64_t*)h->d[0].get();
+  int64_t* dout = (int64_t*)h->d[1].get();
   std::memcpy(h->pinned, in, bin);
   lease.enqueued = true;
   if (hipMemcpyAsync(di, h->pinned, bin, hipMemcpyHostToDevice, s) != hipSuccess) return LOLHIP_ERR_HIP;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "she_host.h"
@@ -36,9 +37,9 @@ struct lolhip_khprf {
   DecompParams dp{};
   ModCtx mc{};
   int fold = 1;                  // Q32 digits per 64-bit sum of k_khprf_node
-  int64_t* d_leaf = nullptr;     // [2][L][n]: a0, a1 (CRT basis)
-  int64_t* d_leafdig = nullptr;  // [L][2][L][n]: crt(G^-1(a0)), crt(G^-1(a1)) interleaved as decompose writes them
-  int64_t* d_leafpow = nullptr;  // the lifted family: [2][L][n] a0, a1 in the powerful basis mod q (a one-leaf A_T)
+  DevBuf<int64_t> d_leaf;        // [2][L][n]: a0, a1 (CRT basis)
+  DevBuf<int64_t> d_leafdig;     // [L][2][L][n]: crt(G^-1(a0)), crt(G^-1(a1)) interleaved as decompose writes them
+  DevBuf<int64_t> d_leafpow;     // the lifted family: [2][L][n] a0, a1 in the powerful basis mod q (a one-leaf A_T)
 };
 
 namespace {
@@ -203,23 +204,14 @@ int eval_root(const lolhip_khprf& f, hipStream_t s, int64_t x0, int64_t B, int64
   return hip_status(launch_khprf_lift(s, dst, dst, B * ln, LIFT_FROM_Q, f.lc));
 }
 
-void free_dev(lolhip_khprf* f) {
-  if (f->d_leaf) (void)hipFree(f->d_leaf);
-  if (f->d_leafdig) (void)hipFree(f->d_leafdig);
-  if (f->d_leafpow) (void)hipFree(f->d_leafpow);
-  f->d_leaf = f->d_leafdig = f->d_leafpow = nullptr;
-}
-
 // a0 | a1 -> d_leaf; crtInv, decompose and crt into d_leafdig (on a private stream, synchronised)
 int upload(lolhip_khprf* f, const std::vector<int64_t>& a) {
   const Plan& P = f->pq->P;
   const size_t words = a.size();                           // 2 L n
-  if (hipMalloc(&f->d_leaf, words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (hipMalloc(&f->d_leafdig, (size_t)f->ell * words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
-  int64_t* tmp = nullptr;
-  if (hipMalloc(&tmp, words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
-  hipStream_t s;
-  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) { (void)hipFree(tmp); return LOLHIP_ERR_HIP; }
+  DevBuf<int64_t> tmp;
+  if (f->d_leaf.alloc(words) || f->d_leafdig.alloc((size_t)f->ell * words) || tmp.alloc(words)) return LOLHIP_ERR_HIP;
+  ScopedStream s;                                          // after every buffer it touches: drained before tmp is freed
+  if (!s.ok()) return LOLHIP_ERR_HIP;
   int rc = LOLHIP_OK;
   if (hipMemcpyAsync(f->d_leaf, a.data(), words * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(tmp, f->d_leaf, words * sizeof(int64_t), hipMemcpyDeviceToDevice, s) != hipSuccess)
@@ -228,10 +220,8 @@ int upload(lolhip_khprf* f, const std::vector<int64_t>& a) {
   if (!rc && launch_decompose(s, tmp, f->d_leafdig, 2 * f->ell, P.n, f->dp, P.d_mod, q_below31(P)) != hipSuccess)
     rc = LOLHIP_ERR_HIP;
   if (!rc) rc = do_crt(P, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;
-  (void)hipStreamDestroy(s);
-  (void)hipFree(tmp);
-  return rc;
+  const int rs = s.sync();                                 // a is read until here
+  return rc ? rc : rs;
 }
 
 // the lifted family: a0 | a1 (powerful, [0, q)) -> d_leafpow; crt_Q (lift_q a) -> d_leaf; decompose mod q, lift_q and
@@ -241,11 +231,9 @@ int upload_lifted(lolhip_khprf* f, const std::vector<int64_t>& a) {
   const Plan& PQ = f->pQ->P;
   const size_t words = a.size();                           // 2 L n
   const int64_t dwords = (int64_t)f->ell * (int64_t)words;
-  if (hipMalloc(&f->d_leafpow, words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (hipMalloc(&f->d_leaf, words * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (hipMalloc(&f->d_leafdig, (size_t)dwords * sizeof(int64_t)) != hipSuccess) return LOLHIP_ERR_HIP;
-  hipStream_t s;
-  if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return LOLHIP_ERR_HIP;
+  if (f->d_leafpow.alloc(words) || f->d_leaf.alloc(words) || f->d_leafdig.alloc((size_t)dwords)) return LOLHIP_ERR_HIP;
+  ScopedStream s;
+  if (!s.ok()) return LOLHIP_ERR_HIP;
   int rc = LOLHIP_OK;
   if (hipMemcpyAsync(f->d_leafpow, a.data(), words * sizeof(int64_t), hipMemcpyHostToDevice, s) != hipSuccess ||
       launch_khprf_lift(s, f->d_leafpow, f->d_leaf, (int64_t)words, LIFT_TO_Q, f->lc) != hipSuccess ||
@@ -254,9 +242,8 @@ int upload_lifted(lolhip_khprf* f, const std::vector<int64_t>& a) {
     rc = LOLHIP_ERR_HIP;
   if (!rc) rc = do_crt(PQ, s, f->d_leaf, 2 * f->ell, false);
   if (!rc) rc = do_crt(PQ, s, f->d_leafdig, 2 * (int64_t)f->ell * f->ell, false);
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;
-  (void)hipStreamDestroy(s);
-  return rc;
+  const int rs = s.sync();
+  return rc ? rc : rs;
 }
 
 // the largest |digit| of decompose over lift_q: remainders in [-b/2, b/2), the last digit f^(k-1)(v) for v in
@@ -280,30 +267,30 @@ int lolhip_khprf_create(const lolhip_plan* pq, int64_t base, const int32_t* tree
   if (!pq || !tree || !a0_crt || !a1_crt || !out || ntree < 1 || ntree > 123) return LOLHIP_ERR_INVALID;
   const Plan& P = pq->P;
   if (P.T != 1) return LOLHIP_ERR_INVALID;
-  lolhip_khprf* f = new lolhip_khprf;
+  std::unique_ptr<lolhip_khprf> f(new lolhip_khprf);
   f->pq = pq;
   f->base = base;
   int rc = make_decomp(P, base, f->dp);
   if (!rc && (parse(tree, ntree, 0, 0, f->nodes, 0) != ntree || f->nodes[0].c > 62)) rc = LOLHIP_ERR_INVALID;
   if (!rc && !P.has_crt) rc = LOLHIP_ERR_NO_CRT;
-  if (rc) { delete f; return rc; }
+  if (rc) return rc;
   f->ell = f->dp.L;
   f->k = f->nodes[0].c;
   const u64 q = P.qs[0];
   f->mc = make_modctx(q);
   f->fold = fold_for(q, f->ell);
   rc = need_device(pq);
-  if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f; return LOLHIP_OK; }      // host-only: validation and work lengths
-  if (rc) { delete f; return rc; }
+  if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f.release(); return LOLHIP_OK; }      // host-only: validation and work lengths
+  if (rc) return rc;
   const int64_t ln = (int64_t)f->ell * P.n;
   std::vector<int64_t> a((size_t)(2 * ln));
   for (int64_t i = 0; i < ln; ++i) {
     a[i] = (int64_t)canon(a0_crt[i], q);
     a[ln + i] = (int64_t)canon(a1_crt[i], q);
   }
-  rc = upload(f, a);
-  if (rc) { free_dev(f); delete f; return rc; }
-  *out = f;
+  rc = upload(f.get(), a);
+  if (rc) return rc;
+  *out = f.release();
   return LOLHIP_OK;
 }
 
@@ -313,7 +300,7 @@ int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int
   const Plan& P = pq->P;
   const Plan& PQ = pQ->P;
   if (P.T != 1 || PQ.T != 1 || !same_index(P, PQ)) return LOLHIP_ERR_INVALID;
-  lolhip_khprf* f = new lolhip_khprf;
+  std::unique_ptr<lolhip_khprf> f(new lolhip_khprf);
   f->pq = pq;
   f->pQ = pQ;
   f->base = base;
@@ -322,7 +309,7 @@ int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int
   const u64 q = P.qs[0], Q = PQ.qs[0];
   if (!rc && (q < 2 || (q & (q - 1)) != 0)) rc = LOLHIP_ERR_MODULUS;
   if (!rc && !PQ.has_crt) rc = LOLHIP_ERR_NO_CRT;
-  if (rc) { delete f; return rc; }
+  if (rc) return rc;
   f->ell = f->dp.L;
   f->k = f->nodes[0].c;
   // exactness over Z: |sum_i L_i digit_i| <= L C_m (q/2) max|digit| and |s A| <= C_m (q/2)^2 below Q/2
@@ -330,31 +317,27 @@ int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int
   const u128 C = growth(P.pps), h = q / 2;
   const u128 node = sat(sat(sat((u128)f->ell, C), h), max_digit(q, base, f->dp.k[0]));
   const u128 key = sat(sat(C, h), h);
-  if (2 * std::max(node, key) >= (u128)Q) { delete f; return LOLHIP_ERR_MODULUS; }
+  if (2 * std::max(node, key) >= (u128)Q) return LOLHIP_ERR_MODULUS;
   f->lc.Q = Q;
   f->lc.qbits = __builtin_ctzll(q);
   f->mc = make_modctx(Q);
   f->fold = fold_for(Q, f->ell);
-  rc = need_device(f);
-  if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f; return LOLHIP_OK; }      // host-only: validation and work lengths
-  if (rc) { delete f; return rc; }
+  rc = need_device(f.get());
+  if (rc == LOLHIP_ERR_NO_DEVICE) { *out = f.release(); return LOLHIP_OK; }      // host-only: validation and work lengths
+  if (rc) return rc;
   const int64_t ln = (int64_t)f->ell * P.n;
   std::vector<int64_t> a((size_t)(2 * ln));
   for (int64_t i = 0; i < ln; ++i) {
     a[i] = (int64_t)((u64)a0_pow[i] & (q - 1));
     a[ln + i] = (int64_t)((u64)a1_pow[i] & (q - 1));
   }
-  rc = upload_lifted(f, a);
-  if (rc) { free_dev(f); delete f; return rc; }
-  *out = f;
+  rc = upload_lifted(f.get(), a);
+  if (rc) return rc;
+  *out = f.release();
   return LOLHIP_OK;
 }
 
-void lolhip_khprf_destroy(lolhip_khprf* f) {
-  if (!f) return;
-  free_dev(f);
-  delete f;
-}
+void lolhip_khprf_destroy(lolhip_khprf* f) { delete f; }
 
 int64_t lolhip_khprf_work_len(const lolhip_khprf* f, int64_t x0, int64_t B) {
   if (!range_ok(f, x0, B)) return LOLHIP_ERR_INVALID;

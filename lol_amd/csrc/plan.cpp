@@ -662,22 +662,11 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
 
 // ---- device upload -------------------------------------------------------------
 
-#define HIPCK(x) do { if ((x) != hipSuccess) return LOLHIP_ERR_HIP; } while (0)
-
-template <typename Tp>
-static int upload(Tp** dptr, const std::vector<Tp>& h) {
-  *dptr = nullptr;
-  if (h.empty()) return LOLHIP_OK;
-  HIPCK(hipMalloc((void**)dptr, h.size() * sizeof(Tp)));
-  HIPCK(hipMemcpy(*dptr, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
-  return LOLHIP_OK;
-}
-
 static int upload_prog(StageProgram& sp) {
   sp.nstages = (int)sp.stages.size();
   sp.big = false;
   for (const Stage& s : sp.stages) if (s.kind != ST_POW2F && s.kind != ST_POW2I && (s.d > 13 || s.d == 8 || s.d == 9)) sp.big = true;
-  return upload(&sp.d_stages, sp.stages);
+  return sp.d_stages.upload(sp.stages);
 }
 
 int plan_upload(Plan& P) {
@@ -687,17 +676,17 @@ int plan_upload(Plan& P) {
   std::vector<ModCtx> mods;
   for (int t = 0; t < T; ++t) mods.push_back(make_modctx(P.qs[(size_t)t]));
   int rc;
-  if ((rc = upload(&P.d_mod, mods))) return rc;
-  if ((rc = upload(&P.d_consts, P.host_consts))) return rc;
+  if ((rc = P.d_mod.upload(mods))) return rc;
+  if ((rc = P.d_consts.upload(P.host_consts))) return rc;
   StageProgram* progs[] = {&P.prog_crt, &P.prog_crtinv, &P.prog_l, &P.prog_linv, &P.prog_gpow, &P.prog_gdec, &P.prog_ginvpow, &P.prog_ginvdec,
                            &P.prog_crt_odd, &P.prog_crtinv_odd, &P.prog_gauss, &P.prog_crt_fused, &P.prog_crtinv_fused,
                            &P.prog_crt_mg, &P.prog_crtinv_mg, &P.prog_crt_mg_big, &P.prog_crtinv_mg_big, &P.prog_crt_fused_big, &P.prog_crtinv_fused_big};
   for (auto* sp : progs) if ((rc = upload_prog(*sp))) return rc;
-  if ((rc = upload(&P.d_cconsts, P.host_cconsts))) return rc;
-  if ((rc = upload(&P.d_rconsts, P.host_rconsts))) return rc;
-  if ((rc = upload(&P.d_gcrt, P.gcrt))) return rc;
-  if ((rc = upload(&P.d_ginvcrt, P.ginvcrt))) return rc;
-  if ((rc = upload(&P.d_lift, P.lift_consts))) return rc;
+  if ((rc = P.d_cconsts.upload(P.host_cconsts))) return rc;
+  if ((rc = P.d_rconsts.upload(P.host_rconsts))) return rc;
+  if ((rc = P.d_gcrt.upload(P.gcrt))) return rc;
+  if ((rc = P.d_ginvcrt.upload(P.ginvcrt))) return rc;
+  if ((rc = P.d_lift.upload(P.lift_consts))) return rc;
 
   if (P.is_pow2 || P.pow2_part) {
     const int L = P.pow2.L;
@@ -742,9 +731,9 @@ int plan_upload(Plan& P) {
         }
       }
     }
-    if ((rc = upload(&P.pow2.d_tw_fwd, fwd))) return rc;
-    if ((rc = upload(&P.pow2.d_tw_inv, inv))) return rc;
-    if ((rc = upload(&P.pow2.d_scale, sc))) return rc;
+    if ((rc = P.pow2.d_tw_fwd.upload(fwd))) return rc;
+    if ((rc = P.pow2.d_tw_inv.upload(inv))) return rc;
+    if ((rc = P.pow2.d_scale.upload(sc))) return rc;
     P.pow2.arith32 = 4;
     for (u64 q : P.qs) { if (q >= (1ull << 27)) P.pow2.arith32 = 2; }
     for (u64 q : P.qs) { if (q >= (1ull << 30)) P.pow2.arith32 = 3; }
@@ -763,9 +752,9 @@ int plan_upload(Plan& P) {
           s32[(size_t)t * 8 + 2 * k + 1] = (uint32_t)((sc[(size_t)t * 8 + 2 * k] << 32) / q);
         }
       }
-      if ((rc = upload(&P.pow2.d_tw_fwd32, f32))) return rc;
-      if ((rc = upload(&P.pow2.d_tw_inv32, i32))) return rc;
-      if ((rc = upload(&P.pow2.d_scale32, s32))) return rc;
+      if ((rc = P.pow2.d_tw_fwd32.upload(f32))) return rc;
+      if ((rc = P.pow2.d_tw_inv32.upload(i32))) return rc;
+      if ((rc = P.pow2.d_scale32.upload(s32))) return rc;
     }
   }
   // polynomials too large for the LDS ping-pong run the generic path out of an HBM scratch ring
@@ -782,10 +771,10 @@ int plan_upload(Plan& P) {
         mont[o] = mulmod(P.host_consts[o] % q, r, q);
       }
     }
-    if ((rc = upload(&P.d_consts_mont, mont))) return rc;
+    if ((rc = P.d_consts_mont.upload(mont))) return rc;
     if (P.mixed_cls == 2 || P.mixed_cls == 4) {
       std::vector<uint32_t> c32(mont.begin(), mont.end());           // every entry is a residue below q < 2^32
-      if ((rc = upload(&P.d_consts32, c32))) return rc;
+      if ((rc = P.d_consts32.upload(c32))) return rc;
     }
   }
   if (P.mixed_cls == 1) {
@@ -795,26 +784,11 @@ int plan_upload(Plan& P) {
         const size_t o = (size_t)t * P.consts_per_comp + i;
         c32[o] = (uint32_t)(P.host_consts[o] % P.qs[(size_t)t]);
       }
-    if ((rc = upload(&P.d_consts32, c32))) return rc;
+    if ((rc = P.d_consts32.upload(c32))) return rc;
   }
-  HIPCK(hipGetDevice(&P.device_id));
+  if (hipGetDevice(&P.device_id) != hipSuccess) return LOLHIP_ERR_HIP;
   P.device = true;
   return LOLHIP_OK;
-}
-
-void plan_free_device(Plan& P) {
-  auto fr = [](void* p) { if (p) (void)hipFree(p); };
-  fr(P.d_mod); fr(P.d_lift); P.d_lift = nullptr; fr(P.d_consts); fr(P.d_consts_mont); fr(P.d_consts32); P.d_consts32 = nullptr; fr(P.d_gcrt); fr(P.d_ginvcrt); fr(P.d_cconsts); fr(P.d_rconsts);
-  P.d_cconsts = nullptr; P.d_rconsts = nullptr; P.d_consts_mont = nullptr;
-  fr(P.pow2.d_tw_fwd); fr(P.pow2.d_tw_inv); fr(P.pow2.d_scale);
-  fr(P.pow2.d_tw_fwd32); fr(P.pow2.d_tw_inv32); fr(P.pow2.d_scale32);
-  StageProgram* progs[] = {&P.prog_crt, &P.prog_crtinv, &P.prog_l, &P.prog_linv, &P.prog_gpow, &P.prog_gdec, &P.prog_ginvpow, &P.prog_ginvdec,
-                           &P.prog_crt_odd, &P.prog_crtinv_odd, &P.prog_gauss, &P.prog_crt_fused, &P.prog_crtinv_fused,
-                           &P.prog_crt_mg, &P.prog_crtinv_mg, &P.prog_crt_mg_big, &P.prog_crtinv_mg_big, &P.prog_crt_fused_big, &P.prog_crtinv_fused_big};
-  for (auto* sp : progs) { fr(sp->d_stages); sp->d_stages = nullptr; }
-  P.d_mod = nullptr; P.d_consts = nullptr; P.d_gcrt = nullptr; P.d_ginvcrt = nullptr;
-  P.pow2 = Pow2Tables();
-  P.device = false;
 }
 
 }  // namespace lolhip

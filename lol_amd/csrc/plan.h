@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "devmem.h"
 #include "hostmath.h"
 #include "zq_dev.h"
 
@@ -58,7 +59,7 @@ struct Stage {
 
 struct StageProgram {
   std::vector<Stage> stages;   // host copy
-  Stage* d_stages = nullptr;   // device copy
+  DevBuf<Stage> d_stages;      // device copy
   int nstages = 0;
   bool big = false;            // holds a dense vector of length 18, 20 (merged 3^3 / 5^2) or 8 (3 (x) 5): the BIG kernels of classes 2 / 4 only
 };
@@ -67,12 +68,12 @@ struct StageProgram {
 struct Pow2Tables {
   int L = 0;                       // n = 2^L
   // per component t, n Shoup pairs: entry (N/2 + i) = psi_N^(2i+1), N = 2..n (entry 0 unused)
-  u64* d_tw_fwd = nullptr;         // [T][n][2]
-  u64* d_tw_inv = nullptr;         // [T][n][2]  inverse twiddles; the level-1 entry is pre-scaled
-  u64* d_scale = nullptr;          // [T][8]     Shoup pairs of mhatInv, the level-1 inverse twiddle times mhatInv, and both times 2^64 (plan.cpp),
+  DevBuf<u64> d_tw_fwd;            // [T][n][2]
+  DevBuf<u64> d_tw_inv;            // [T][n][2]  inverse twiddles; the level-1 entry is pre-scaled
+  DevBuf<u64> d_scale;             // [T][8]     Shoup pairs of mhatInv, the level-1 inverse twiddle times mhatInv, and both times 2^64 (plan.cpp),
                                    // then [T][4]: both times 4 2^64 (the fused poly-mul's truncated route)
   // the same three tables as 32-bit Shoup pairs (w, floor(w*2^32/q)) when every q_t < 2^31
-  uint32_t *d_tw_fwd32 = nullptr, *d_tw_inv32 = nullptr, *d_scale32 = nullptr;
+  DevBuf<uint32_t> d_tw_fwd32, d_tw_inv32, d_scale32;
   int arith32 = 0;                 // 4: every q_t < 2^27; 2: < 2^30; 3: < 2^31; 0: no 32-bit tables
 };
 
@@ -100,11 +101,11 @@ struct Plan {
   std::vector<u64> lift_consts;
   bool lift_ok = false;
 
-  // device tables
-  ModCtx* d_mod = nullptr;                  // [T]
-  u64* d_consts = nullptr;                  // generic-path constant pool, [T][consts_per_comp]
-  u64* d_consts_mont = nullptr;             // the same pool times 2^64 mod q_t (every q_t odd): Montgomery class of mixed.hip
-  uint32_t* d_consts32 = nullptr;           // 32-bit copy of the pool the 32-bit classes of the vector interpreter read (class 2: the Montgomery one)
+  // device tables: each owns its allocation (devmem.h), so a Plan cannot be copied and frees them when it is deleted
+  DevBuf<ModCtx> d_mod;                     // [T]
+  DevBuf<u64> d_consts;                     // generic-path constant pool, [T][consts_per_comp]
+  DevBuf<u64> d_consts_mont;                // the same pool times 2^64 mod q_t (every q_t odd): Montgomery class of mixed.hip
+  DevBuf<uint32_t> d_consts32;              // 32-bit copy of the pool the 32-bit classes of the vector interpreter read (class 2: the Montgomery one)
   int consts_per_comp = 0;
   StageProgram prog_crt, prog_crtinv, prog_l, prog_linv, prog_gpow, prog_gdec, prog_ginvpow, prog_ginvdec;
   // m = 2^e * odd, 5 <= e <= 15: the 2-power tensor factor is innermost (tensor.h:46-73), i.e. it
@@ -125,9 +126,9 @@ struct Plan {
   // e >= 4) need the BIG kernels (mixed_impl.h): the *_big programs, empty when they would equal the others; lone
   // transforms and the fused poly-mul take them, the fused key switch at <= 12 coefficients per thread.
   StageProgram prog_crt_mg, prog_crtinv_mg, prog_crt_mg_big, prog_crtinv_mg_big, prog_crt_fused_big, prog_crtinv_fused_big;
-  i64* d_gcrt = nullptr;                    // [n*T]
-  u64* d_lift = nullptr;                    // lift_consts
-  i64* d_ginvcrt = nullptr;                 // [n*T]
+  DevBuf<i64> d_gcrt;                       // [n*T]
+  DevBuf<u64> d_lift;                       // lift_consts
+  DevBuf<i64> d_ginvcrt;                    // [n*T]
   Pow2Tables pow2;
   bool is_pow2 = false;
   int device_id = -1;                       // HIP device the tables were uploaded to
@@ -136,7 +137,7 @@ struct Plan {
   // constant pool, (re, im) interleaved, same offsets as host_consts — and the real maps of
   // tensorGaussianDec
   std::vector<double> host_cconsts, host_rconsts;
-  double *d_cconsts = nullptr, *d_rconsts = nullptr;
+  DevBuf<double> d_cconsts, d_rconsts;
   StageProgram prog_gauss;
   bool float_ok = false;                    // n <= 8192 and every prime <= 13 (one LDS-resident polynomial, register vectors)
   // Nothing in a plan is written after plan_upload(): per-call workspaces (the operand copy of the
@@ -150,17 +151,15 @@ struct ExtPlan {
   const Plan* lo = nullptr;    // index m
   const Plan* hi = nullptr;    // index m'
   ExtTables host;
-  int32_t *d_twace_powdec = nullptr, *d_ext_crt = nullptr, *d_embed_pow = nullptr,
-          *d_embed_dec = nullptr, *d_embed_crt = nullptr, *d_coeffs = nullptr;
+  DevBuf<int32_t> d_twace_powdec, d_ext_crt, d_embed_pow, d_embed_dec, d_embed_crt, d_coeffs;
   std::vector<i64> tweak;      // [n'*T] AoS, twaceCRT's tweak vector (Extension.hs:110-125)
-  i64* d_tweak = nullptr;
+  DevBuf<i64> d_tweak;
 };
 
 // plan.cpp
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
                     const u64* omega_pp /* [npp*T] or null */, const i64* mhatinv /* [T] or null */);
 int plan_upload(Plan& P);
-void plan_free_device(Plan& P);
 
 // A/B switches of the launch paths (development and tests): read ONCE from the environment
 // (LOLHIP_<NAME>) into atomics; tests flip them through lolhip_debug_set, never through setenv

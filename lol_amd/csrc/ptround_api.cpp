@@ -36,8 +36,7 @@ struct lolhip_ptround {
   const lolhip_ext* xq[2] = {nullptr, nullptr};
   const Plan* lo[2] = {nullptr, nullptr};                      // index m over Z_0 / Z_1
   i64 n_m = 0;
-  int64_t* d_src = nullptr;                                    // [1 + p/4][n_m]: 1, then y (1 - y) for odd y, then for even y
-  ~lolhip_ptround() { if (d_src) (void)hipFree(d_src); }
+  DevBuf<int64_t> d_src;                                       // [1 + p/4][n_m]: 1, then y (1 - y) for odd y, then for even y
 };
 
 namespace {
@@ -80,7 +79,7 @@ int public_consts(const Plan& P, const Plan& lo, const lolhip_ext* x_q, const Pl
   const int rc = public_lift(P, lo, &PP, s, src, lo.n, items, k, linv, p, true, pw, lifted); if (rc) return rc;
   PubScales one;
   set_scale(one, P, nullptr, nullptr);
-  return hip_status(launch_pub_apply(s, PUB_ADD, lifted, lo.n * P.T, x_q ? x_q->X.d_embed_crt : nullptr, zero, true, emb, 1,
+  return hip_status(launch_pub_apply(s, PUB_ADD, lifted, lo.n * P.T, x_q ? x_q->X.d_embed_crt.get() : nullptr, zero, true, emb, 1,
                                      items, P.n, one, P.d_mod));
 }
 
@@ -170,8 +169,7 @@ int lolhip_ptround_create(int e, int64_t p, const lolhip_plan* const* p_lvl, con
       const i64 slot = (y & 1) ? 1 + (y - 1) / 2 : 1 + half + (y - 2) / 2;       // odd y first (the a side of the pairs)
       src[(size_t)(slot * c->n_m)] = y * (1 - y);
     }
-    if (hipMalloc((void**)&c->d_src, src.size() * sizeof(int64_t)) != hipSuccess) { c->d_src = nullptr; return LOLHIP_ERR_HIP; }
-    if (hipMemcpy(c->d_src, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) return LOLHIP_ERR_HIP;
+    if (c->d_src.upload(src)) return LOLHIP_ERR_HIP;
   }
   *out = c.release();
   return LOLHIP_OK;

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "crtset.h"
@@ -18,7 +19,7 @@ struct lolhip_pt_tunnel {
   int nhops = 0;
   std::vector<const lolhip_ext*> er, es;
   Relift rl{};                       // p^e; Qin / Qout are set per launch
-  std::vector<int64_t*> d_ys;        // per hop [rel][n_S]: crt mod Q_h of the centred lift of f_h's values
+  std::vector<DevBuf<int64_t>> d_ys; // per hop [rel][n_S]: crt mod Q_h of the centred lift of f_h's values
   bool device = false;
   int64_t n_max = 0;
 };
@@ -65,12 +66,6 @@ int64_t hop_bound(const std::vector<PP>& r, const std::vector<PP>& s, int64_t re
   mul(pe / 2);
   return v >= cap ? (int64_t)LOLHIP_ERR_MODULUS : (int64_t)v;
 }
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess; }
-};
 
 }  // namespace
 
@@ -126,16 +121,17 @@ int64_t lolhip_crtset(const lolhip_plan* pQ, const lolhip_pp* pps_m, int npps_m,
   if (K2 != K) return K2 < 0 ? K2 : (int64_t)LOLHIP_ERR_INVALID;
   const int64_t nb = P.n, n2 = X.phi2, words = K * nb;
   hipStream_t s = (hipStream_t)stream;
-  DevBuf bx, by, bi;
-  if (!bx.alloc(sizeof(int64_t) * (size_t)words) || !by.alloc(sizeof(int64_t) * (size_t)words) ||
-      !bi.alloc(sizeof(int32_t) * (size_t)n2))
+  DevBuf<int64_t> bx, by;
+  DevBuf<int32_t> bi;
+  if (bx.alloc(std::max<size_t>((size_t)words, 1)) || by.alloc(std::max<size_t>((size_t)words, 1)) ||
+      bi.alloc(std::max<size_t>((size_t)n2, 2)))         // at least 8 bytes each
     return LOLHIP_ERR_HIP;
-  int64_t *x = (int64_t*)bx.p, *y = (int64_t*)by.p;
+  int64_t *x = bx, *y = by;
   Relift rl = make_relift(pe);
   rl.Qin = rl.Qout = Q;
   auto hip = [](hipError_t err) { return err == hipSuccess ? LOLHIP_OK : LOLHIP_ERR_HIP; };
   rc = hip(hipMemcpyAsync(x, dec.data(), sizeof(int64_t) * (size_t)words, hipMemcpyHostToDevice, s));
-  if (!rc) rc = hip(hipMemcpyAsync(bi.p, X.embed_pow.data(), sizeof(int32_t) * (size_t)n2, hipMemcpyHostToDevice, s));
+  if (!rc) rc = hip(hipMemcpyAsync(bi, X.embed_pow.data(), sizeof(int32_t) * (size_t)n2, hipMemcpyHostToDevice, s));
   // the decoding-basis residues in [0, p) -> powerful basis (prefix sums below Q/2) -> centred lift of the class mod p^e
   if (!rc) rc = run_prog_or_copy(P, P.prog_l, s, x, K);
   if (!rc) rc = hip(launch_relift(s, x, nullptr, x, words, rl));
@@ -148,7 +144,7 @@ int64_t lolhip_crtset(const lolhip_plan* pQ, const lolhip_pp* pps_m, int npps_m,
     std::swap(x, y);
   }
   if (!rc) rc = hip(launch_relift(s, x, y, nullptr, words, rl));
-  if (!rc) rc = hip(launch_embed_rows(s, y, out_dev, (const int32_t*)bi.p, rows, nb, n2));
+  if (!rc) rc = hip(launch_embed_rows(s, y, out_dev, bi, rows, nb, n2));
   if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;   // also on error: the buffers are freed next
   return rc ? rc : K;
 }
@@ -163,11 +159,7 @@ int64_t lolhip_pt_tunnel_modulus(const lolhip_pp* pps_r, int npps_r, const lolhi
   return hop_bound(r, s, rel, first_hop != 0, pe);
 }
 
-void lolhip_pt_tunnel_destroy(lolhip_pt_tunnel* c) {
-  if (!c) return;
-  for (int64_t* d : c->d_ys) if (d) (void)hipFree(d);
-  delete c;
-}
+void lolhip_pt_tunnel_destroy(lolhip_pt_tunnel* c) { delete c; }
 
 int lolhip_pt_tunnel_create(int nhops, const lolhip_ext* const* x_er, const lolhip_ext* const* x_es,
                             const int64_t* const* funcs_pow, int64_t p, int e, lolhip_pt_tunnel** out) {
@@ -191,19 +183,19 @@ int lolhip_pt_tunnel_create(int nhops, const lolhip_ext* const* x_er, const lolh
     device = device && ER.d_coeffs && ES.d_embed_dec && ES.hi->device && ER.hi->device;
     n_max = std::max(n_max, (int64_t)ES.host.phi2);
   }
-  lolhip_pt_tunnel* c = new lolhip_pt_tunnel;
+  std::unique_ptr<lolhip_pt_tunnel> c(new lolhip_pt_tunnel);
   c->nhops = nhops;
   c->er.assign(x_er, x_er + nhops);
   c->es.assign(x_es, x_es + nhops);
   c->rl = make_relift(pe);
   c->n_max = n_max;
   c->device = device;
-  c->d_ys.assign((size_t)nhops, nullptr);
-  if (!device) { *out = c; return LOLHIP_OK; }                      // host-only: validation and work lengths
-  int rc = need_device(*x_es[0]->X.hi);
-  hipStream_t s = nullptr;
-  if (!rc && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) rc = LOLHIP_ERR_HIP;
+  c->d_ys.resize((size_t)nhops);
+  if (!device) { *out = c.release(); return LOLHIP_OK; }            // host-only: validation and work lengths
+  int rc = need_device(*x_es[0]->X.hi); if (rc) return rc;
   std::vector<std::vector<int64_t>> host((size_t)nhops);           // alive until the stream has drained
+  ScopedStream s;                                                  // after c and host: drained before either goes
+  if (!s.ok()) return LOLHIP_ERR_HIP;
   for (int h = 0; h < nhops && !rc; ++h) {
     const ExtPlan &ER = x_er[h]->X, &ES = x_es[h]->X;
     const Plan& S = *ES.hi;
@@ -215,17 +207,15 @@ int lolhip_pt_tunnel_create(int nhops, const lolhip_ext* const* x_er, const lolh
       const u64 r = canon(funcs_pow[h][i], pe);
       y[(size_t)i] = 2 * r >= pe ? (int64_t)(r + Q - pe) : (int64_t)r;
     }
-    if (hipMalloc((void**)&c->d_ys[(size_t)h], sizeof(int64_t) * (size_t)words) != hipSuccess ||
-        hipMemcpyAsync(c->d_ys[(size_t)h], y.data(), sizeof(int64_t) * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess)
+    DevBuf<int64_t>& d = c->d_ys[(size_t)h];
+    if (d.alloc((size_t)words) ||
+        hipMemcpyAsync(d, y.data(), sizeof(int64_t) * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess)
       rc = LOLHIP_ERR_HIP;
-    if (!rc) rc = do_crt(S, s, c->d_ys[(size_t)h], rel, false);
+    if (!rc) rc = do_crt(S, s, d, rel, false);
   }
-  if (s) {
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = LOLHIP_ERR_HIP;
-    (void)hipStreamDestroy(s);
-  }
-  if (rc) { lolhip_pt_tunnel_destroy(c); return rc; }
-  *out = c;
+  const int rs = s.sync();
+  if (rc || rs) return rc ? rc : rs;
+  *out = c.release();
   return LOLHIP_OK;
 }
 

@@ -126,7 +126,7 @@ int lolhip_add_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, const 
   const auto [lifted, pw] = pub_work(w, P, *lo, items);
   rc = public_lift(P, *lo, k > 0 ? &pp_m->P : nullptr, s, b_pow, b_stride, items, k, linv, up, cs_crt != 0, pw, lifted);
   if (rc) return rc;
-  const int32_t* idx = x_q ? (cs_crt ? x_q->X.d_embed_crt : x_q->X.d_embed_pow) : nullptr;
+  const int32_t* idx = x_q ? (cs_crt ? x_q->X.d_embed_crt : x_q->X.d_embed_pow).get() : nullptr;
   PubScales sc;
   set_scale(sc, P, enc == 1 ? zq : nullptr, nullptr);
   return hip_status(launch_pub_apply(s, PUB_ADD, lifted, b_stride == 0 ? 0 : n_m * P.T, idx, cs, cs_shared != 0, out,
@@ -151,7 +151,7 @@ int lolhip_mul_public_batch(const lolhip_plan* pq, const lolhip_ext* x_q, void* 
   PubScales sc;
   set_scale(sc, P, nullptr, nullptr);
   return hip_status(launch_pub_apply(s, PUB_MUL, work, a_stride == 0 ? 0 : n_m * P.T,
-                                     x_q ? x_q->X.d_embed_crt : nullptr, cs, cs_shared != 0, out, ncs, B, P.n, sc,
+                                     x_q ? x_q->X.d_embed_crt.get() : nullptr, cs, cs_shared != 0, out, ncs, B, P.n, sc,
                                      P.d_mod));
 }
 

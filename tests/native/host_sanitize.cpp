@@ -1,5 +1,6 @@
 // tests/native/host_sanitize.cpp — drives the HOST side of liblolhip (plan construction, number
-// theory, index tables, the protobuf codec, argument checking of the C ABI) under
+// theory, index tables, the protobuf codec, argument checking of the C ABI, the device-memory
+// owners of devmem.h and the host-only life of every handle kind) under
 // AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (sanitizers on the
 // CPU build only; GPU ASan is not available on this pool).  Built and run by
 // tests/test_sanitize.py with -fsanitize=address,undefined -fno-sanitize-recover.
@@ -8,6 +9,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "lolhip.h"
@@ -177,6 +180,152 @@ int main() {
     }
     lolhip_ext_destroy(XR); lolhip_ext_destroy(XS);
     for (lolhip_plan* P : pl) lolhip_plan_destroy(P);
+  }
+
+  // ---- device-memory owners (devmem.h): the empty states, moves and the no-device answers ---------------------------------
+  {
+    using lolhip::DevBuf;
+    static_assert(!std::is_copy_constructible_v<lolhip::Plan> && !std::is_copy_constructible_v<lolhip::ExtPlan>);
+    static_assert(!std::is_copy_constructible_v<DevBuf<int64_t>> && !std::is_copy_assignable_v<DevBuf<int64_t>>);
+    static_assert(sizeof(DevBuf<int64_t>) == sizeof(int64_t*));
+    DevBuf<int64_t> a;
+    CHECK(!a && a.get() == nullptr);
+    DevBuf<int64_t> b(std::move(a));
+    CHECK(!a && !b);
+    a = std::move(b);                                              // onto an empty buffer
+    DevBuf<int64_t>& self = a;
+    a = std::move(self);                                           // onto itself
+    CHECK(!a && !b);
+    a.reset(); a.reset();
+    CHECK(a.upload(std::vector<int64_t>()) == LOLHIP_OK && !a);
+    CHECK(a.alloc(1) == LOLHIP_ERR_HIP && !a);                     // no device here
+    CHECK(a.upload(std::vector<int64_t>(3, 7)) == LOLHIP_ERR_HIP && !a);
+    std::vector<DevBuf<int64_t>> v(3);                             // as lolhip_pt_tunnel keeps them
+    v.resize(40);
+    CHECK(!v[39]);
+  }
+  {  // every handle kind: host-only create and destroy, and a create that fails after the struct is allocated
+    auto plan = [](long m, std::vector<int64_t> qs) {
+      auto pps = factor(m);
+      lolhip_plan* P = nullptr;
+      CHECK(lolhip_plan_create(pps.data(), (int)pps.size(), qs.data(), (int)qs.size(), 1, &P) == LOLHIP_OK && P);
+      return P;
+    };
+    {  // plan: a device plan is refused here after its host tables are built
+      auto pps = factor(12);
+      int64_t q = lolhip_good_q(12, 1000);
+      lolhip_plan* P = (lolhip_plan*)8;
+      CHECK(lolhip_plan_create(pps.data(), (int)pps.size(), &q, 1, 0, &P) == LOLHIP_ERR_NO_DEVICE && !P);
+    }
+    // khprf, both families
+    const int32_t tree[] = {3, 2, 1, 1, 1}, bad_tree[] = {3, 1, 1};
+    {
+      const int64_t q = lolhip_good_q(32, 200);
+      lolhip_plan* P = plan(32, {q});
+      std::vector<int64_t> z((size_t)(lolhip_decompose_len(P, 2) * lolhip_plan_n(P)), 1);
+      lolhip_khprf *f = nullptr, *g = (lolhip_khprf*)8;
+      CHECK(lolhip_khprf_create(P, 2, tree, 5, z.data(), z.data(), &f) == LOLHIP_OK && f);
+      CHECK(lolhip_khprf_work_len(f, 0, 8) > 0);
+      CHECK(lolhip_khprf_eval_batch(f, nullptr, 0, 8, z.data(), z.data()) == LOLHIP_ERR_NO_DEVICE);
+      CHECK(lolhip_khprf_create(P, 2, bad_tree, 3, z.data(), z.data(), &g) == LOLHIP_ERR_INVALID);    // fails in parse
+      CHECK(lolhip_khprf_create(P, 1, tree, 5, z.data(), z.data(), &g) == LOLHIP_ERR_INVALID);        // fails in make_decomp
+      lolhip_khprf_destroy(f);
+      lolhip_khprf_destroy(nullptr);
+      lolhip_plan *Pq = plan(32, {8}), *PQ = plan(32, {lolhip_good_q(32, (int64_t)1 << 30)}), *Psmall = plan(32, {97});
+      CHECK(lolhip_khprf_create_lifted(Pq, PQ, 2, tree, 5, z.data(), z.data(), &f) == LOLHIP_OK && f);
+      CHECK(lolhip_khprf_work_len(f, 1, 5) > 0);
+      CHECK(lolhip_khprf_create_lifted(Pq, Psmall, 2, tree, 5, z.data(), z.data(), &g) == LOLHIP_ERR_MODULUS);   // the bound
+      CHECK(lolhip_khprf_create_lifted(P, PQ, 2, tree, 5, z.data(), z.data(), &g) == LOLHIP_ERR_MODULUS);        // q not 2^k
+      lolhip_khprf_destroy(f);
+      for (lolhip_plan* p : {P, Pq, PQ, Psmall}) lolhip_plan_destroy(p);
+    }
+    // ringmul
+    {
+      auto pps = factor(16);
+      int64_t q = (int64_t)1 << 32, Qs[3];
+      const int K = lolhip_ringmul_moduli(pps.data(), (int)pps.size(), &q, 1, Qs);
+      CHECK(K == 2);
+      lolhip_plan *Pq = plan(16, {q}), *PQ = plan(16, {Qs[0], Qs[1]}), *Pone = plan(16, {Qs[0]}), *P8 = plan(8, {Qs[0], Qs[1]});
+      lolhip_ringmul *h = nullptr, *g = (lolhip_ringmul*)8;
+      CHECK(lolhip_ringmul_create(Pq, PQ, &h) == LOLHIP_OK && h);
+      CHECK(lolhip_ringmul_work_len(h, 3) > 0);
+      CHECK(lolhip_ringmul_create(Pq, Pone, &g) == LOLHIP_ERR_MODULUS);       // one prime: the bound fails
+      CHECK(lolhip_ringmul_create(Pq, P8, &g) == LOLHIP_ERR_INVALID);         // another index
+      lolhip_ringmul_destroy(h);
+      lolhip_ringmul_destroy(nullptr);
+      for (lolhip_plan* p : {Pq, PQ, Pone, P8}) lolhip_plan_destroy(p);
+    }
+    // ptround: e = 3 over four moduli of index 16
+    {
+      int64_t qs[4];
+      qs[0] = lolhip_good_q(16, (int64_t)1 << 29);
+      for (int i = 1; i < 4; ++i) qs[i] = lolhip_good_q(16, qs[i - 1]);
+      lolhip_plan *lvl[3], *up[2];
+      for (int i = 0; i < 3; ++i) lvl[i] = plan(16, std::vector<int64_t>(qs + i + 1, qs + 4));
+      for (int i = 0; i < 2; ++i) up[i] = plan(16, std::vector<int64_t>(qs + i, qs + 4));
+      lolhip_plan* pp = plan(16, {8});
+      const int64_t word = 0;
+      const int64_t* hints[2] = {&word, &word};                   // create keeps the addresses and reads nothing
+      lolhip_ptround *c = nullptr, *g = (lolhip_ptround*)8;
+      CHECK(lolhip_ptround_create(3, 8, lvl, up, hints, 0, pp, nullptr, nullptr, &c) == LOLHIP_OK && c);
+      CHECK(lolhip_ptround_work_len(c, 2) > 0);
+      CHECK(lolhip_ptround_create(3, 16, lvl, up, hints, 0, pp, nullptr, nullptr, &g) == LOLHIP_ERR_INVALID && !g);   // pp is over 8
+      lolhip_plan* up_bad[2] = {up[0], lvl[1]};
+      g = (lolhip_ptround*)8;
+      CHECK(lolhip_ptround_create(3, 8, lvl, up_bad, hints, 0, pp, nullptr, nullptr, &g) == LOLHIP_ERR_INVALID && !g);  // fails at level 1
+      lolhip_ptround_destroy(c);
+      lolhip_ptround_destroy(nullptr);
+      for (lolhip_plan* p : lvl) lolhip_plan_destroy(p);
+      for (lolhip_plan* p : up) lolhip_plan_destroy(p);
+      lolhip_plan_destroy(pp);
+    }
+    // tunnel chain (no hop, and one hop 4 | 12 -> 4 | 20) and pt_tunnel (the same hop over one prime)
+    {
+      int64_t qs[2];
+      qs[0] = lolhip_good_q(60, (int64_t)1 << 29);
+      qs[1] = lolhip_good_q(60, qs[0]);
+      lolhip_plan *E = plan(4, {qs[0], qs[1]}), *R = plan(12, {qs[0], qs[1]}), *S = plan(20, {qs[0], qs[1]}), *S1 = plan(20, {qs[1]});
+      lolhip_ext *XR = nullptr, *XS = nullptr;
+      CHECK(lolhip_ext_create(E, R, &XR) == LOLHIP_OK && lolhip_ext_create(E, S, &XS) == LOLHIP_OK);
+      const int64_t word = 0;
+      const int64_t* dev[1] = {&word};
+      lolhip_tunnel_chain *c = nullptr, *g = (lolhip_tunnel_chain*)8;
+      CHECK(lolhip_tunnel_chain_create(0, nullptr, nullptr, nullptr, nullptr, 0, S, S1, &c) == LOLHIP_OK && c);
+      lolhip_tunnel_chain_destroy(c);
+      CHECK(lolhip_tunnel_chain_create(1, &XR, &XS, dev, dev, 0, R, S1, &c) == LOLHIP_OK && c);
+      CHECK(lolhip_tunnel_chain_work_len(c, 2) > 0);
+      CHECK(lolhip_tunnel_chain_create(1, &XR, &XS, dev, dev, 0, S, S1, &g) == LOLHIP_ERR_INVALID && !g);   // p_in is not of R's index: fails last
+      lolhip_tunnel_chain_destroy(c);
+      lolhip_tunnel_chain_destroy(nullptr);
+      lolhip_ext_destroy(XR); lolhip_ext_destroy(XS);
+      for (lolhip_plan* p : {E, R, S, S1}) lolhip_plan_destroy(p);
+    }
+    {
+      auto pr = factor(12), ps = factor(20);
+      const int64_t bound = lolhip_pt_tunnel_modulus(pr.data(), (int)pr.size(), ps.data(), (int)ps.size(), 2, 1, 2, 3);
+      CHECK(bound > 0);
+      const int64_t Q = lolhip_good_q(60, bound), Qsmall = lolhip_good_q(60, 8);
+      CHECK(Qsmall <= bound);
+      std::vector<int64_t> f((size_t)(2 * 8), 1);                   // [rel = n_R / n_E][n_S]
+      const int64_t* funcs[1] = {f.data()};
+      for (int64_t q : {Q, Qsmall}) {
+        lolhip_plan *E = plan(4, {q}), *R = plan(12, {q}), *S = plan(20, {q});
+        lolhip_ext *XR = nullptr, *XS = nullptr;
+        CHECK(lolhip_ext_create(E, R, &XR) == LOLHIP_OK && lolhip_ext_create(E, S, &XS) == LOLHIP_OK);
+        lolhip_pt_tunnel* t = (lolhip_pt_tunnel*)8;
+        if (q == Q) {
+          CHECK(lolhip_pt_tunnel_create(1, &XR, &XS, funcs, 2, 3, &t) == LOLHIP_OK && t);
+          CHECK(lolhip_pt_tunnel_work_len(t, 2) > 0);
+          CHECK(lolhip_pt_tunnel_batch(t, nullptr, f.data(), f.data(), f.data(), 1) == LOLHIP_ERR_NO_DEVICE);
+          lolhip_pt_tunnel_destroy(t);
+        } else {
+          CHECK(lolhip_pt_tunnel_create(1, &XR, &XS, funcs, 2, 3, &t) == LOLHIP_ERR_MODULUS && !t);   // below the hop's bound
+        }
+        lolhip_ext_destroy(XR); lolhip_ext_destroy(XS);
+        for (lolhip_plan* p : {E, R, S}) lolhip_plan_destroy(p);
+      }
+      lolhip_pt_tunnel_destroy(nullptr);
+    }
   }
 
   // ---- wire format: round trips, every truncation, random mutations ----------------------------
