@@ -771,6 +771,48 @@ LOLHIP_API int lolhip_ringmul_prepare(const lolhip_ringmul *h, void *stream, int
 LOLHIP_API int lolhip_ringmul_prepared_batch(const lolhip_ringmul *h, void *stream, int64_t *out, const int64_t *a,
                                              const int64_t *bhat, int64_t Bb, int64_t *work, int64_t B);
 
+/* --- gadget error correction (gadget_api.cpp, gadget.hip) ----------------------------------------------------------
+ * Correct gad (Cyc t m zq) (Cyc.hs:615-621 over Gadget.hs:84-134 and ZqBasic.hs:234-314), the inverse direction of
+ * lolhip_gadget / lolhip_decompose_batch: from L = lolhip_decompose_len(p, base) noisy multiples xs_j = g_j s + e_j of
+ * the gadget it recovers u (= s when the e_j are small) and the L integer error polynomials, coefficient by coefficient
+ * in the DECODING basis.  base as for lolhip_decompose_batch (0 = TrivGad, b >= 2 = BaseBGad b).  Defined for every
+ * input, an encoding or not.  For one modulus q, k = gadlen(b, q) digits, v_i the centred lift of entry i and
+ * divModCent (a, d) = floor ((a + floor (d/2)) / d):
+ *     w_i = divModCent (b v_i - v_(i+1), q) (i < k-1),  x = sum_i w_i floor (q / b^(i+1)),
+ *     y_0 = x, y_(i+1) = b y_i - q w_i,  v' = v - y,  s = divModCent (v'_(k-1), b^(k-1)),  e_i = v'_i - s b^i,
+ *     u = xs_0 - e_0 mod q;                     k = 1 and TrivGad: u = xs_0, e = [0].
+ * A pair (q_a, q_b) carries the gadget g_a x (1, 0) ++ g_b x (0, 1) (the rows of lolhip_gadget): a row (a, beta) of the
+ * first block has x = lift beta and the entry q_b^-1 (a - x) mod q_a to correct over q_a, its error is x + q_b e'; the
+ * second block the same with the roles swapped; u = (q_b u'_a mod q_a, q_a u'_b mod q_b).
+ * T = 1 or 2 (the class instance is for fields and pairs of fields).
+ * Domain: with h = floor (q/2), W = max (floor ((b+2) h / q), ceil (b h / q)) >= |w_i|,
+ *     Y_i = W (sum_{j<i} b^(i-1-j) (q mod b^(j+1)) + b^i sum_{i<=j<k-1} floor (q / b^(j+1))) >= |y_i|   (Y_0 >= |x|),
+ *     S = floor ((h + Y_(k-1) + ceil (b^(k-1) / 2)) / b^(k-1)) >= |s|,   E = max_i (h + Y_i + S b^i) >= |v'_i|, |e_i|,
+ * every modulus with k >= 2 needs E + b^(k-1) < 2^63 and, in a pair, h_other + q_other E < 2^63 (with k = 1 the errors
+ * of its block are the x alone); anything else is refused with LOLHIP_ERR_MODULUS.  Inside the domain every value is
+ * exact: the kernel's 64-bit sums wrap, and a wrapped sum whose true value fits is that value.
+ * lolhip_gadget_correct_work_len(p, base, basis, B): int64 words of device scratch: 0 for LOLHIP_BASIS_DEC, L B n T for
+ *   LOLHIP_BASIS_POW / LOLHIP_BASIS_CRT (the copy the basis change runs on).  Negative status on error.
+ * lolhip_gadget_correct_batch(p, stream, xs, base, basis, u_dec, es_dec, work, B): xs [L][B][n][T], any int64 taken
+ *   mod q_t, in `basis`; for POW the copy in work goes through lInv, for CRT through crtInv and lInv (one launch plan
+ *   over L B polynomials each), then k_gadget_correct runs once.  u_dec [B][n][T] in [0, q_t), es_dec [L][B][n] int64 or
+ *   NULL (no error is stored, u is the same).  u_dec and es_dec must not overlap xs.
+ * lolhip_gadget_encode_batch(p, stream, s, base, e, out, B): Gadget.encode plus noise, out_j = g_j s + reduce (e_j):
+ *   s [B][n][T] (any int64 mod q_t), e [L][B][n] int64 or NULL (no noise), out [L][B][n][T] in [0, q_t); any T <= 16
+ *   and any basis (s and the e_j in the same one).
+ * Status, all decided on the host before any launch (outputs are then not written): LOLHIP_ERR_INVALID for a NULL plan,
+ *   base 1 or negative, T > 2 (correct) or T > 16 (encode), an unknown basis, B < 0, NULL pointers (es_dec, e and a
+ *   zero-length work excepted) with B > 0; LOLHIP_ERR_MODULUS for moduli of a pair that are not coprime
+ *   and for tuples outside the domain above; LOLHIP_ERR_NO_CRT for LOLHIP_BASIS_CRT on a plan without a CRT basis;
+ *   LOLHIP_ERR_NO_DEVICE on a host-only plan; LOLHIP_ERR_DEVICE as elsewhere.  B = 0 is a no-op returning LOLHIP_OK.
+ *   The calls neither allocate nor synchronise. */
+enum { LOLHIP_BASIS_DEC = 0, LOLHIP_BASIS_POW = 1, LOLHIP_BASIS_CRT = 2 };
+LOLHIP_API int64_t lolhip_gadget_correct_work_len(const lolhip_plan *p, int64_t base, int basis, int64_t B);
+LOLHIP_API int lolhip_gadget_correct_batch(const lolhip_plan *p, void *stream, const int64_t *xs, int64_t base, int basis,
+                                           int64_t *u_dec, int64_t *es_dec, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_gadget_encode_batch(const lolhip_plan *p, void *stream, const int64_t *s, int64_t base,
+                                          const int64_t *e, int64_t *out, int64_t B);
+
 /* --- host-pointer convenience (H2D, run, D2H on an internal stream) --------------
  * op: see LOLHIP_OP_*.  y (and b for MUL/POLYMUL) are host arrays of B polynomials. */
 enum {

@@ -252,13 +252,7 @@ int make_decomp(const Plan& P, int64_t base, DecompParams& d) {
     d.L += d.k[t];
   }
   d.magic = 1; d.sh1 = 0; d.sh2 = 0;
-  if (base >= 2) {
-    int l = 0;
-    while (((u128)1 << l) < (u128)base) ++l;                       // ceil(log2 base)
-    d.magic = (u64)((((u128)1 << 64) * (((u128)1 << l) - (u128)base)) / (u128)base) + 1;
-    d.sh1 = l < 1 ? l : 1;
-    d.sh2 = l > 1 ? l - 1 : 0;
-  }
+  if (base >= 2) inv_div((u64)base, d.magic, d.sh1, d.sh2);
   return LOLHIP_OK;
 }
 

@@ -1,9 +1,10 @@
 // lol_amd/csrc/elementwise_dev.h — the building blocks the element-wise passes share (pipeline.hip, decrypt.hip,
-// encrypt.hip, kshint.hip, khprf.hip, public.hip, modswitch.hip, ptround.hip, pttunnel.hip, ringmul.hip and the
-// element-wise launches of kernels.hip).  Host side of a launch: the tile count (tiles_for), the capped
+// encrypt.hip, kshint.hip, khprf.hip, public.hip, modswitch.hip, ptround.hip, pttunnel.hip, ringmul.hip, gadget.hip and
+// the element-wise launches of kernels.hip).  Host side of a launch: the tile count (tiles_for), the capped
 // block count of a grid-stride launch (grid_stride_blocks) and the 16-byte alignment test of the two-words-per-lane
-// variants (aligned16).  Device side: the 16-byte store type, two scalar reductions (trim, mod_any), the centred lift
-// (centred), the mixed-radix digits of an RNS value (garner_digits) and their sign test (above_half).
+// variants (aligned16).  Device side: the 16-byte store type, two scalar reductions (trim, mod_any), the floor division
+// by an invariant divisor (floor_div_inv), the centred lift (centred), the mixed-radix digits of an RNS value
+// (garner_digits) and their sign test (above_half).
 // Included by .hip files only.  A new pass adds here rather than copying.
 #pragma once
 #include "zq_dev.h"
@@ -39,6 +40,15 @@ __device__ __forceinline__ u64 mod_any(i64 x, const ModCtx& mc) {
   const u64 a = x >= 0 ? (u64)x : 0 - (u64)x;
   const u64 r = rem128(0, a, mc);
   return (x < 0 && r != 0) ? mc.q - r : r;
+}
+
+// floor(x / d) for any signed x through the invariant-divisor multiply: magic = floor(2^64 (2^l - d) / d) + 1,
+// l = ceil(log2 d), sh1 = min(l, 1), sh2 = max(l - 1, 0) (she_host.h inv_div), d >= 1
+__device__ __forceinline__ i64 floor_div_inv(i64 x, u64 magic, int sh1, int sh2) {
+  const u64 n = x >= 0 ? (u64)x : (u64)(-x - 1);
+  const u64 t1 = __umul64hi(magic, n);
+  const u64 q = (t1 + ((n - t1) >> sh1)) >> sh2;
+  return x >= 0 ? (i64)q : -(i64)q - 1;
 }
 
 // the centred lift of a residue r in [0, q): r when 2 r < q, else r - q; at most floor(q / 2) in absolute value

@@ -73,10 +73,7 @@ hipError_t launch_ctmul(hipStream_t s, const i64* c0, const i64* c1, const i64* 
 // ---------------------------------------------------------------------------------------
 // floor(x / base) for any signed x, base >= 2, through the invariant-divisor multiply
 __device__ __forceinline__ i64 floor_div(i64 x, const DecompParams& p) {
-  const u64 n = x >= 0 ? (u64)x : (u64)(-x - 1);
-  const u64 t1 = __umul64hi(p.magic, n);
-  const u64 q = (t1 + ((n - t1) >> p.sh1)) >> p.sh2;
-  return x >= 0 ? (i64)q : -(i64)q - 1;
+  return floor_div_inv(x, p.magic, p.sh1, p.sh2);
 }
 
 // One thread per ROW (coefficient): the T components are lifted and their digits extracted once, every

@@ -71,6 +71,16 @@ inline bool same_index(const Plan& a, const Plan& b) { return a.m == b.m && same
 // x rounded up to an even count of words: work-buffer regions keep the 16-byte alignment of the buffer
 inline int64_t even(int64_t x) { return (x + 1) & ~(int64_t)1; }
 
+// the constants of floor division by the invariant divisor d >= 1 (elementwise_dev.h floor_div_inv):
+// magic = floor(2^64 (2^l - d) / d) + 1, l = ceil(log2 d), sh1 = min(l, 1), sh2 = max(l - 1, 0)
+inline void inv_div(u64 d, u64& magic, int& sh1, int& sh2) {
+  int l = 0;
+  while (((u128)1 << l) < (u128)d) ++l;
+  magic = (u64)((((u128)1 << 64) * (((u128)1 << l) - (u128)d)) / (u128)d) + 1;
+  sh1 = l < 1 ? l : 1;
+  sh2 = l > 1 ? l - 1 : 0;
+}
+
 // floor(2^32 (2^l - base) / base) + 1, l = ceil(log2 base): the 32-bit invariant-divisor constant of the fused key
 // switches (1 for TrivGad, base = 0)
 inline uint32_t magic32(int64_t base) {

@@ -171,6 +171,10 @@ def lib():
     L.lolhip_ringmul_batch.argtypes = [vp, vp, vp, vp, vp, vp, i64]
     L.lolhip_ringmul_prepare.argtypes = [vp, vp, vp, vp, vp, i64]
     L.lolhip_ringmul_prepared_batch.argtypes = [vp, vp, vp, vp, vp, i64, vp, i64]
+    L.lolhip_gadget_correct_work_len.argtypes = [vp, i64, ci, i64]
+    L.lolhip_gadget_correct_work_len.restype = i64
+    L.lolhip_gadget_correct_batch.argtypes = [vp, vp, vp, i64, ci, vp, vp, vp, i64]
+    L.lolhip_gadget_encode_batch.argtypes = [vp, vp, vp, i64, vp, vp, i64]
     L.lolhip_gsqnorm_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_gsqnorm_f64_batch.argtypes = [vp, vp, vp, vp, i64]
     L.lolhip_rlwe_work_len.argtypes = [vp, ci, i64]
@@ -769,6 +773,49 @@ class Plan:
         out = torch.empty((L, B, self.n, self.T), dtype=torch.int64, device=c.device)
         _check(lib().lolhip_decompose_batch(self._h, _stream(stream), _devptr(c), int(base), _devptr(out), B))
         return self._unstage(host, out)
+
+    _BASIS = {"dec": 0, "pow": 1, "crt": 2, 0: 0, 1: 1, 2: 2}
+
+    def gadgetEncode(self, s, base, e=None, stream=None):
+        """Gadget.encode plus noise (Gadget.hs:47-56): out_j = g_j s + reduce (e_j) for s [B][n][T] and integer errors
+        e [L][B][n] (None: no noise) -> [L][B][n][T], L = decomposeLen(base); s and e in one basis, any."""
+        import torch
+        _check(lib().lolhip_gadget_encode_batch(self._h, None, None, int(base), None, None, 0))
+        host, (s, e) = self._stage(s, e)
+        B, L = self._batch_t(s), self.decomposeLen(base)
+        if e is not None and e.numel() != L * B * self.n:
+            raise ValueError(f"errors are not [L={L}][B={B}][n={self.n}]")
+        out = torch.empty((L, B, self.n, self.T), dtype=torch.int64, device=s.device)
+        _check(lib().lolhip_gadget_encode_batch(self._h, _stream(stream), _devptr(s), int(base),
+                                                None if e is None else _devptr(e), _devptr(out), B))
+        return self._unstage(host, out)
+
+    def gadgetCorrectWorkLen(self, base, basis="dec", B=1):
+        wl = lib().lolhip_gadget_correct_work_len(self._h, int(base), self._BASIS[basis], int(B))
+        _check(min(wl, 0))
+        return wl
+
+    def gadgetCorrect(self, xs, base, basis="dec", errors=True, stream=None):
+        """Gadget error correction (Correct gad (Cyc t m zq), Cyc.hs:615-621): xs [L][B][n][T], the noisy multiples
+        g_j s + e_j in `basis` ("dec", "pow" or "crt") -> (u [B][n][T], es [L][B][n] int64), both in the decoding basis;
+        es is None with errors=False.  T = 1 or 2; defined for every input."""
+        import torch
+        L, bs = self.decomposeLen(base), self._BASIS[basis]
+        lb = lib()
+        _check(lb.lolhip_gadget_correct_batch(self._h, None, None, int(base), bs, None, None, None, 0))
+        host, (xs,) = self._stage(xs)
+        if self._batch_t(xs) % L:
+            raise ValueError(f"xs is not [L={L}][B][n={self.n}][T={self.T}]")
+        B = self._batch_t(xs) // L
+        wl = self.gadgetCorrectWorkLen(base, basis, B)
+        work = torch.empty((max(wl, 1),), dtype=torch.int64, device=xs.device)
+        u = torch.empty((B, self.n, self.T), dtype=torch.int64, device=xs.device)
+        es = torch.empty((L, B, self.n), dtype=torch.int64, device=xs.device) if errors else None
+        _check(lb.lolhip_gadget_correct_batch(self._h, _stream(stream), _devptr(xs), int(base), bs, _devptr(u),
+                                              None if es is None else _devptr(es), _devptr(work), B))
+        if es is None:
+            return self._unstage(host, u), None
+        return self._unstage(host, u, es)
 
     def knapsack(self, xs_crt, hint, addend=None, stream=None):
         """sum_j xs_j *>> hint_j (+ addend), CRT basis (SymmSHE.hs:302-304): xs [L][B][n][T],

@@ -6,7 +6,8 @@ ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q 
 (`--modswitch`: that leg alone), of multi-hop tunnelling (`--tunnel-chain`: that leg alone), of homomorphic rounding
 (`--ptround`: that leg alone, also written to profiles/ptround_pipelines.jsonl) and of RLWE instance
 verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl) and of the exact ring
-product over moduli without a CRT basis (`--ringmul`: that leg alone, also written to profiles/ringmul_pipelines.jsonl).
+product over moduli without a CRT basis (`--ringmul`: that leg alone, also written to profiles/ringmul_pipelines.jsonl)
+and of gadget error correction (`--gadget-correct`: that leg alone, also written to profiles/gadget_correct_pipelines.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -731,8 +732,69 @@ def ringmul_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def gadget_correct_leg(gen):
+    """Gadget error correction (lolhip_gadget_correct_batch, decoding basis) at config 5's shape (m = 2048, q = (1017857,
+    1032193), B = 8192) with base 256 and over one 61-bit modulus (q = 2^60 + 147457, m = 2^14, B = 64) with base 2: with
+    and without the error polynomials, beside lolhip_gadget_encode_batch and lolhip_decompose_batch at the same shape and
+    lolhip_copy_slab on a slab of the input's size, all in the same process.  alg_bytes = (L T + T + L) 8 per row (L T + T
+    without errors); frac_of_copy = alg_GBps over the copy's.  Median of five rounds of ten calls.
+    Also written to profiles/gadget_correct_pipelines.jsonl."""
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    lines = []
+    rounds = lambda fn: [timeit(fn) for _ in range(5)]
+
+    def rep(name, cfg, ts, items, alg_bytes, copy_gbps=None, note=None):
+        ms = statistics.median(ts)
+        d = {"op": name, "config": cfg, "ms": round(ms, 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
+             "items_per_s": round(items / ms * 1e3, 1), "alg_bytes": alg_bytes, "alg_GBps": round(alg_bytes / ms / 1e6, 1)}
+        if copy_gbps:
+            d["frac_of_copy"] = round(alg_bytes / ms / 1e6 / copy_gbps, 4)
+        if note:
+            d["note"] = note
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+        return alg_bytes / ms / 1e6
+
+    for pps, qs, B, base in (([(2, 11)], [1017857, 1032193], 8192, 256), ([(2, 14)], [2 ** 60 + 147457], 64, 2)):
+        P = lol_amd.Plan(pps, qs)
+        n, T, Ld = P.n, P.T, P.decomposeLen(base)
+        rows = B * n
+        cfg = f"m={P.m} T={T} q={qs} base={base} L={Ld} B={B}"
+        s = rnd(gen, qs, B, n)
+        cap = min(min(qs) // (2 * (base + 1)), (base ** (Ld // T - 1) - 1) // 2) - 1
+        e = torch.randint(-cap, cap + 1, (Ld, B, n), dtype=torch.int64, device="cuda", generator=gen)
+        xs = torch.empty((Ld, B, n, T), dtype=torch.int64, device="cuda")
+        u, es = torch.empty_like(s), torch.empty_like(e)
+        dst = torch.empty_like(xs)
+        copy = rep("  copy_slab", f"{xs.numel() * 8 >> 20} MiB read + written",
+                   rounds(lambda: L.lolhip_copy_slab(st, ptr(dst), ptr(xs), xs.numel() * 8, 0)), B, 2 * xs.numel() * 8,
+                   note="lolhip_copy_slab, the HBM yardstick")
+        del dst
+        rep("gadget_encode", cfg, rounds(lambda: L.lolhip_gadget_encode_batch(P._h, st, ptr(s), base, ptr(e), ptr(xs), B)),
+            B, (T + Ld + Ld * T) * rows * 8, copy)
+        rep("gadget_correct", cfg, rounds(lambda: L.lolhip_gadget_correct_batch(P._h, st, ptr(xs), base, 0, ptr(u), ptr(es), None, B)),
+            B, (Ld * T + T + Ld) * rows * 8, copy, note="u and the L error polynomials")
+        torch.cuda.synchronize()
+        assert torch.equal(u, s) and torch.equal(es, e), "gadget_correct did not recover (s, e)"
+        rep("gadget_correct(es=NULL)", cfg, rounds(lambda: L.lolhip_gadget_correct_batch(P._h, st, ptr(xs), base, 0, ptr(u), None, None, B)),
+            B, (Ld * T + T) * rows * 8, copy, note="u alone: one sweep")
+        rep("  decompose", cfg, rounds(lambda: L.lolhip_decompose_batch(P._h, st, ptr(s), base, ptr(xs), B)),
+            B, (T + Ld * T) * rows * 8, copy, note="k_decompose at the same shape, the mirror pass")
+        del s, e, xs, u, es
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "gadget_correct_pipelines.jsonl"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--gadget-correct" in sys.argv:   # the gadget error correction leg alone
+        gadget_correct_leg(gen)
+        return
     if "--ringmul" in sys.argv:          # the exact ring product leg alone
         ringmul_leg(gen)
         return
