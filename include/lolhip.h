@@ -834,6 +834,41 @@ LOLHIP_API int lolhip_ext_host(const lolhip_ext *x, int op, int64_t *out, const 
  * e.g. to hand the memory back between phases).  The name dates from round 2, when the sets were per thread. */
 LOLHIP_API void lolhip_thread_release(void);
 
+/* --- L, L^-1, mulG, divG over Z, R and C, and mulC (eltops_api.cpp, eltops.hip) ------------------------
+ * The Tensor members l, lInv, mulGPow, mulGDec, divGPow, divGDec for the element types that are not Z_q (tensorL{R,Double,
+ * C}, tensorLInv*, tensorG{Pow,Dec}{R,C}, tensorGInv{Pow,Dec}{R,C} of l.cpp / g.cpp), in place on a device slab
+ * y [B][n][T] with the T components innermost (the reference's tupSize).  elt: LOLHIP_ELT_I64 int64, LOLHIP_ELT_F64
+ * double, LOLHIP_ELT_C64 complex double stored (re, im): every op is a real-linear map applied componentwise, so a C64
+ * slab is run as an F64 slab of 2 T components.  The index is the plan's; its moduli play no role.  op is one of
+ * LOLHIP_OP_L ... LOLHIP_OP_DIVGDEC.  The structure is tensorFuserPrime's (tensor.h:39-74): the plan's prime powers in
+ * order, the first fastest-varying, p^e as I_lts (x) A_p (x) I_rts with p^(e-1) folded into lts, p = 2 the identity.
+ * Per (p-1)-vector every op runs the recurrence of the reference in its order (l.cpp:28-57, 67-98; g.cpp:16-35, 37-58,
+ * 60-90, 92-123); divG then divides by oddrad = the product of the odd primes of m.
+ *   I64  arithmetic mod 2^64.  divG: ok[b] = 1 and item b holds the exact quotients when every coefficient of the
+ *        transform (as a wrapped int64) is divisible by oddrad; otherwise ok[b] = 0 and item b holds the undivided
+ *        transform (nothing is truncated).  m a power of two: ok[b] = 1, data untouched.  ok is int32 [B], required for
+ *        divG over I64 and ignored (may be NULL) everywhere else.
+ *   F64 / C64  every IEEE operation rounded on its own, in the reference's order (no contraction): L, LInv, mulGPow,
+ *        mulGDec equal the reference bit for bit.  divG is the reference's transform and then y / (double) oddrad; it
+ *        always succeeds.  (The reference's own tensorGInv*R invert the divisibility test and tensorGInv*C scale by the
+ *        integer quotient 1 / oddrad = 0: g.cpp:169-184, 209-237, 262-273.)
+ * One launch reads and writes every word once while n T (2 T for C64) words fit the 160 KiB of LDS; larger items take one
+ * pass over the slab per odd prime straight from HBM (debug switch ELT_GLOBAL forces that route; both give the same
+ * bits).  Primes of any size; a (p-1)-vector is one thread's sequential work, so large primes run slowly.
+ * lolhip_mulc_batch: a[i] *= b[i] over count complex doubles (mulC, types.h:146-152): re = a_re b_re - a_im b_im,
+ * im = a_re b_im + a_im b_re, each product and sum rounded on its own.  b may equal a.
+ * Status, decided on the host before any launch, in this order: LOLHIP_ERR_INVALID for a NULL plan, an unknown op or
+ * elt, T < 1 or T > 16, B < 0 or n > 16384 (mulc: count < 0); LOLHIP_ERR_NO_DEVICE on a host-only plan (mulc: without a
+ * device), LOLHIP_ERR_DEVICE as elsewhere; LOLHIP_ERR_INVALID for NULL y with B > 0 or NULL ok for divG over I64 with
+ * B > 0 (mulc: NULL a or b with count > 0).  B = 0 (count = 0) returns LOLHIP_OK with nothing launched.  No call
+ * synchronises or allocates; the result does not depend on how a batch is split.
+ * With the environment variable LOLHIP_ELT_INFO set (read at every call) each lolhip_elt_op_batch that launches prints
+ * one line to stderr: "k_elt: route <lds|global>, op <op>, word <u64|f64>, n <n>, W <words per coefficient>, lds <bytes> B". */
+enum { LOLHIP_ELT_I64 = 0, LOLHIP_ELT_F64 = 1, LOLHIP_ELT_C64 = 2 };
+LOLHIP_API int lolhip_elt_op_batch(const lolhip_plan *p, void *stream, int op, int elt, int T, void *y, int32_t *ok,
+                                   int64_t B);
+LOLHIP_API int lolhip_mulc_batch(void *stream, double *a, const double *b, int64_t count);
+
 /* --- wire format: Lol's protobuf ring elements, host side -------
  * message Rq { uint32 m = 1; uint64 q = 2; repeated sint64 xs = 3; }   (lol/Lol.proto)
  * message RqProduct { repeated Rq rqlist = 1; }
@@ -902,7 +937,7 @@ LOLHIP_API int64_t lolhip_chain_write(const uint8_t *const *elems, const int64_t
 LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_t bytes, int variant);
 
 /* Test and A/B aid, not part of the drop-in surface: force a launch path.  `name` is one of
- * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built) and NO_TRUNC (each is
+ * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC and ELT_GLOBAL (each is
  * also read ONCE at first use from the environment variable LOLHIP_<name>); value 0 restores the
  * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID.
  * Two environment variables are test hooks of the persistent pipelined poly-mul, read at EVERY launch of it:

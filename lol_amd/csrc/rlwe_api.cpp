@@ -15,21 +15,6 @@ namespace {
 
 enum { KIND_DISC = 0, KIND_CONT = 1, KIND_RLWR = 2 };
 
-// the odd primes' dimensions of the plan's index (rlwe.h NormDims)
-NormDims norm_dims(const Plan& P) {
-  NormDims nd = {};
-  i64 rts = 1;
-  for (const PP& pe : P.pps) {
-    if (pe.p != 2 && nd.k < NORM_MAX_PRIMES) {
-      nd.d[nd.k] = pe.p - 1;
-      nd.rts[nd.k] = (int)rts;
-      ++nd.k;
-    }
-    rts *= totient_pp(pe.p, pe.e);
-  }
-  return nd;
-}
-
 int odd_primes(const Plan& P) {
   int k = 0;
   for (const PP& pe : P.pps) k += pe.p != 2;

@@ -10,6 +10,7 @@
 #include "pipeline.h"
 #include "plan.h"
 #include "public.h"
+#include "rlwe.h"
 #include "work.h"
 
 struct lolhip_plan { lolhip::Plan P; };
@@ -67,6 +68,21 @@ inline int run_prog_or_copy(const Plan& P, const StageProgram& sp, hipStream_t s
 
 // the same index with the same tensor order: m and every (p, e)
 inline bool same_index(const Plan& a, const Plan& b) { return a.m == b.m && same_pps(a.pps, b.pps); }
+
+// the odd primes' dimensions of the plan's index (rlwe.h NormDims)
+inline NormDims norm_dims(const Plan& P) {
+  NormDims nd = {};
+  i64 rts = 1;
+  for (const PP& pe : P.pps) {
+    if (pe.p != 2 && nd.k < NORM_MAX_PRIMES) {
+      nd.d[nd.k] = pe.p - 1;
+      nd.rts[nd.k] = (int)rts;
+      ++nd.k;
+    }
+    rts *= totient_pp(pe.p, pe.e);
+  }
+  return nd;
+}
 
 // x rounded up to an even count of words: work-buffer regions keep the 16-byte alignment of the buffer
 inline int64_t even(int64_t x) { return (x + 1) & ~(int64_t)1; }

@@ -8,6 +8,8 @@ the fused ring product `polymul` (Cyc (*), lol/Crypto/Lol/Cyclotomic/Cyc.hs:262-
 Arrays are int64 with shape [..., n, T] (T = number of RNS moduli; a trailing axis of
 length 1 for a single modulus) — the reference's AoS layout (tensor.h:69).
 `divG*` return None where the reference returns Nothing (CPP.hs:309-323).
+The same six L / G methods over the class's other element types (int64, float64, complex128 slabs) are `eltOp` and its
+wrappers `lR`, `lInvR`, `mulGPowR`, `mulGDecR`, `divGPowR`, `divGDecR`; `mulC` is the complex pointwise product.
 
 Two calling styles per operation:
   * numpy arrays  -> host round trip through `lolhip_op_host`
@@ -35,6 +37,7 @@ _ERRNAMES = {ERR_INVALID: "invalid argument", ERR_MODULUS: "modulus out of range
 
 OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC, OP_MULGCRT, OP_DIVGCRT = range(12)
 EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS = range(6)
+ELT_I64, ELT_F64, ELT_C64 = range(3)
 
 
 class LolHipError(RuntimeError):
@@ -227,6 +230,8 @@ def lib():
         getattr(L, f"lolhip_{nm}").restype = i64
     for nm in ("r_read", "secretkey_read", "kqproduct_read", "linearrq_read", "kshint_write", "tunnelhint_read"):
         getattr(L, f"lolhip_{nm}").restype = i64
+    L.lolhip_elt_op_batch.argtypes = [vp, vp, ci, ci, ci, vp, vp, i64]
+    L.lolhip_mulc_batch.argtypes = [vp, vp, vp, i64]
     L.lolhip_debug_set.argtypes = [C.c_char_p, ci]
     L.lolhip_copy_slab.argtypes = [vp, vp, vp, i64, ci]
     L.lolhip_device_count.restype = ci
@@ -709,6 +714,46 @@ class Plan:
         """iid real Gaussians [..., n] -> decoding-basis sample (tensorGaussianDec, random.cpp:61-64)."""
         return self._float_op("gaussian_dec", y, False)
 
+    # ---- l, lInv, mulG, divG over Z, R and C (DESIGN.md 3.4k) ------------------------------
+    _ELT = {"int64": ELT_I64, "float64": ELT_F64, "complex128": ELT_C64}
+
+    def eltOp(self, op, y, T=None, stream=None):
+        """One of OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC over a slab [..., n, T] of int64 (arithmetic
+        mod 2^64), float64 or complex128 elements (tensorL{R,Double,C}, tensorLInv*, tensorG*{R,C}; lolhip_elt_op_batch).  The
+        plan's moduli play no role.  T: components per coefficient; by default the last axis when the one before it has
+        length n, else 1.  numpy in -> numpy out (staged through HBM); a torch CUDA tensor is transformed in place.  Returns
+        y, or (y, ok) for divG over int64: ok int32 [B], 1 where item b was divisible by g (it then holds the quotient; an
+        item with ok = 0 holds the undivided transform)."""
+        import torch
+        host = isinstance(y, np.ndarray)
+        elt = self._ELT.get(str(y.dtype).replace("torch.", ""))
+        if elt is None:
+            raise TypeError("expected an int64, float64 or complex128 array or CUDA tensor")
+        if T is None:
+            T = int(y.shape[-1]) if len(y.shape) >= 2 and y.shape[-2] == self.n else 1
+        # a dry run at B = 0: every host status is raised before anything is staged
+        _check(lib().lolhip_elt_op_batch(self._h, None, int(op), elt, int(T), None, None, 0), "elt_op")
+        t = torch.from_numpy(np.ascontiguousarray(y)).cuda() if host else y
+        if not (t.is_cuda and t.is_contiguous()):
+            raise TypeError("expected a contiguous CUDA tensor")
+        if t.numel() % (self.n * T):
+            raise ValueError(f"slab is not a whole number of [n={self.n}, T={T}] polynomials")
+        B = t.numel() // (self.n * T)
+        divi = elt == ELT_I64 and op in (OP_DIVGPOW, OP_DIVGDEC)
+        ok = torch.empty((max(B, 1),), dtype=torch.int32, device=t.device)[:B] if divi else None
+        _check(lib().lolhip_elt_op_batch(self._h, _stream(stream), int(op), elt, T, t.data_ptr(),
+                                         ok.data_ptr() if divi else None, B), "elt_op")
+        if divi:
+            return (t.cpu().numpy(), ok.cpu().numpy()) if host else (t, ok)
+        return t.cpu().numpy() if host else t
+
+    def lR(self, y, T=None, stream=None): return self.eltOp(OP_L, y, T, stream)
+    def lInvR(self, y, T=None, stream=None): return self.eltOp(OP_LINV, y, T, stream)
+    def mulGPowR(self, y, T=None, stream=None): return self.eltOp(OP_MULGPOW, y, T, stream)
+    def mulGDecR(self, y, T=None, stream=None): return self.eltOp(OP_MULGDEC, y, T, stream)
+    def divGPowR(self, y, T=None, stream=None): return self.eltOp(OP_DIVGPOW, y, T, stream)
+    def divGDecR(self, y, T=None, stream=None): return self.eltOp(OP_DIVGDEC, y, T, stream)
+
     # ---- ring-level pipelines of SymmSHE (include/lolhip.h, SURVEY.md 8f N1) -----------
     # numpy in -> numpy out (staged through HBM with torch); CUDA tensors in -> CUDA tensors out.
     @staticmethod
@@ -1166,6 +1211,23 @@ class Plan:
             d = torch.from_numpy(d).to(cs.device)
         return self.mulPublic(d.reshape(-1) if isinstance(d, np.ndarray) else d.reshape(-1), cs, pp.qs[0], stride=0,
                               stream=stream), 0
+
+
+def mulC(a, b, stream=None):
+    """a * b elementwise over complex128 (mulC, types.h:146-152: each product and each sum rounded on its own): with
+    crtC / crtInvC the reference's product for moduli without a CRT basis (UCyc CRTExt).  numpy in -> numpy out; a torch
+    CUDA tensor a is overwritten.  b may be a."""
+    import torch
+    host = isinstance(a, np.ndarray)
+    ta = torch.from_numpy(np.ascontiguousarray(a, dtype=np.complex128)).cuda() if host else a
+    tb = ta if b is a else (torch.from_numpy(np.ascontiguousarray(b, dtype=np.complex128)).cuda() if isinstance(b, np.ndarray) else b)
+    for t in (ta, tb):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.complex128):
+            raise TypeError("expected contiguous complex128 arrays or CUDA tensors")
+    if ta.numel() != tb.numel():
+        raise ValueError("operand sizes differ")
+    _check(lib().lolhip_mulc_batch(_stream(stream), ta.data_ptr(), tb.data_ptr(), ta.numel()), "mulc")
+    return ta.cpu().numpy() if host else ta
 
 
 def chacha20_block(key, counter, nonce):

@@ -7,7 +7,8 @@ ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q 
 (`--ptround`: that leg alone, also written to profiles/ptround_pipelines.jsonl) and of RLWE instance
 verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl) and of the exact ring
 product over moduli without a CRT basis (`--ringmul`: that leg alone, also written to profiles/ringmul_pipelines.jsonl)
-and of gadget error correction (`--gadget-correct`: that leg alone, also written to profiles/gadget_correct_pipelines.jsonl).
+and of gadget error correction (`--gadget-correct`: that leg alone, also written to profiles/gadget_correct_pipelines.jsonl)
+and of L / divG over int64 and double slabs (`--eltops`: that leg alone, also written to profiles/eltops_bench.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -790,8 +791,79 @@ def gadget_correct_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def eltops_leg(gen):
+    """L and divGPow over int64 and float64 slabs (lolhip_elt_op_batch, T = 1) at the tunnelling index m = 128 * 7 * 13
+    (n = 4608) and at m = 3 * 2^13 (n = 8192), batches of at least 1 GiB, on the route the library picks (LDS-resident
+    items) and, for L over int64, on the forced global route (one pass per odd prime); beside lolhip_copy_slab on a slab
+    of the same size (`hbm_copy`) and lolhip_l_batch (Z_q, one 31-bit modulus) at the same index and batch, all in the
+    same process.  alg_bytes = 2 x slab; frac_of_copy = alg_GBps over the copy's.  The ops work in place, so the operand
+    changes from call to call (the int64 slab of divGPow is indivisible after the first: the flags say 0 and the
+    numerators are stored, the same traffic).  Median of five rounds of ten calls.
+    Also written to profiles/eltops_bench.jsonl."""
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    lines = []
+    rounds = lambda fn: [timeit(fn) for _ in range(5)]
+
+    def rep(name, cfg, ts, items, alg_bytes, copy_gbps=None, note=None):
+        ms = statistics.median(ts)
+        d = {"op": name, "config": cfg, "ms": round(ms, 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
+             "items_per_s": round(items / ms * 1e3, 1), "alg_bytes": alg_bytes, "alg_GBps": round(alg_bytes / ms / 1e6, 1)}
+        if copy_gbps:
+            d["frac_of_copy"] = round(alg_bytes / ms / 1e6 / copy_gbps, 4)
+        if note:
+            d["note"] = note
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+        return alg_bytes / ms / 1e6
+
+    OP_L, OP_DIVGPOW, I64, F64 = 4, 8, 0, 1
+    q31 = 2 ** 31 - 1
+    for m in (128 * 7 * 13, 3 * 2 ** 13):
+        P = lol_amd.Plan(lol_amd.factor_pps(m), [q31])
+        n = P.n
+        B = -(-2 ** 30 // (n * 8))
+        slab = B * n * 8
+        cfg = f"m={m} n={n} T=1 B={B} ({slab >> 20} MiB)"
+        yi = torch.randint(-2 ** 62, 2 ** 62, (B, n, 1), dtype=torch.int64, device="cuda", generator=gen)
+        yf = torch.randn((B, n, 1), dtype=torch.float64, device="cuda", generator=gen)
+        ok = torch.empty((B,), dtype=torch.int32, device="cuda")
+        dst = torch.empty_like(yi)
+        copy = rep("  hbm_copy", cfg, rounds(lambda: L.lolhip_copy_slab(st, dst.data_ptr(), yi.data_ptr(), slab, 0)), B, 2 * slab,
+                   note="lolhip_copy_slab, the HBM yardstick")
+        del dst
+        for name, op in (("L", OP_L), ("divGPow", OP_DIVGPOW)):
+            for ename, elt, y in (("i64", I64, yi), ("f64", F64, yf)):
+                call = lambda: L.lolhip_elt_op_batch(P._h, st, op, elt, 1, y.data_ptr(), ok.data_ptr(), B)
+                assert call() == 0
+                rep(f"elt_{name}_{ename}", cfg, rounds(call), B, 2 * slab, copy, note="on-chip route, one launch")
+        lol_amd.debug_set("ELT_GLOBAL", True)
+        try:
+            for name, op in (("L", OP_L), ("divGPow", OP_DIVGPOW)):
+                call = lambda: L.lolhip_elt_op_batch(P._h, st, op, I64, 1, yi.data_ptr(), ok.data_ptr(), B)
+                assert call() == 0
+                rep(f"elt_{name}_i64(global)", cfg, rounds(call), B, 2 * slab, copy, note="forced global route: one pass per odd prime"
+                    + (", then the flag and division passes" if op == OP_DIVGPOW else ""))
+        finally:
+            lol_amd.debug_set("ELT_GLOBAL", False)
+        yq = torch.randint(0, q31, (B, n, 1), dtype=torch.int64, device="cuda", generator=gen)
+        call = lambda: L.lolhip_l_batch(P._h, st, yq.data_ptr(), B)
+        assert call() == 0
+        rep("  l_batch(Zq)", cfg + f" q={q31}", rounds(call), B, 2 * slab, copy, note="lolhip_l_batch over Z_q, one 31-bit modulus")
+        torch.cuda.synchronize()
+        del yi, yf, yq, ok
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "eltops_bench.jsonl"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--eltops" in sys.argv:           # the L / divG over Z and R leg alone
+        eltops_leg(gen)
+        return
     if "--gadget-correct" in sys.argv:   # the gadget error correction leg alone
         gadget_correct_leg(gen)
         return
