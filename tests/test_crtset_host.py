@@ -235,6 +235,9 @@ def test_pt_tunnel_create_statuses(lolhip):
     nmax = 72
     assert t.workLen(3) == 2 * 3 * nmax + max(2 * 3 * (2 + 12), 2 * 3 * (6 + 72))
     assert L.lolhip_pt_tunnel_batch(t._h, None, None, None, None, 0) == ERR_NO_DEVICE
+    with pytest.raises(lolhip.LolHipError) as ei:                              # the method raises it before it stages anything
+        t(np.zeros((3, 4), dtype=np.int64))
+    assert ei.value.code == ERR_NO_DEVICE
     assert L.lolhip_pt_tunnel_work_len(t._h, -1) == ERR_INVALID
     # the bound of a hop: 2 rel C_S G_S D_R (p^e/2)^2
     b0 = lolhip.PTTunnel.modulus(8, 28, 2, True, p, e)

@@ -92,6 +92,11 @@ def test_modswitch_statuses_on_host_only_plans(lolhip):
     assert call(f=nf, t=nt, p=5) == NO_DEVICE and call(f=nf, t=nt, p=5, crt=1) == NO_CRT and call(f=nf, t=nt, p=5, ocrt=1) == NO_CRT
     assert (out == SENT).all() and lo.value == SENT
     assert call(Bn=0, c=None, o=None, w=None) == NO_DEVICE
+    # the Python method raises the same codes before it stages anything
+    for to, p, code in ((last2, 257, NO_DEVICE), (other, 257, INVALID), (last2, qs[1], MODULUS)):
+        with pytest.raises(lolhip.LolHipError) as e:
+            full.modSwitch(to, cs, p)
+        assert e.value.code == code
 
 
 def test_modswitch_work_len(lolhip):
@@ -160,6 +165,12 @@ def test_tunnel_chain_statuses_and_work_len(lolhip):
     assert batch(p=1) == MODULUS and batch(p=up[1]) == MODULUS
     assert (out == SENT).all() and lo.value == SENT
     L.lolhip_tunnel_chain_destroy(h)
+    # the Python class raises the same codes before it stages anything
+    ch = lolhip.TunnelChain([x[0] for x in hops], [x[1] for x in hops], fake, fake, 2, p_in, p_out)
+    for p, code in ((8, NO_DEVICE), (1, MODULUS)):
+        with pytest.raises(lolhip.LolHipError) as e:
+            ch(cs, p)
+        assert e.value.code == code
     # create: hops that do not meet, plans not of the end rings or not over a suffix of the up list
     assert create(er=er[::-1], es=es[::-1])[0] == INVALID
     assert create(pi=mk(12, up[1:]))[0] == INVALID and create(po=mk(12, up[2:]))[0] == INVALID

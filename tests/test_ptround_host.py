@@ -125,6 +125,11 @@ def test_ct_affine_mul_statuses(lolhip):
     assert call(h=mk([2 ** 20, 2 ** 21 + 1])) == NO_CRT
     assert call(Bn=0, a_=None, b_=None, o=None) == NO_DEVICE
     assert (out == SENT).all()
+    # the Python method raises the same codes before it stages anything
+    for plan, kw, code in ((pq, {}, NO_DEVICE), (pq, dict(npairs=0), INVALID), (mk([2 ** 20, 2 ** 21 + 1]), {}, NO_CRT)):
+        with pytest.raises(lolhip.LolHipError) as e:
+            plan.ctAffineMul(a, 1, **kw)
+        assert e.value.code == code
 
 
 def test_ptround_statuses_and_work_len(lolhip):
@@ -177,6 +182,12 @@ def test_ptround_statuses_and_work_len(lolhip):
     assert batch(Bn=0, c=None, o=None, w=None) == NO_DEVICE
     assert (out == SENT).all() and ko.value == SENT and lo.value == SENT
     L.lolhip_ptround_destroy(h)
+    # the Python class raises the same codes before it stages anything
+    rnd = lolhip.PTRound(lv, up, fake, 2, p, pp_m=pp)
+    for l, code in ((1, NO_DEVICE), (2, MODULUS)):
+        with pytest.raises(lolhip.LolHipError) as e:
+            rnd(cs, l=l)
+        assert e.value.code == code
     # create
     assert create(e=0)[0] == INVALID and create(e=17)[0] == INVALID and create(ok_out=False)[0] == INVALID
     assert create(lv=[lv[0], None, lv[2]])[0] == INVALID and create(up=[up[0], None])[0] == INVALID
