@@ -20,8 +20,10 @@ Method by method this follows the reference instance (CPP.hs:204-264):
                                                                    with liblolhip's own root of unity (include/lolhip.h)
   scalarPow, tGaussianDec, gSqNormDec, fmapT, unzipT, entail*  ->  CT
 
-The batched SymmSHE entries of include/lolhip.h sit beside the class (INTEGRATION.md): (*) -> lolhip_ctmul_crt_batch,
-keySwitchQuadCirc -> lolhip_keyswitch_batch, modSwitch -> lolhip_modswitch_batch, addPublic / mulPublic ->
+The batched SymmSHE entries of include/lolhip.h sit beside the class (INTEGRATION.md): (*) -> lolhip_ct_mul_batch with
+the (enc, k, l) of lolhip_ct_mul_rule (any degree, either basis; HIP/Backend.hs c_ctMul; two linear CRT-basis operands
+also lolhip_ctmul_crt_batch), keySwitchLinear / keySwitchQuadCirc -> toMSD (lolhip_ct_lincomb_batch) and
+lolhip_keyswitch_batch, embedCT / twaceCT -> the embed / twace entries on every component, modSwitch -> lolhip_modswitch_batch, addPublic / mulPublic ->
 lolhip_add_public_batch / lolhip_mul_public_batch, tunnelH -> lolhip_tunnel_chain_batch, ptRound (HomomPRF.hs:215-270)
 -> lolhip_ptround_batch over lolhip_ct_affine_mul_batch; homomPRF is mulPublic, tunnelH and ptRound in a row.  UCyc.crtSet
 -> lolhip_crtset, ptTunnel (HomomPRF.hs:510-531) -> lolhip_pt_tunnel_batch.

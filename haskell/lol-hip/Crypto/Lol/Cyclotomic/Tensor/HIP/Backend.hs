@@ -19,6 +19,7 @@ module Crypto.Lol.Cyclotomic.Tensor.HIP.Backend
 , planFor, extFor, planHasCRT
 , opHost, opHostMaybe, op2Host, extHost
 , powBasisPowIdx, crtSetDecHost
+, c_ctMulRule, c_ctMulWorkLen, c_ctMul
 , ok, errNotDivisible
 ) where
 
@@ -78,6 +79,19 @@ foreign import ccall unsafe "lolhip_ext_table"
   c_extTable :: Ptr ExtH -> CInt -> Ptr Int32 -> Int64 -> IO Int64
 foreign import ccall unsafe "lolhip_crtset_dec"
   c_crtSetDec :: Ptr CPP -> CInt -> Ptr CPP -> CInt -> Int64 -> Ptr Int64 -> Int64 -> IO Int64
+
+-- (*) on CT of any degree (SymmSHE.hs:438-452; include/lolhip.h), device slabs [.][B][n'][T]:
+-- plan -> p -> enc1 -> k1 -> l1 -> enc2 -> k2 -> l2 -> alpha [T] -> enc_out -> k_out -> l_out   (host only)
+foreign import ccall unsafe "lolhip_ct_mul_rule"
+  c_ctMulRule :: Ptr PlanH -> Int64 -> CInt -> Int64 -> Int64 -> CInt -> Int64 -> Int64
+              -> Ptr Int64 -> Ptr CInt -> Ptr Int64 -> Ptr Int64 -> IO CInt
+-- plan -> na -> nb -> cs_crt -> square -> B
+foreign import ccall unsafe "lolhip_ct_mul_work_len"
+  c_ctMulWorkLen :: Ptr PlanH -> CInt -> CInt -> CInt -> CInt -> Int64 -> IO Int64
+-- plan -> stream -> a -> na -> b -> nb -> cs_crt -> alpha (or nullPtr) -> out -> out_crt -> work -> B
+foreign import ccall unsafe "lolhip_ct_mul_batch"
+  c_ctMul :: Ptr PlanH -> Ptr () -> Ptr Int64 -> CInt -> Ptr Int64 -> CInt -> CInt -> Ptr Int64
+          -> Ptr Int64 -> CInt -> Ptr Int64 -> Int64 -> IO CInt
 
 -- | One plan per (prime powers, moduli), created on first use and kept for the life of the
 -- process: where CT recomputes @ru@/@ruInv@ per type (CPP.hs:422-442) and re-marshals the moduli

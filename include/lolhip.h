@@ -584,6 +584,37 @@ LOLHIP_API int lolhip_ptround_batch(const lolhip_ptround *c, void *stream, const
                                     int64_t l, int64_t *out, int out_crt, int64_t *k_out, int64_t *l_out, int64_t *work,
                                     int64_t B);
 
+/* The ciphertext product (*) of any degree (instance Ring.C (CT m zp (Cyc t m' zq)), lol-apps SymmSHE.hs:438-452).
+ * lolhip_ct_mul_rule, host only: the rule of (*) (:444-452).  enc 0 = LSD, 1 = MSD.  Both MSD -> toLSD on the first
+ *   operand: alpha_t = p mod q_t and l1 <- l1 (-Q)^-1 mod p (LOLHIP_ERR_MODULUS when gcd(Q, p) != 1), else alpha_t = 1.
+ *   enc_out = LSD iff both are LSD, else MSD;  k_out = k1 + k2 + 1;  l_out = l1 l2 mod p.  alpha: HOST array [T].
+ *   Status: LOLHIP_ERR_INVALID for NULL pointers, enc not 0 / 1, k < 0, T > 16; LOLHIP_ERR_MODULUS for p < 2 or
+ *   p >= 2^62 (every encoding pair), and as above.  Nothing is written on error.
+ * lolhip_ct_mul_batch: a [na][B][n'][T] times b [nb][B][n'][T], 1 <= na, nb <= LOLHIP_CT_MUL_MAX, residues in
+ *   (-q_t, q_t), both in the CRT basis (cs_crt = 1) or both in the powerful basis (cs_crt = 0) ->
+ *     out_k = alpha_t g sum_{i + j = k} a_i b_j mod q_t,  k < na + nb - 1,  g = gCRT (mulG <$> (c1 * c2), :449)
+ *   out [na + nb - 1][B][n'][T], canonical, in the CRT basis (out_crt = 1) or the powerful basis (out_crt = 0).  alpha:
+ *   HOST array [T] of any int64 (from lolhip_ct_mul_rule), or NULL for 1.  b == a with nb == na squares: every input
+ *   word is read once, cross terms are doubled.  a and b are only read.  Launch plan: cs_crt = 0: a and b copied into
+ *   work and one batched crt over all (na + nb) B polynomials there (the square: na B); k_ct_mul (component counts up
+ *   to 3 x 3 compiled in: two words per lane with 16-byte accesses when n' T is even and every pointer is 16-byte
+ *   aligned, else one word per lane; larger counts through the run-time form, one word per lane; two distinct linear
+ *   operands with alpha = 1 through the kernel of lolhip_ctmul_crt_batch, which computes the same); out_crt = 0: crtInv in place on out.
+ *   work: lolhip_ct_mul_work_len(pq, na, nb, cs_crt, square, B) int64 of device scratch, 16-byte aligned:
+ *   (na + (square ? 0 : nb)) B n' T for cs_crt = 0, else 0 (work may then be NULL); a negative status for bad arguments.
+ *   Status, decided on the host in this order before any launch (out is then not written): LOLHIP_ERR_INVALID for a
+ *   NULL plan, na or nb outside 1 .. LOLHIP_CT_MUL_MAX, B < 0, T > 16, a NULL pointer beside B > 0 (alpha excepted;
+ *   work only for cs_crt = 0), out = a or out = b (the output has more components than either input: it cannot alias);
+ *   LOLHIP_ERR_NO_CRT when pq has no CRT basis; LOLHIP_ERR_NO_DEVICE on a host-only plan, LOLHIP_ERR_DEVICE as
+ *   elsewhere.  B = 0 returns LOLHIP_OK.  A failing launch (LOLHIP_ERR_HIP) leaves out undefined.  The call does not
+ *   allocate or synchronise (beyond what crt / crtInv do). */
+#define LOLHIP_CT_MUL_MAX 8
+LOLHIP_API int lolhip_ct_mul_rule(const lolhip_plan *pq, int64_t p, int enc1, int64_t k1, int64_t l1, int enc2, int64_t k2,
+                                  int64_t l2, int64_t *alpha, int *enc_out, int64_t *k_out, int64_t *l_out);
+LOLHIP_API int64_t lolhip_ct_mul_work_len(const lolhip_plan *pq, int na, int nb, int cs_crt, int square, int64_t B);
+LOLHIP_API int lolhip_ct_mul_batch(const lolhip_plan *pq, void *stream, const int64_t *a, int na, const int64_t *b, int nb,
+                                   int cs_crt, const int64_t *alpha, int64_t *out, int out_crt, int64_t *work, int64_t B);
+
 /* --- gSqNormDec and RLWE / RLWR instances (lol RLWE/{Continuous,Discrete,RLWR}.hs; rlwe-challenges Generate.hs:192-218,
  * Verify.hs:346-366), device pointers ------------------------------------------------------------------------------
  * gSqNormDec (Tensor.hs:147-151; norm.cpp:15-75): e_dec [B][n] decoding-basis coefficients -> out [B],

@@ -119,6 +119,9 @@ ABI = _rows(
     ("ct_affine_mul_batch", ci, vp, vp, vp, _i64p, vp, vp, _i64p, vp, ci, vp, i64),
     ("ptround_create", ci, ci, i64, vpp, vpp, vpp, i64, vp, vp, vp, vpp),
     ("ptround_batch", ci, vp, vp, vp, ci, ci, i64, i64, vp, ci, _i64p, _i64p, vp, i64),
+    ("ct_mul_rule", ci, vp, i64, ci, i64, i64, ci, i64, i64, _i64p, cip, _i64p, _i64p),
+    ("ct_mul_work_len", i64, vp, ci, ci, ci, ci, i64),
+    ("ct_mul_batch", ci, vp, vp, vp, ci, vp, ci, ci, _i64p, vp, ci, vp, i64),
     ("crtset_dec", i64, pp, ci, pp, ci, i64, _i64p, i64),
     ("crtset_modulus", i64, pp, ci, i64, ci),
     ("crtset_host", i64, pp, ci, pp, ci, i64, ci, _i64p, i64),

@@ -1,6 +1,6 @@
 // lol_amd/csrc/elementwise_dev.h — the building blocks the element-wise passes share (pipeline.hip, decrypt.hip,
-// encrypt.hip, kshint.hip, khprf.hip, public.hip, modswitch.hip, ptround.hip, pttunnel.hip, ringmul.hip, gadget.hip and
-// the element-wise launches of kernels.hip).  Host side of a launch: the tile count (tiles_for), the capped
+// encrypt.hip, kshint.hip, khprf.hip, public.hip, modswitch.hip, ptround.hip, pttunnel.hip, ringmul.hip, gadget.hip,
+// ctmul.hip and the element-wise launches of kernels.hip).  Host side of a launch: the tile count (tiles_for), the capped
 // block count of a grid-stride launch (grid_stride_blocks) and the 16-byte alignment test of the two-words-per-lane
 // variants (aligned16).  Device side: the 16-byte store type, two scalar reductions (trim, mod_any), the floor division
 // by an invariant divisor (floor_div_inv), the centred lift (centred), the mixed-radix digits of an RNS value

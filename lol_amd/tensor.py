@@ -796,6 +796,73 @@ class Plan(_Handle):
                 raise ValueError("va / vb are not [npairs][n][T]")
         return _run(call, stream, (a, b, va, vb), B, None, lambda: (npairs, 3, B, self.n, self.T), out=out, dry=False)
 
+    # ---- the ciphertext product (*) of any degree and the ciphertext-level key switches (SymmSHE.hs:339-371, 438-452) --
+    def ctMulRule(self, p, enc1, k1, l1, enc2, k2, l2):
+        """The rule of (*) (SymmSHE.hs:444-452), host only -> (alpha, enc, k, l): both MSD -> toLSD on the first operand
+        (alpha_t = p mod q_t, l1 (-Q)^-1), else alpha_t = 1; enc = LSD iff both are; k = k1 + k2 + 1; l = l1 l2 mod p."""
+        al, e, k, l = (C.c_int64 * self.T)(), C.c_int(0), C.c_int64(0), C.c_int64(0)
+        _check(lib().lolhip_ct_mul_rule(self._h, int(p), _enc(enc1), int(k1), int(l1), _enc(enc2), int(k2), int(l2), al,
+                                        C.byref(e), C.byref(k), C.byref(l)), "ct_mul_rule")
+        return al, ("LSD", "MSD")[e.value], int(k.value), int(l.value)
+
+    def ctMul(self, ct1, ct2=None, p=None, cs_crt=False, out_crt=None, stream=None):
+        """(*) (SymmSHE.hs:438-452) of ct = (cs, enc, k, l) as ctAdd takes it, any number of components up to 8 each:
+        mulG <$> (c1 * c2) with the toLSD factor of the MSD x MSD case folded in (lolhip_ct_mul_batch).  ct2 None, or
+        ct1 itself, squares.  cs in the powerful basis, or the CRT basis with cs_crt; the result in the basis out_crt
+        asks for (default: that of the inputs).  Returns (cs [na + nb - 1][B][n][T], enc, k, l)."""
+        if p is None:
+            raise TypeError("ctMul needs the plaintext modulus p")
+        square = ct2 is None or ct2 is ct1
+        (c1, e1, k1, l1), (c2, e2, k2, l2) = ct1, (ct1 if square else ct2)
+        al, enc, k, l = self.ctMulRule(p, e1, k1, l1, e2, k2, l2)
+        out_crt = cs_crt if out_crt is None else out_crt
+        _, a, na, B = self._cs(c1)
+        b, nb = a, na
+        if not square:
+            _, b, nb, Bb = self._cs(c2)
+            if Bb != B:
+                raise ValueError("batch sizes differ")
+        L = lib()
+        out = _run(lambda st, i, o, w, n: L.lolhip_ct_mul_batch(self._h, st, i[0], na, i[0] if square else i[1], nb,
+                                                                 int(cs_crt), al, o[0], int(out_crt), w, n),
+                   stream, (a,) if square else (a, b), B,
+                   lambda: L.lolhip_ct_mul_work_len(self._h, na, nb, int(cs_crt), int(square), B),
+                   lambda: (na + nb - 1, B, self.n, self.T))
+        return out, enc, k, l
+
+    def _ksCT(self, hint, ct, base, p, cs_crt, stream, deg):
+        """toMSD, then c_0 .. c_(deg-1) + switch hint c_deg for a ciphertext of deg + 1 components; a shorter one is
+        returned as it is (SymmSHE.hs:343-371)"""
+        cs, enc, k, l = ct
+        _, cs, ncs, B = self._cs(cs)
+        if ncs <= deg:
+            return ct
+        if ncs > deg + 1:
+            raise ValueError(f"a ciphertext of {ncs} components: this key switch takes at most {deg + 1}")
+        cs, _, l = self.toMSD(cs, p, enc, l, stream=stream)
+        host, (cs, hint) = _stage(cs, hint)
+        cs = cs.reshape(ncs, B, self.n, self.T)
+        last = cs[deg].clone()
+        add = _alloc((2, B, self.n, self.T), "int64", cs.device).zero_()
+        add[:deg] = cs[:deg]
+        if cs_crt:
+            self.crtInv(last, stream=stream)                      # switch decomposes in the powerful basis
+        else:
+            self.crt(add[:deg], stream=stream)
+        return _unstage(host, self.keySwitch(last, base, hint, addend=add, stream=stream)), "MSD", int(k), l
+
+    def keySwitchLinear(self, hint, ct, base, p, cs_crt=False, stream=None):
+        """keySwitchLinear (SymmSHE.hs:339-348): toMSD, then (c0 + switch hint c1) for a linear ciphertext
+        ct = (cs, enc, k, l) -> (cs [2][B][n][T] in the CRT basis, "MSD", k, l'), a ciphertext under the hint's output
+        key; one of fewer components is returned unchanged.  hint: Plan.ksLinearHint's, over the gadget of `base`."""
+        return self._ksCT(hint, ct, base, p, cs_crt, stream, 1)
+
+    def keySwitchQuadCirc(self, hint, ct, base, p, cs_crt=False, stream=None):
+        """keySwitchQuadCirc (SymmSHE.hs:361-371): toMSD, then ((c0, c1) + switch hint c2) for a quadratic ciphertext
+        ct = (cs, enc, k, l) -> (cs [2][B][n][T] in the CRT basis, "MSD", k, l'); one of fewer components is returned
+        unchanged.  hint: Plan.ksQuadCircHint's, over the gadget of `base`."""
+        return self._ksCT(hint, ct, base, p, cs_crt, stream, 2)
+
     def absorbGFactors(self, cs, k, pp, stream=None):
         """absorbGFactors (SymmSHE.hs:464-473) of a CRT-basis ciphertext: every c_i times decode'(divG^k 1), divG over
         pp (the Plan of this index over p alone) -> (cs, 0)"""
@@ -908,6 +975,29 @@ class Ext(_Handle):
                                                                        int(base), kb, int(ctr), o[0], w),
                     stream, (ys_crt, s_in_crt, s_out_crt), 0, lambda: wl, lambda: (rel, S.decomposeLen(base), 2, S.n, S.T),
                     dry=False)
+
+    def _mapCT(self, ct, maps, basis, what):
+        cs, enc, k, l = ct
+        if int(k) != 0:
+            raise ValueError(f"{what} requires 0 factors of g; call absorbGFactors first")
+        if basis not in maps:
+            raise ValueError(f"{what}: basis is one of {sorted(maps)}")
+        src = self.hi if what == "twaceCT" else self.lo
+        _, cs, ncs, B = src._cs(cs)
+        out = maps[basis](cs)
+        return out.reshape(ncs, B, *out.shape[-2:]), enc, 0, l
+
+    def embedCT(self, ct, basis="pow", stream=None):
+        """embedCT (SymmSHE.hs:477-487): embed on every component of ct = (cs, enc, k, l) over the lower ring, cs in
+        `basis` ("pow", "dec" or "crt") -> the ciphertext over the higher ring in the same basis.  k must be 0."""
+        maps = {"pow": self.embedPow, "dec": self.embedDec, "crt": self.embedCRT}
+        return self._mapCT(ct, {b: (lambda x, f=f: f(x, stream=stream)) for b, f in maps.items()}, basis, "embedCT")
+
+    def twaceCT(self, ct, basis="pow", stream=None):
+        """twaceCT (SymmSHE.hs:498-503): twace on every component of ct = (cs, enc, k, l) over the higher ring, cs in
+        `basis` ("pow", "dec" or "crt") -> the ciphertext over the lower ring in the same basis.  k must be 0."""
+        maps = {"pow": self.twacePowDec, "dec": self.twacePowDec, "crt": self.twaceCRT}
+        return self._mapCT(ct, {b: (lambda x, f=f: f(x, stream=stream)) for b, f in maps.items()}, basis, "twaceCT")
 
     def twacePowDec(self, x, out=None, stream=None): return self._map(EXT_TWACE_POWDEC, "twace_powdec", x, False, out, stream)
     def twaceCRT(self, x, out=None, stream=None): return self._map(EXT_TWACE_CRT, "twace_crt", x, False, out, stream)

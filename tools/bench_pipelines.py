@@ -8,7 +8,8 @@ ring PRF (`--khprf`: that leg alone; `--khprf-lifted`: its lifted family over q 
 verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlwe_pipelines.jsonl) and of the exact ring
 product over moduli without a CRT basis (`--ringmul`: that leg alone, also written to profiles/ringmul_pipelines.jsonl)
 and of gadget error correction (`--gadget-correct`: that leg alone, also written to profiles/gadget_correct_pipelines.jsonl)
-and of L / divG over int64 and double slabs (`--eltops`: that leg alone, also written to profiles/eltops_bench.jsonl).
+and of L / divG over int64 and double slabs (`--eltops`: that leg alone, also written to profiles/eltops_bench.jsonl)
+and of the ciphertext product of any degree (`--ctmul`: that leg alone, also written to profiles/ctmul_bench.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -859,8 +860,139 @@ def eltops_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def ctmul_leg(gen):
+    """The ciphertext product of any degree (lolhip_ct_mul_batch) at the shape of bench.py's c3_ctmul_pow leg (m = 2^15,
+    four ~59-bit moduli, B = 256), against entries whose device code is older than it, in one process:
+      (a) linear x linear, CRT -> CRT: against lolhip_ctmul_crt_batch (without a factor the entry launches the same
+          kernel, k_ctmul; `_msd`: with the MSD x MSD factor it launches k_ct_mul<2, 2>);
+      (b) linear x linear, powerful -> powerful, MSD x MSD: against the composition ctLinComb (toLSD), 4 crt, ctMulCRT,
+          3 crtInv (in place on its second operand, as bench.py's leg), and against the same composition with a copy of
+          that operand in front (`_keep`): the new entry only reads its operands;
+      (c) 3 x 3 components and the square of a quadratic ciphertext, CRT -> CRT: against lolhip_copy_slab moving the same
+          number of bytes.
+    Every round times the baseline twice (base_a, base_b) and the new entry once, each over a window of about a
+    quarter of a second of calls, the order alternating from round to round; a row holds the medians over the rounds, and `spread_ms` = |median base_a - median base_b| is what two runs of
+    the baseline alone differ by.  `within_spread`: new <= min(base_a, base_b) + spread.
+    Also written to profiles/ctmul_bench.jsonl."""
+    import ctypes as C
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    lines = []
+    m, T, B, p, ROUNDS = 2 ** 15, 4, 256, 5, 6
+    qs = good_qs(m, 2 ** 59, T)
+    P = lol_amd.Plan([(2, 15)], qs)
+    slab = B * P.n * P.T * 8
+    cfg = f"m=2^15 T=4 59-bit B={B} ({slab >> 20} MiB per component)"
+
+    def emit(d):
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+
+    def window(fn, iters):
+        """ms per call over one window of `iters` calls between two events"""
+        s_, e_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s_.record()
+        for _ in range(iters):
+            fn()
+        e_.record()
+        torch.cuda.synchronize()
+        return s_.elapsed_time(e_) / iters
+
+    def versus(name, new, base, alg_bytes, new_note, base_note):
+        assert new() == 0
+        base()
+        # windows of about a quarter of a second each (shorter ones measure the clock ramp), after as much warm-up
+        iters = max(10, int(250.0 / max(window(new, 20), window(base, 20))))
+        window(new, iters), window(base, iters)
+        ts = {"new": [], "base_a": [], "base_b": []}
+        for r in range(ROUNDS):
+            order = ("base_a", "new", "base_b") if r % 2 == 0 else ("new", "base_b", "base_a")
+            for which in order:
+                ts[which].append(window(new if which == "new" else base, iters))
+        med = {k: statistics.median(v) for k, v in ts.items()}
+        spread = abs(med["base_a"] - med["base_b"])
+        best = min(med["base_a"], med["base_b"])
+        for which, note in (("new", new_note), ("base_a", base_note), ("base_b", base_note)):
+            d = {"op": f"{name}:{which}", "config": cfg, "ms": round(med[which], 4), "ms_min": round(min(ts[which]), 4),
+                 "ms_max": round(max(ts[which]), 4), "calls_per_window": iters, "alg_bytes": alg_bytes,
+                 "alg_GBps": round(alg_bytes / med[which] / 1e6, 1), "note": note}
+            if which == "new":
+                d.update(spread_ms=round(spread, 4), ratio_to_base=round(med["new"] / best, 4),
+                         within_spread=bool(med["new"] <= best + spread))
+            emit(d)
+
+    a, b = torch.stack([rnd(gen, qs, B, P.n) for _ in range(2)]), torch.stack([rnd(gen, qs, B, P.n) for _ in range(2)])
+    out = torch.empty((3, B, P.n, P.T), dtype=torch.int64, device="cuda")
+    # (a)
+    versus("ctmul_2x2_crt", lambda: L.lolhip_ct_mul_batch(P._h, st, ptr(a), 2, ptr(b), 2, 1, None, ptr(out), 1, None, B),
+           lambda: L.lolhip_ctmul_crt_batch(P._h, st, ptr(a[0]), ptr(a[1]), ptr(b[0]), ptr(b[1]), ptr(out[0]), ptr(out[1]),
+                                            ptr(out[2]), B),
+           7 * slab, "lolhip_ct_mul_batch, CRT -> CRT, no factor: routed to k_ctmul", "lolhip_ctmul_crt_batch")
+    al, e_, k_, l_ = (C.c_int64 * T)(), C.c_int(0), C.c_int64(0), C.c_int64(0)
+    assert L.lolhip_ct_mul_rule(P._h, p, 1, 0, 1, 1, 0, 1, al, C.byref(e_), C.byref(k_), C.byref(l_)) == 0
+    versus("ctmul_2x2_crt_msd", lambda: L.lolhip_ct_mul_batch(P._h, st, ptr(a), 2, ptr(b), 2, 1, al, ptr(out), 1, None, B),
+           lambda: L.lolhip_ctmul_crt_batch(P._h, st, ptr(a[0]), ptr(a[1]), ptr(b[0]), ptr(b[1]), ptr(out[0]), ptr(out[1]),
+                                            ptr(out[2]), B),
+           7 * slab, "lolhip_ct_mul_batch, CRT -> CRT, MSD x MSD (alpha = p mod q_t): k_ct_mul<2, 2>",
+           "lolhip_ctmul_crt_batch (no factor: not the same result, the same traffic)")
+    # (b)
+    wl = L.lolhip_ct_mul_work_len(P._h, 2, 2, 0, 0, B)
+    work = torch.empty((wl,), dtype=torch.int64, device="cuda")
+    tmp = torch.empty_like(a)
+    zq, _ = P.encodeScales(p, False)
+    zq = (C.c_int64 * T)(*zq)
+
+    def composed():
+        L.lolhip_ct_lincomb_batch(P._h, st, ptr(a), 2, zq, None, 0, None, ptr(tmp), B)        # toLSD of the first operand
+        for x in (tmp[0], tmp[1], b[0], b[1]):
+            L.lolhip_crt_batch(P._h, st, ptr(x), B)
+        L.lolhip_ctmul_crt_batch(P._h, st, ptr(tmp[0]), ptr(tmp[1]), ptr(b[0]), ptr(b[1]), ptr(out[0]), ptr(out[1]), ptr(out[2]), B)
+        for x in out:
+            L.lolhip_crtinv_batch(P._h, st, ptr(x), B)
+
+    versus("ctmul_2x2_pow_msd", lambda: L.lolhip_ct_mul_batch(P._h, st, ptr(a), 2, ptr(b), 2, 0, al, ptr(out), 0, ptr(work), B),
+           composed, 7 * slab, "lolhip_ct_mul_batch, powerful -> powerful, MSD x MSD: 2 copies, crt over 4 B, product, crtInv over 3 B",
+           "ctLinComb (toLSD), 4 crt, ctMulCRT, 3 crtInv (9 launches), in place on its operands")
+    tmpb = torch.empty_like(b)
+
+    def composed_keep():
+        """the same composition leaving its operands as it found them, as the new entry does: b is copied first"""
+        L.lolhip_copy_slab(st, ptr(tmpb), ptr(b), 2 * slab, 0)
+        L.lolhip_ct_lincomb_batch(P._h, st, ptr(a), 2, zq, None, 0, None, ptr(tmp), B)
+        for x in (tmp[0], tmp[1], tmpb[0], tmpb[1]):
+            L.lolhip_crt_batch(P._h, st, ptr(x), B)
+        L.lolhip_ctmul_crt_batch(P._h, st, ptr(tmp[0]), ptr(tmp[1]), ptr(tmpb[0]), ptr(tmpb[1]), ptr(out[0]), ptr(out[1]), ptr(out[2]), B)
+        for x in out:
+            L.lolhip_crtinv_batch(P._h, st, ptr(x), B)
+
+    versus("ctmul_2x2_pow_msd_keep", lambda: L.lolhip_ct_mul_batch(P._h, st, ptr(a), 2, ptr(b), 2, 0, al, ptr(out), 0, ptr(work), B),
+           composed_keep, 7 * slab, "lolhip_ct_mul_batch, powerful -> powerful, MSD x MSD (the same call as above)",
+           "copy of b, ctLinComb (toLSD), 4 crt, ctMulCRT, 3 crtInv (10 launches): the composition with its operands left intact")
+    del work, tmp, tmpb, a, b, out
+    # (c)
+    a3, b3 = (torch.stack([rnd(gen, qs, B, P.n) for _ in range(3)]) for _ in range(2))
+    out5 = torch.empty((5, B, P.n, P.T), dtype=torch.int64, device="cuda")
+    src = torch.empty((11 * slab // 16,), dtype=torch.int64, device="cuda")
+    dst = torch.empty_like(src)
+    versus("ctmul_3x3_crt", lambda: L.lolhip_ct_mul_batch(P._h, st, ptr(a3), 3, ptr(b3), 3, 1, None, ptr(out5), 1, None, B),
+           lambda: L.lolhip_copy_slab(st, ptr(dst), ptr(src), 11 * slab // 2, 0), 11 * slab,
+           "lolhip_ct_mul_batch, 3 x 3 components, CRT -> CRT", "lolhip_copy_slab moving the same 11 slabs (5.5 read, 5.5 written)")
+    versus("ctmul_square3_crt", lambda: L.lolhip_ct_mul_batch(P._h, st, ptr(a3), 3, ptr(a3), 3, 1, None, ptr(out5), 1, None, B),
+           lambda: L.lolhip_copy_slab(st, ptr(dst), ptr(src), 8 * slab // 2, 0), 8 * slab,
+           "lolhip_ct_mul_batch, the square of a quadratic ciphertext, CRT -> CRT", "lolhip_copy_slab moving the same 8 slabs (4 read, 4 written)")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "ctmul_bench.jsonl"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--ctmul" in sys.argv:            # the ciphertext product of any degree leg alone
+        ctmul_leg(gen)
+        return
     if "--eltops" in sys.argv:           # the L / divG over Z and R leg alone
         eltops_leg(gen)
         return
