@@ -417,6 +417,50 @@ LOLHIP_API int lolhip_khprf_create_lifted(const lolhip_plan *pq, const lolhip_pl
                                           const int32_t *tree, int ntree, const int64_t *a0_pow,
                                           const int64_t *a1_pow, lolhip_khprf **out);
 
+/* key-homomorphic PRF over standard lattices, eq. (2.3) of [BP14] (lol-apps KeyHomomorphicPRF.hs:189-207 latticePRF',
+ * latticePRFM, over buildDecTree / evalTree), one modulus q, 2 <= q < 2^62 (even and 2-power moduli included: no
+ * cyclotomic index and no CRT basis are involved).  With l = gadlen(base, q) (1 for base 0 = TrivGad) and K = n l, a
+ * family is a full binary tree of k leaves (1 <= k <= 62, the encoding of lolhip_khprf_create) and A0, A1 in Z_q^(n x K):
+ *     A_leaf(x) = A_x;   A_(I c l r)(x) = A_l(x >> c_r) * G^-1(A_r(x & (2^c_r - 1)))
+ *   G^-1 = fmap reduce . decomposeMatrix (Gadget.hs:76-81) is K x K: row i l + j of column c is digit j of entry (i, c),
+ *   digits ordered and centred as lolhip_decompose_batch does (ZqBasic.hs:227-232, 258-264).
+ *     latticePRF' s x = rescale <$> s * A_T(x), s in Z_q^(1 x n):  y = fst (divModCent (p lift z) q) mod p per entry z
+ *   (lift centred into [-q/2, q/2); divModCent a q = floor((a + q div 2) / q)).
+ * lolhip_lprf_create: a0, a1 HOST arrays [n][K] of any int64, taken mod q.  The family lives on the calling thread's
+ *   current device (as a plan does); without a device it is host-only and answers work_len only.  Allocates and
+ *   synchronises; nothing after it does.
+ * lolhip_lprf_work_len: int64 words of scratch of a call over inputs [x0, x0 + B); nkeys = 0 for eval_batch, the key count
+ *   for batch (negative status on error).  With U_v = min(2^c_v, ((x0 + B - 1) >> s_v) - (x0 >> s_v) + 1) the slot count
+ *   of node v (2 for a leaf) as for lolhip_khprf_work_len:
+ *       sum over internal nodes v other than the root of U_v n K,  plus for nkeys > 0 and an internal root  U_l nkeys K
+ *   (s A_l for every slot of the root's left child l); 0 for B = 0 or a one-leaf tree.  There is no per-slot K x K term:
+ *   the digits of a right operand are produced where its tile is loaded and never stored.
+ * lolhip_lprf_eval_batch: out [B][n][K] = A_T(x) for x = x0 .. x0 + B - 1, residues in [0, q); every distinct subtree
+ *   value of the window is computed once.
+ * lolhip_lprf_batch: s [nkeys][n] on the device, any int64 (taken mod q); out [nkeys][B][K] = latticePRF s_key x in
+ *   [0, p).  The root is computed as (s A_l) * G^-1(A_r) (nkeys rows instead of n; the same residues mod q), with the
+ *   rounding in its write-back.
+ * Node products take one of two routes with the same bits: the matrix cores (i8 MFMA: the left operand in W <= 8
+ *   balanced base-256 limbs, the digits as int8, one i32 sum per limb recombined mod q) where max|digit| <= 127 and
+ *   K 128 max|digit| < 2^31 are certified from (q, base) and K >= 56 (below that a call is bound by its launches and
+ *   the matrix route measured no faster), else int64 lazy sums on the vector ALU (debug switch LPRF_VALU forces this).  With the environment variable LOLHIP_LPRF_INFO set (read at every call) each node launch
+ *   prints one line to stderr: "k_lprf: route <mfma|valu>, M <rows>, N <cols>, K <depth>, W <limbs>, slots <U>".
+ * Status, decided on the host before any launch (the output is then not written): LOLHIP_ERR_INVALID for n < 1, a
+ *   malformed tree or k > 62, base 1 or negative, NULL pointers, x0 < 0, B < 0, x0 + B > 2^k, nkeys < 1 for batch (< 0
+ *   for work_len), n K >= 2^31; LOLHIP_ERR_MODULUS for q < 2, q >= 2^62, p < 2, p >= q, p q >= 2^63; LOLHIP_ERR_NO_DEVICE
+ *   on a host-only family; LOLHIP_ERR_DEVICE when the current device is not the family's. */
+typedef struct lolhip_lprf lolhip_lprf;
+LOLHIP_API int lolhip_lprf_create(int64_t q, int64_t base, int n, const int32_t *tree, int ntree, const int64_t *a0,
+                                  const int64_t *a1, lolhip_lprf **out);
+LOLHIP_API void lolhip_lprf_destroy(lolhip_lprf *f);
+LOLHIP_API int lolhip_lprf_n(const lolhip_lprf *f);
+LOLHIP_API int lolhip_lprf_ell(const lolhip_lprf *f);
+LOLHIP_API int64_t lolhip_lprf_work_len(const lolhip_lprf *f, int nkeys, int64_t x0, int64_t B);
+LOLHIP_API int lolhip_lprf_eval_batch(const lolhip_lprf *f, void *stream, int64_t x0, int64_t B, int64_t *out,
+                                      int64_t *work);
+LOLHIP_API int lolhip_lprf_batch(const lolhip_lprf *f, void *stream, const int64_t *s, int nkeys, int64_t p, int64_t x0,
+                                 int64_t B, int64_t *out, int64_t *work);
+
 /* SymmSHE public operations and ciphertext addition (lol-apps SymmSHE.hs:214-230, 381-436; ZqBasic.hs:92-94,132-137).
  * A ciphertext is CT enc k l c over R'_q (pq: index m', moduli q_0..q_{T-1}, Q = prod q_t): components cs
  * [ncs][B][n'][T].  Public values are elements of R_m (m | m') mod p in the powerful basis, [B][n_m] int64 of any value
@@ -968,7 +1012,7 @@ LOLHIP_API int64_t lolhip_chain_write(const uint8_t *const *elems, const int64_t
 LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_t bytes, int variant);
 
 /* Test and A/B aid, not part of the drop-in surface: force a launch path.  `name` is one of
- * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC and ELT_GLOBAL (each is
+ * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL and LPRF_VALU (each is
  * also read ONCE at first use from the environment variable LOLHIP_<name>); value 0 restores the
  * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID.
  * Two environment variables are test hooks of the persistent pipelined poly-mul, read at EVERY launch of it:

@@ -67,7 +67,7 @@ ABI = _rows(
     # plans and the Tensor operations
     ("plan_create", ci, pp, ci, _i64p, ci, ci, vpp),
     ("plan_create_roots", ci, pp, ci, _i64p, ci, _i64p, _i64p, ci, vpp),
-    ("plan_destroy ext_destroy khprf_destroy tunnel_chain_destroy ptround_destroy pt_tunnel_destroy ringmul_destroy", None, vp),
+    ("plan_destroy ext_destroy khprf_destroy tunnel_chain_destroy ptround_destroy pt_tunnel_destroy ringmul_destroy lprf_destroy", None, vp),
     ("plan_n plan_m", i64, vp),
     ("plan_T plan_has_crt", ci, vp),
     ("plan_table", i64, vp, ci, ci, _i64p, i64),
@@ -108,6 +108,11 @@ ABI = _rows(
     ("khprf_create_lifted", ci, vp, vp, i64, _i32p, ci, _i64p, _i64p, vpp),
     ("khprf_eval_batch", ci, vp, vp, i64, i64, vp, vp),
     ("khprf_batch", ci, vp, vp, vp, ci, i64, i64, i64, vp, vp),
+    ("lprf_create", ci, i64, i64, ci, _i32p, ci, _i64p, _i64p, vpp),
+    ("lprf_n lprf_ell", ci, vp),
+    ("lprf_work_len", i64, vp, ci, i64, i64),
+    ("lprf_eval_batch", ci, vp, vp, i64, i64, vp, vp),
+    ("lprf_batch", ci, vp, vp, vp, ci, i64, i64, i64, vp, vp),
     ("encode_scales", ci, vp, i64, ci, _i64p, _i64p),
     ("ct_lincomb_batch", ci, vp, vp, vp, ci, _i64p, vp, ci, _i64p, vp, i64),
     ("add_public_batch", ci, vp, vp, vp, vp, vp, i64, vp, ci, ci, ci, ci, i64, i64, i64, vp, _i64p, vp, i64),

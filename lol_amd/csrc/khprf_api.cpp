@@ -1,6 +1,7 @@
 // lol_amd/csrc/khprf_api.cpp — the C ABI of the key-homomorphic ring PRF (include/lolhip.h; lol-apps
-// KeyHomomorphicPRF.hs buildDecTree / ringPRF'): the tree, the slot planner over an input window and the launch plan
-// over the existing crt / crtInv / lInv / decompose and the kernels of khprf.hip.
+// KeyHomomorphicPRF.hs buildDecTree / ringPRF'): the family and the launch plan over the existing crt / crtInv / lInv /
+// decompose and the kernels of khprf.hip.  The tree and the slot planner over an input window are prftree.h's, shared
+// with the lattice PRF (lprf_api.cpp).
 //
 // The lifted family (lolhip_khprf_create_lifted) runs over q = 2^k, which has no CRT basis: every node product is
 // computed exactly over the integers in the CRT basis mod an NTT prime Q (certified at creation) and brought back to
@@ -12,19 +13,10 @@
 #include <memory>
 #include <vector>
 
+#include "prftree.h"
 #include "she_host.h"
 
 using namespace lolhip;
-
-namespace {
-
-struct KNode {
-  int c;        // leaves
-  int s;        // leaves to its right: the node sees (x >> s) & (2^c - 1)
-  int l, r;     // children (-1 for a leaf)
-};
-
-}  // namespace
 
 struct lolhip_khprf {
   const lolhip_plan* pq = nullptr;
@@ -33,7 +25,7 @@ struct lolhip_khprf {
   int64_t base = 0;
   int ell = 0;                   // gadget length L
   int k = 0;                     // leaves
-  std::vector<KNode> nodes;      // preorder; nodes[0] is the root
+  std::vector<PrfNode> nodes;    // preorder; nodes[0] is the root
   DecompParams dp{};
   ModCtx mc{};
   int fold = 1;                  // Q32 digits per 64-bit sum of k_khprf_node
@@ -44,85 +36,19 @@ struct lolhip_khprf {
 
 namespace {
 
-// preorder leaf counts -> nodes; returns the index after the subtree at pos, or -1
-int parse(const int32_t* tree, int ntree, int pos, int s, std::vector<KNode>& out, int depth) {
-  if (pos >= ntree || depth > 64) return -1;
-  const int c = tree[pos];
-  const int me = (int)out.size();
-  out.push_back(KNode{c, s, -1, -1});
-  if (c == 1) return pos + 1;
-  if (c < 1) return -1;
-  // the right subtree's size is known only after the left one is parsed: shifts of the left subtree are fixed after
-  const int lpos = pos + 1;
-  const int l = (int)out.size();
-  int next = parse(tree, ntree, lpos, 0, out, depth + 1);
-  if (next < 0) return -1;
-  const int cl = out[l].c;
-  if (cl >= c) return -1;
-  const int cr = c - cl;
-  const int r = (int)out.size();
-  next = parse(tree, ntree, next, s, out, depth + 1);
-  if (next < 0 || out[r].c != cr) return -1;
-  out[me].l = l;
-  out[me].r = r;
-  // the left subtree was parsed with shift 0: it sits cr + s leaves from the right
-  for (int i = l; i < r; ++i) out[i].s += s + cr;
-  return next;
-}
-
-bool is_leaf(const KNode& v) { return v.l < 0; }
-
-// the node's view of the window [x0, x0 + B), B >= 1
-struct View { int64_t U, lo; bool full; };
-View view(const KNode& v, int64_t x0, int64_t B) {
-  View w;
-  w.lo = x0 >> v.s;
-  const int64_t span = ((x0 + B - 1) >> v.s) - w.lo + 1;
-  const int64_t all = (int64_t)1 << v.c;
-  w.U = span < all ? span : all;
-  w.full = w.U == all;
-  if (v.l < 0) { w.U = 2; w.full = true; }                // a leaf: its two vectors a0, a1
-  return w;
-}
+using KNode = PrfNode;
+using View = PrfView;
+using Layout = PrfLayout;
+bool is_leaf(const KNode& v) { return prf_is_leaf(v); }
+View view(const KNode& v, int64_t x0, int64_t B) { return prf_view(v, x0, B); }
 
 // work offsets of one call: values of every internal node (root last) and digits of every internal right child
-struct Layout {
-  std::vector<int64_t> val, dig;   // per node, -1 where none
-  int64_t total = 0;
-};
 Layout layout(const lolhip_khprf& f, int64_t x0, int64_t B) {
-  Layout L;
-  const size_t N = f.nodes.size();
-  L.val.assign(N, -1);
-  L.dig.assign(N, -1);
-  if (B == 0) return L;
   const int64_t ln = (int64_t)f.ell * f.pq->P.n;
-  for (size_t i = 1; i < N; ++i) {
-    const KNode& v = f.nodes[i];
-    if (is_leaf(v)) continue;
-    const int64_t U = view(v, x0, B).U;
-    L.val[i] = L.total;
-    L.total += U * ln;
-  }
-  for (size_t i = 0; i < N; ++i) {
-    const KNode& v = f.nodes[i];
-    if (is_leaf(v) || is_leaf(f.nodes[v.r])) continue;
-    const int64_t Ur = view(f.nodes[v.r], x0, B).U;
-    L.dig[v.r] = L.total;
-    L.total += (int64_t)f.ell * Ur * ln;
-  }
-  if (!is_leaf(f.nodes[0])) {
-    L.val[0] = L.total;
-    L.total += B * ln;
-  }
-  return L;
+  return prf_layout(f.nodes, x0, B, ln, f.ell, B * ln);
 }
 
-bool range_ok(const lolhip_khprf* f, int64_t x0, int64_t B) {
-  if (!f || x0 < 0 || B < 0) return false;
-  const int64_t dom = (int64_t)1 << f->k;
-  return x0 <= dom && B <= dom - x0;
-}
+bool range_ok(const lolhip_khprf* f, int64_t x0, int64_t B) { return f && prf_range_ok(f->k, x0, B); }
 
 bool q_below31(const Plan& P) { return P.qs[0] < ((u64)1 << 31); }
 
@@ -246,18 +172,6 @@ int upload_lifted(lolhip_khprf* f, const std::vector<int64_t>& a) {
   return rc ? rc : rs;
 }
 
-// the largest |digit| of decompose over lift_q: remainders in [-b/2, b/2), the last digit f^(k-1)(v) for v in
-// [-q/2, q/2) with f v = floor((v + b/2) / b) monotone; TrivGad: q/2
-u64 max_digit(u64 q, int64_t base, int k) {
-  if (base == 0) return q / 2;
-  auto fl = [&](int64_t a) { const int64_t d = a + base / 2; return d >= 0 ? d / base : -((-d + base - 1) / base); };
-  int64_t lo = -(int64_t)(q / 2), hi = (int64_t)(q / 2) - 1;
-  for (int i = 0; i + 1 < k; ++i) { lo = fl(lo); hi = fl(hi); }
-  u64 m = (u64)(base / 2);
-  m = std::max(m, (u64)(lo < 0 ? -lo : lo));
-  return std::max(m, (u64)(hi < 0 ? -hi : hi));
-}
-
 }  // namespace
 
 extern "C" {
@@ -271,7 +185,7 @@ int lolhip_khprf_create(const lolhip_plan* pq, int64_t base, const int32_t* tree
   f->pq = pq;
   f->base = base;
   int rc = make_decomp(P, base, f->dp);
-  if (!rc && (parse(tree, ntree, 0, 0, f->nodes, 0) != ntree || f->nodes[0].c > 62)) rc = LOLHIP_ERR_INVALID;
+  if (!rc && !prf_tree(tree, ntree, f->nodes)) rc = LOLHIP_ERR_INVALID;
   if (!rc && !P.has_crt) rc = LOLHIP_ERR_NO_CRT;
   if (rc) return rc;
   f->ell = f->dp.L;
@@ -305,7 +219,7 @@ int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int
   f->pQ = pQ;
   f->base = base;
   int rc = make_decomp(P, base, f->dp);
-  if (!rc && (parse(tree, ntree, 0, 0, f->nodes, 0) != ntree || f->nodes[0].c > 62)) rc = LOLHIP_ERR_INVALID;
+  if (!rc && !prf_tree(tree, ntree, f->nodes)) rc = LOLHIP_ERR_INVALID;
   const u64 q = P.qs[0], Q = PQ.qs[0];
   if (!rc && (q < 2 || (q & (q - 1)) != 0)) rc = LOLHIP_ERR_MODULUS;
   if (!rc && !PQ.has_crt) rc = LOLHIP_ERR_NO_CRT;
@@ -315,7 +229,7 @@ int lolhip_khprf_create_lifted(const lolhip_plan* pq, const lolhip_plan* pQ, int
   // exactness over Z: |sum_i L_i digit_i| <= L C_m (q/2) max|digit| and |s A| <= C_m (q/2)^2 below Q/2
   auto sat = [](u128 a, u128 b) -> u128 { const u128 cap = (u128)1 << 100; return a >= cap || b >= cap || a * b >= cap ? cap : a * b; };
   const u128 C = growth(P.pps), h = q / 2;
-  const u128 node = sat(sat(sat((u128)f->ell, C), h), max_digit(q, base, f->dp.k[0]));
+  const u128 node = sat(sat(sat((u128)f->ell, C), h), prf_max_digit(q, base, f->dp.k[0]));
   const u128 key = sat(sat(C, h), h);
   if (2 * std::max(node, key) >= (u128)Q) return LOLHIP_ERR_MODULUS;
   f->lc.Q = Q;

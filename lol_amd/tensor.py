@@ -1367,6 +1367,60 @@ class KHPRF(_Handle):
         return out[0] if single else out
 
 
+class LatticePRF(_WorkHandle):
+    """A family of the key-homomorphic PRF over standard lattices, eq. (2.3) of [BP14] (latticePRF / latticePRFM;
+    lolhip_lprf_create): one modulus q (any 2 <= q < 2^62), gadget `base` (0 = TrivGad), a full binary tree (preorder
+    leaf counts, as for KHPRF) and a0, a1 [n][K] over Z_q, K = n * ell, ell the gadget length of (base, q).  Without a
+    device the family answers workLen only."""
+    _kind = "lprf"
+
+    def __init__(self, q, base, tree, a0, a1):
+        self.q, self.base, self.tree = int(q), int(base), [int(c) for c in tree]
+        a0 = np.ascontiguousarray(np.asarray(a0, dtype=np.int64))
+        a1 = np.ascontiguousarray(np.asarray(a1, dtype=np.int64))
+        if a0.ndim != 2 or a0.shape != a1.shape:
+            raise ValueError("a0 and a1 must be [n][K]")
+        if self.q >= 2 and self.base >= 2:                           # gadlen; anything else is the library's to refuse
+            ell, t = 0, self.q
+            while t:
+                ell, t = ell + 1, t // self.base
+            if a0.shape[1] != a0.shape[0] * ell:
+                raise ValueError(f"a0 and a1 must be [n][K] with K = n * ell = {a0.shape[0] * ell}")
+        elif self.base == 0 and a0.shape[1] != a0.shape[0]:
+            raise ValueError("a0 and a1 must be [n][n] under TrivGad")
+        tr = (C.c_int32 * max(1, len(self.tree)))(*self.tree)
+        self._create("lprf_create", self.q, self.base, int(a0.shape[0]), tr, len(self.tree), a0.ctypes.data_as(_i64p),
+                     a1.ctypes.data_as(_i64p), what=f"lprf_create(q={q}, base={base}, tree={self.tree})")
+        self.n, self.ell = lib().lolhip_lprf_n(self._h), lib().lolhip_lprf_ell(self._h)
+        self.K, self.k = self.n * self.ell, self.tree[0]
+
+    def workLen(self, nkeys, x0, B):
+        """int64 words of scratch of eval (nkeys = 0) or of a call with nkeys keys over [x0, x0 + B)"""
+        return _len(lib().lolhip_lprf_work_len(self._h, int(nkeys), int(x0), int(B)))
+
+    def eval(self, x0, B, stream=None):
+        """A_T(x) for x = x0 .. x0 + B - 1: a CUDA tensor [B][n][K] of residues in [0, q) (lolhip_lprf_eval_batch)"""
+        L = lib()
+        call = lambda st, i, o, w, b: L.lolhip_lprf_eval_batch(self._h, st, int(x0), b, o[0], w)
+        _dry(call)                                                   # before the window check
+        _len(L.lolhip_lprf_work_len(self._h, 0, int(x0), int(B)), "x0 + B > 2^k")
+        return _run(call, stream, (), int(B), lambda: self.workLen(0, x0, B), lambda: (int(B), self.n, self.K), dry=False)
+
+    def __call__(self, s, p, x0, B, stream=None):
+        """latticePRF s x for x = x0 .. x0 + B - 1 (lolhip_lprf_batch): s [n] or [nkeys][n], any int64 (numpy or a CUDA
+        tensor) -> a CUDA tensor [nkeys][B][K] in [0, p) ([B][K] for a single key s [n]); outputs are indexed by x."""
+        L = lib()
+        single = len(s.shape) == 1
+        nkeys = 1 if single else int(s.shape[0])
+        call = lambda st, i, o, w, b: L.lolhip_lprf_batch(self._h, st, i[0], nkeys, int(p), int(x0), b, o[0], w)
+        _dry(call)                                                   # before the window check
+        _len(L.lolhip_lprf_work_len(self._h, nkeys, int(x0), int(B)), "x0 + B > 2^k")
+        s = _stage(s)[1][0]                                          # the result stays a CUDA tensor whatever s is
+        out = _run(call, stream, (s.reshape(nkeys, self.n).contiguous(),), int(B), lambda: self.workLen(nkeys, x0, B),
+                   lambda: (nkeys, int(B), self.K), dry=False)
+        return out[0] if single else out
+
+
 class RLWE:
     """RLWE / RLWR instances over one plan (lol RLWE/{Continuous,Discrete,RLWR}.hs; rlwe-challenges Generate.hs:192-218,
     Verify.hs:346-366): batched sampling against one secret, error terms, their gSqNorm and the validity checks.  Arrays

@@ -9,7 +9,9 @@ verification and gSqNorm (`--rlwe`: that leg alone, also written to profiles/rlw
 product over moduli without a CRT basis (`--ringmul`: that leg alone, also written to profiles/ringmul_pipelines.jsonl)
 and of gadget error correction (`--gadget-correct`: that leg alone, also written to profiles/gadget_correct_pipelines.jsonl)
 and of L / divG over int64 and double slabs (`--eltops`: that leg alone, also written to profiles/eltops_bench.jsonl)
-and of the ciphertext product of any degree (`--ctmul`: that leg alone, also written to profiles/ctmul_bench.jsonl).
+and of the ciphertext product of any degree (`--ctmul`: that leg alone, also written to profiles/ctmul_bench.jsonl)
+and of the key-homomorphic lattice PRF, matrix-core route against VALU route (`--lprf`: that leg alone, also written to
+profiles/lprf_bench.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -860,6 +862,80 @@ def eltops_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def lprf_leg(gen):
+    """The key-homomorphic lattice PRF (lolhip_lprf_batch): the route the host rule picks (the matrix cores from K = 56 on:
+    `route` says which) against the VALU route (debug switch LPRF_VALU) in the same process, alternately, three rounds each (median; min and max beside it).  Shapes: n = 256,
+    q = 12289, base 2 (ell = 14, K = 3584), p = 64, a balanced 10-leaf tree, all of B = 1024 inputs, 1 and 16 keys; the same
+    at n = 64, 16, 8 and 4 (K = 896 ... 56: where the routes cross); the reference's toy shapes (Zq 8 -> Zq 2, n = 3, 5 leaves, three trees;
+    Zq 257 -> Zq 32, n = 3, 10 leaves); a 62-bit modulus (W = 8 limbs) at K = 62 and 248.  macs = the multiply-adds of the node products and of s A_l as the host plans
+    them; the matrix route runs W limb products per multiply-add and is rated against the i8 MFMA peak (2 x the 2.5 PF
+    BF16 peak = 2.5e15 multiply-adds/s), the VALU route against 256 CUs x 64 lanes x 2.4 GHz / 3 (a 64 x 64 -> 64
+    product is at least three 32-bit multiplier instructions).  Also written to profiles/lprf_bench.jsonl."""
+    import statistics
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import khprf_cases as kc
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    lines = []
+    MFMA_PEAK, VALU_PEAK = 2.5e15, 256 * 64 * 2.4e9 / 3
+
+    def macs(tree, n, K, nkeys, B):
+        nodes = kc.parse(tree)
+        tot = sum(kc.view(v, 0, B)[0] * n * K * K for i, v in enumerate(nodes) if i and not v.leaf)
+        return tot + kc.view(nodes[nodes[0].l], 0, B)[0] * nkeys * n * K + B * nkeys * K * K
+
+    def limbs(q):
+        W = 1
+        while q - 1 > 127 * ((256 ** W - 1) // 255):
+            W += 1
+        return W
+
+    shapes = [(12289, 64, 2, n, lol_amd.balanced_tree(10), nk, "balanced10") for n in (256, 64, 16, 8, 4) for nk in (1, 16)]
+    shapes += [(8, 2, 2, 3, t(5), 1, nm) for t, nm in ((lol_amd.left_spine_tree, "left5"), (lol_amd.balanced_tree, "balanced5"),
+                                                      (lol_amd.right_spine_tree, "right5"))]
+    shapes += [(257, 32, 2, 3, lol_amd.balanced_tree(10), 1, "balanced10")]
+    shapes += [(2 ** 62 - 57, 2, 2, n, lol_amd.balanced_tree(10), 1, "balanced10") for n in (1, 4)]      # W = 8, 128-bit VALU sums
+    for q, p, base, n, tree, nkeys, tname in shapes:
+        ell = len(np.base_repr(q, base))
+        K, B = n * ell, 1 << tree[0]
+        a = [torch.randint(0, q, (n, K), dtype=torch.int64, generator=gen, device="cuda").cpu().numpy() for _ in range(2)]
+        f = lol_amd.LatticePRF(q, base, tree, a[0], a[1])
+        s = torch.randint(0, q, (nkeys, n), dtype=torch.int64, device="cuda", generator=gen)
+        out = torch.empty((nkeys, B, K), dtype=torch.int64, device="cuda")
+        work = torch.empty((max(f.workLen(nkeys, 0, B), 1),), dtype=torch.int64, device="cuda")
+        call = lambda: L.lolhip_lprf_batch(f._h, st, s.data_ptr(), nkeys, p, 0, B, out.data_ptr(), work.data_ptr())
+        assert call() == 0
+        it = 3 if n >= 64 else 10
+        m, W = macs(tree, n, K, nkeys, B), limbs(q)
+        mfma = K >= 56                                      # the host rule (every shape here passes the certificate)
+        ts = {"default": [], "valu": []}
+        for _ in range(3):
+            for route in ("default", "valu"):
+                lol_amd.debug_set("LPRF_VALU", route == "valu")
+                try:
+                    ts[route].append(timeit(call, iters=it, warm=1))
+                finally:
+                    lol_amd.debug_set("LPRF_VALU", False)
+        cfg = f"q={q} p={p} base={base} n={n} ell={ell} K={K} tree={tname} B={B} nkeys={nkeys}"
+        for route in ("default", "valu"):
+            ms = statistics.median(ts[route])
+            on_mfma = mfma and route == "default"
+            rate = m * (W if on_mfma else 1) / ms * 1e3
+            d = {"op": f"lprf_prf({route})", "route": "mfma" if on_mfma else "valu", "config": cfg, "ms": round(ms, 4), "ms_min": round(min(ts[route]), 4),
+                 "ms_max": round(max(ts[route]), 4), "items_per_s": round(nkeys * B / ms * 1e3, 1), "macs": m,
+                 "W": W if on_mfma else 0, "mac_per_s": float(f"{rate:.4g}"),
+                 "frac_of_peak": round(rate / (MFMA_PEAK if on_mfma else VALU_PEAK), 5),
+                 "valu_over_default": round(statistics.median(ts["valu"]) / statistics.median(ts["default"]), 3)}
+            lines.append(json.dumps(d))
+            print(lines[-1], flush=True)
+        torch.cuda.synchronize()
+        del f, out, work
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "lprf_bench.jsonl"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def ctmul_leg(gen):
     """The ciphertext product of any degree (lolhip_ct_mul_batch) at the shape of bench.py's c3_ctmul_pow leg (m = 2^15,
     four ~59-bit moduli, B = 256), against entries whose device code is older than it, in one process:
@@ -990,6 +1066,9 @@ def ctmul_leg(gen):
 
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--lprf" in sys.argv:             # the key-homomorphic lattice PRF leg alone
+        lprf_leg(gen)
+        return
     if "--ctmul" in sys.argv:            # the ciphertext product of any degree leg alone
         ctmul_leg(gen)
         return
