@@ -846,6 +846,67 @@ LOLHIP_API int lolhip_ringmul_prepare(const lolhip_ringmul *h, void *stream, int
 LOLHIP_API int lolhip_ringmul_prepared_batch(const lolhip_ringmul *h, void *stream, int64_t *out, const int64_t *a,
                                              const int64_t *bhat, int64_t Bb, int64_t *work, int64_t B);
 
+/* --- RLWE / RLWR instances over moduli without a CRT basis (rlwe_ring_api.cpp, rlwe_ring.hip) -------
+ * The instances of lolhip_rlwe_* above for ANY single modulus 2 <= q < 2^62 (2^k, p^e, 105, 500, 900 ...: most of
+ * rlwe-challenges' parameter list), where those entries answer LOLHIP_ERR_NO_CRT.  a s is the exact ring product of
+ * lolhip_ringmul_* against a prepared secret; the reference computes it through the CRT over C (exact only while
+ * n q^2 < 2^53).  Every call takes the RingMul handle h and pq, THE PLAN h WAS CREATED FROM: one modulus (T = 1), the
+ * index of h's pQ, the q of h.  A q that has a CRT basis is accepted too.
+ * Bases: a [B][n], the secret [n] and the Disc b [B][n] are int64 in the POWERFUL basis, outputs in [0, q); the Cont b
+ *   (double [B][n], in [0, q)) and the RLWR b (int64 [B][n], in [0, p)) are in the decoding basis, as above.
+ * shat [n][K]: lolhip_ringmul_prepare of the secret with Bb = 1.  lolhip_rlwe_ring_secret draws a uniform secret from
+ *   item ctr of domain 7 and writes both s_pow [n] and shat; a caller with its own secret calls lolhip_ringmul_prepare.
+ * Stream: a_pow[b][j] is the uniform residue j of item ctr + b of domain 5, the very words lolhip_rlwe_sample_batch
+ *   writes to a_crt over a one-modulus plan of the same q, read as powerful-basis coefficients.  Gaussians come from
+ *   domain 6 with the bit layout and arithmetic of lolhip_rlwe_sample_batch.  THE CALLER'S DUTY extends unchanged.
+ * Semantics, with x = the decoding-basis residues in [0, q) of a s (the exact product, then lInv over pq):
+ *   Disc sample  b = (a s + l(e)) mod q, e the integers lolhip_rlwe_sample_batch draws for (index, svar, key, ctr + b):
+ *                e does not depend on q, a or s.
+ *   Disc error   e = the lift of lInv(b - a s) mod q, a residue r lifting to r when 2 r < q, else r - q (RingMul's
+ *                convention, the reference's lift); b is any int64 taken mod q.  norm as lolhip_gsqnorm_batch.
+ *   Cont sample / error   exactly the double operations stated above on (x, g) and (x, b); norm as
+ *                lolhip_gsqnorm_f64_batch.
+ *   RLWR rounded product / check   the rounding stated above on x, 2 <= p < q.
+ * Launch plans (la: the lifted a, [B][n][K]):
+ *   way in   sample: k_rr_draw_lift (a_pow and la in one pass); a given: k_ring_lift.
+ *   product  crt on pQ, the pointwise product with shat (period n K), crtInv on pQ.
+ *   way out  k_rr_fold: the fold of k_ring_fold with a tail in registers.  At a 2-power index (L, lInv and the Gaussian
+ *            map are identities) the tail finishes the call: + the rounded Gaussian drawn in the pass (Disc sample),
+ *            b - fold then the lift (Disc error), the RRq add of a Gaussian drawn in the pass (Cont sample), the Cont
+ *            error, the RLWR rounding.  Elsewhere: Disc sample  the sampler of errorRounded -> l on pq -> k_rr_fold
+ *            (+ addend);  Disc error  k_rr_fold (b - fold) -> lInv on pq -> k_rr_centre -> gSqNorm;  Cont and RLWR
+ *            k_ring_fold -> lInv on pq -> the element-wise passes of lolhip_rlwe_*.  The RLWR check always ends in
+ *            lInv and the counting pass.  Debug switch RLWE_RING_UNFUSED forces the second form at a 2-power index; both
+ *            give the same bits.
+ * work: lolhip_rlwe_ring_work_len(h, pq, kind, B) int64 of device scratch, 16-byte aligned:
+ *   even(B n K) + even(B n) + (kind == 2 ? 0 : even(B n)), even(x) = x rounded up to an even count.  It answers on
+ *   host-only handles and serves the sample, error and rounding calls of that kind alike.
+ * Limits: T = 1; for Disc and Cont the sampler's index limits of lolhip_encrypt_batch; n <= 16384 for norm_out; the
+ *   size limits of lolhip_ringmul_prepared_batch.
+ * Status, decided on the host in this order before any launch (outputs are then not written): LOLHIP_ERR_INVALID for a
+ *   NULL h or pq, an unknown kind, B < 0 or beyond RingMul's limits, a pq that is not h's plan (index, T != 1, q), p
+ *   outside [2, q), svar <= 0 or not finite, an index beyond the sampler's limits (Disc and Cont);
+ *   LOLHIP_ERR_NO_DEVICE over host-only plans; LOLHIP_ERR_DEVICE as elsewhere; LOLHIP_ERR_INVALID for NULL pointers at
+ *   B > 0 (e_out or norm_out may be NULL, not both; norm_out needs n <= 16384).  B = 0 returns LOLHIP_OK.  No call
+ *   allocates or synchronises beyond what crt on pQ does; output does not depend on how a batch is split.
+ * With the environment variable LOLHIP_RLWE_RING_INFO set (read at every call) each call that launches prints one line
+ *   to stderr: "rlwe_ring: <entry> kind <kind>, route <fused|unfused>, K <K>, n <n>, B <B>". */
+LOLHIP_API int64_t lolhip_rlwe_ring_work_len(const lolhip_ringmul *h, const lolhip_plan *pq, int kind, int64_t B);
+LOLHIP_API int lolhip_rlwe_ring_secret(const lolhip_ringmul *h, const lolhip_plan *pq, void *stream, const uint8_t key[32],
+                                       uint64_t ctr, int64_t *s_pow, int64_t *shat);
+LOLHIP_API int lolhip_rlwe_ring_sample_batch(const lolhip_ringmul *h, const lolhip_plan *pq, void *stream, int kind, int64_t p,
+                                             const int64_t *shat, double svar, const uint8_t key[32], uint64_t ctr,
+                                             int64_t *a_pow, void *b_out, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwe_ring_error_batch(const lolhip_ringmul *h, const lolhip_plan *pq, void *stream, int kind,
+                                            const int64_t *a_pow, const void *b, const int64_t *shat, void *e_out,
+                                            void *norm_out, int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwr_ring_rounded_prod_batch(const lolhip_ringmul *h, const lolhip_plan *pq, int64_t p, void *stream,
+                                                   const int64_t *a_pow, const int64_t *shat, int64_t *b_out,
+                                                   int64_t *work, int64_t B);
+LOLHIP_API int lolhip_rlwr_ring_check_batch(const lolhip_ringmul *h, const lolhip_plan *pq, int64_t p, void *stream,
+                                            const int64_t *a_pow, const int64_t *b, const int64_t *shat, int32_t *mismatch,
+                                            int64_t *work, int64_t B);
+
 /* --- gadget error correction (gadget_api.cpp, gadget.hip) ----------------------------------------------------------
  * Correct gad (Cyc t m zq) (Cyc.hs:615-621 over Gadget.hs:84-134 and ZqBasic.hs:234-314), the inverse direction of
  * lolhip_gadget / lolhip_decompose_batch: from L = lolhip_decompose_len(p, base) noisy multiples xs_j = g_j s + e_j of
@@ -1012,7 +1073,7 @@ LOLHIP_API int64_t lolhip_chain_write(const uint8_t *const *elems, const int64_t
 LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_t bytes, int variant);
 
 /* Test and A/B aid, not part of the drop-in surface: force a launch path.  `name` is one of
- * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL and LPRF_VALU (each is
+ * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL, LPRF_VALU and RLWE_RING_UNFUSED (each is
  * also read ONCE at first use from the environment variable LOLHIP_<name>); value 0 restores the
  * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID.
  * Two environment variables are test hooks of the persistent pipelined poly-mul, read at EVERY launch of it:

@@ -10,7 +10,7 @@ calls raise.
 """
 from .tensor import (  # noqa: F401
     LolHipError, NoDeviceError, Plan, Ext, TunnelChain, PTRound, PTTunnel, RingMul, crtSetDec, crtSet, lib, lib_path, device_count, debug_set, good_q, factor_pps,
-    chacha20_block, mulC, KHPRF, LatticePRF, RLWE, balanced_tree, left_spine_tree, right_spine_tree, gray_code,
+    chacha20_block, mulC, KHPRF, LatticePRF, RLWE, RingRLWE, balanced_tree, left_spine_tree, right_spine_tree, gray_code,
 )
 from .wire import (  # noqa: F401
     rqproduct_read, rqproduct_write, kshint_read, kshint_write, r_read, secretkey_read, kqproduct_read,
@@ -20,5 +20,5 @@ from .wire import (  # noqa: F401
 __all__ = ["LolHipError", "NoDeviceError", "Plan", "Ext", "TunnelChain", "PTRound", "PTTunnel", "RingMul", "crtSetDec", "crtSet", "lib", "lib_path", "device_count", "debug_set",
            "good_q", "factor_pps", "rqproduct_read", "rqproduct_write", "kshint_read", "kshint_write", "r_read",
            "secretkey_read", "kqproduct_read", "linearrq_read", "tunnelhint_read", "r_write", "secretkey_write",
-           "linearrq_write", "tunnelhint_write", "chain_read", "chain_write", "chacha20_block", "mulC", "KHPRF", "LatticePRF", "RLWE", "balanced_tree", "left_spine_tree",
+           "linearrq_write", "tunnelhint_write", "chain_read", "chain_write", "chacha20_block", "mulC", "KHPRF", "LatticePRF", "RLWE", "RingRLWE", "balanced_tree", "left_spine_tree",
            "right_spine_tree", "gray_code"]

@@ -149,6 +149,13 @@ ABI = _rows(
     ("rlwr_rounded_prod_batch", ci, vp, i64, vp, vp, vp, vp, vp, i64),
     ("rlwr_check_batch", ci, vp, i64, vp, vp, vp, vp, vp, vp, i64),
     ("rlwe_error_bound", ci, pp, ci, f64, f64, ci, f64p),
+    # RLWE / RLWR over moduli without a CRT basis
+    ("rlwe_ring_work_len", i64, vp, vp, ci, i64),
+    ("rlwe_ring_secret", ci, vp, vp, vp, cstr, u64, vp, vp),
+    ("rlwe_ring_sample_batch", ci, vp, vp, vp, ci, i64, vp, f64, cstr, u64, vp, vp, vp, i64),
+    ("rlwe_ring_error_batch", ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, i64),
+    ("rlwr_ring_rounded_prod_batch", ci, vp, vp, i64, vp, vp, vp, vp, vp, i64),
+    ("rlwr_ring_check_batch", ci, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64),
     # serialisation (lol_amd/wire.py)
     ("rqproduct_read", i64, _u8p, i64, u32p, _i64p, ci, cip, _i64p, i64),
     ("rqproduct_write", i64, u32, _i64p, ci, _i64p, i64, _u8p, i64),

@@ -16,6 +16,7 @@
 
 #include "elementwise_dev.h"
 #include "pipeline.h"
+#include "rlwe_dev.h"
 #include "rng_dev.h"
 
 namespace lolhip {
@@ -31,32 +32,6 @@ bool grid_for(i64 nblk, i64 B, dim3* grid) {
   return true;
 }
 
-// the block of item b: nonce (domain, lo32(ctr + b), hi32(ctr + b)), block counter k
-__device__ __forceinline__ void stream_block(const ChaChaKey& key, u64 ctr, int domain, i64 b, u32 k, u32 w[16]) {
-  const u64 nb = ctr + (u64)b;
-  chacha20_block(key, k, (u32)domain, (u32)nb, (u32)(nb >> 32), w);
-}
-
-// basic Box-Muller on words w[0..3]: u1 = ((a >> 11) + 1) 2^-53 in (0, 1], u2 = (c >> 11) 2^-53
-__device__ __forceinline__ void box_muller(const u32* w, double sigma, double* g0, double* g1) {
-  const u64 a = (u64)w[0] | (u64)w[1] << 32, c = (u64)w[2] | (u64)w[3] << 32;
-  const double u1 = (double)((a >> 11) + 1) * 0x1p-53;
-  const double u2 = (double)(c >> 11) * 0x1p-53;
-  const double r = sigma * sqrt(-2.0 * log(u1));
-  double sn, cs;
-  sincos(6.283185307179586 * u2, &sn, &cs);
-  *g0 = r * cs;
-  *g1 = r * sn;
-}
-
-// the 8 Gaussians of block k (coefficients 8k .. 8k+7)
-__device__ __forceinline__ void gauss8(const ChaChaKey& key, u64 ctr, int domain, i64 b, u32 k, double sigma,
-                                       double g[8]) {
-  u32 w[16];
-  stream_block(key, ctr, domain, b, k, w);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) box_muller(w + 4 * i, sigma, &g[2 * i], &g[2 * i + 1]);
-}
 }  // namespace
 
 // ---------------------------------------------------------------------------------------

@@ -32,3 +32,11 @@ hipError_t launch_ring_lift(hipStream_t s, const i64* in, i64* out, i64 rows, i6
 hipError_t launch_ring_fold(hipStream_t s, const i64* in, i64* out, i64 rows, i64 n, const RingMul& c);
 
 }  // namespace lolhip
+
+// the handle behind include/lolhip.h's lolhip_ringmul (ringmul_api.cpp makes it; rlwe_ring_api.cpp reads it)
+struct lolhip_plan;
+struct lolhip_ringmul {
+  const lolhip_plan* pQ = nullptr;   // the transforms run on it; pq's moduli live on in rm
+  lolhip::RingMul rm{};
+  bool device = false;
+};

@@ -16,64 +16,14 @@
 
 #include "elementwise_dev.h"
 #include "ringmul.h"
+#include "ringmul_dev.h"
 
 namespace lolhip {
 
 namespace {
-constexpr int TPB = 256;
-constexpr i64 MAX_BLOCKS = 1 << 16;      // grid-stride above, in both grid dimensions
-
-// W coefficients per thread: `per` threads cover a row, grid.x strides over them, grid.y over the rows
-struct Shape { dim3 grid, block; };
-Shape shape_for(i64 rows, i64 per) {
-  unsigned threads = 64;
-  while (threads < (unsigned)TPB && (i64)threads < per) threads <<= 1;
-  i64 gx = (per + threads - 1) / threads;
-  gx = gx < 1 ? 1 : (gx < MAX_BLOCKS ? gx : MAX_BLOCKS);
-  i64 gy = MAX_BLOCKS / gx;
-  gy = gy < 1 ? 1 : (gy < rows ? gy : rows);
-  if (gy > 65535) gy = 65535;
-  return Shape{dim3((unsigned)gx, (unsigned)gy), dim3(threads)};
-}
-
-template <int K, bool POW2>
-__device__ __forceinline__ void lift_word(i64 x, const ModCtx& mc, const RingMul& c, u64* y) {
-  const u64 r = POW2 ? (u64)x & (mc.q - 1) : mod_any(x, mc);
-  const i64 v = centred(r, mc.q);
-#pragma unroll
-  for (int k = 0; k < K; ++k) y[k] = c.wide ? mod_any(v, c.Q[k]) : canon_in(v, c.Q[k].q);
-}
-
-template <int K, bool POW2>
-__device__ __forceinline__ u64 fold_word(const u64* xs, const ModCtx& mc, int t, const RingMul& c) {
-  u64 x[K], v[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = canon_in((i64)xs[k], c.Q[k].q);
-  garner_digits<K>(v, [&](int k) { return x[k]; }, c.Q, c.pinv, c.qmod, RING_MAX_K);
-  const bool neg = above_half<K>(v, c.half);
-  if constexpr (POW2) {
-    u64 acc = v[0];                            // mod 2^64, of which q_t is a divisor
-#pragma unroll
-    for (int k = 1; k < K; ++k) acc += v[k] * c.pw[t][k];
-    if (neg) acc -= c.Qp[t];
-    return acc & (mc.q - 1);
-  } else {
-    u64 r;
-    if constexpr (K == 1) {
-      r = rem128(0, v[0], mc);
-    } else {
-      unsigned __int128 acc = v[0];            // K terms below 2^124 each
-#pragma unroll
-      for (int k = 1; k < K; ++k) acc += (unsigned __int128)v[k] * c.pw[t][k];
-      r = reduce128((u64)(acc >> 64), (u64)acc, mc);
-    }
-    return neg ? submod(r, c.Qp[t], mc.q) : r;
-  }
-}
-
 // V2: every slab is 16-byte aligned and n is even; two coefficients per thread
 template <int K, bool POW2, bool V2>
-__global__ void __launch_bounds__(TPB)
+__global__ void __launch_bounds__(RING_TPB)
 k_ring_lift(const i64* __restrict__ in, i64* __restrict__ out, i64 rows, i64 n, RingMul c) {
   constexpr int W = V2 ? 2 : 1;
   const int T = c.T;
@@ -110,7 +60,7 @@ k_ring_lift(const i64* __restrict__ in, i64* __restrict__ out, i64 rows, i64 n, 
 }
 
 template <int K, bool POW2, bool V2>
-__global__ void __launch_bounds__(TPB)
+__global__ void __launch_bounds__(RING_TPB)
 k_ring_fold(const i64* __restrict__ in, i64* __restrict__ out, i64 rows, i64 n, RingMul c) {
   constexpr int W = V2 ? 2 : 1;
   const int T = c.T;
@@ -157,7 +107,7 @@ bool params_ok(const i64* in, const i64* out, i64 rows, i64 n, const RingMul& c)
 #define LOLHIP_RING_LAUNCH(KERNEL)                                                                                  \
   do {                                                                                                              \
     const bool v2 = aligned16(in, out) && n % 2 == 0;                                                               \
-    const Shape sh = shape_for(rows, v2 ? n / 2 : n);                                                               \
+    const RingShape sh = ring_shape_for(rows, v2 ? n / 2 : n);                                                      \
     const bool p2 = c.pow2 != 0;                                                                                    \
     switch (c.K * 4 + (p2 ? 2 : 0) + (v2 ? 1 : 0)) {                                                                \
       case 4:  hipLaunchKernelGGL((KERNEL<1, false, false>), sh.grid, sh.block, 0, s, in, out, rows, n, c); break;  \

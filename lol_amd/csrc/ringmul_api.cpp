@@ -13,12 +13,6 @@
 
 using namespace lolhip;
 
-struct lolhip_ringmul {
-  const lolhip_plan* pQ = nullptr;   // the transforms run on it; pq's moduli live on in rm
-  RingMul rm{};
-  bool device = false;
-};
-
 namespace {
 
 // Unsigned integers below 2^256 for the exactness bound: 2 C H^2 reaches 2^185 and a product of three primes 2^183.

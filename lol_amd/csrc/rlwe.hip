@@ -16,6 +16,7 @@
 
 #include "elementwise_dev.h"
 #include "rlwe.h"
+#include "rlwe_dev.h"
 #include "rng_dev.h"
 
 // b = f(x, g) and e = f(x, b) are pure functions of their IEEE double operations in the stated order (include/lolhip.h)
@@ -167,13 +168,6 @@ hipError_t launch_gsqnorm(hipStream_t st, const V* e, V* out, i64 B, i64 n, cons
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------
-// the samplers' stream (rng_dev.h): the block of item b, nonce (domain, lo32(ctr + b), hi32(ctr + b)), block counter k
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void stream_block(const ChaChaKey& key, u64 ctr, int domain, i64 b, u32 k, u32 w[16]) {
-  const u64 nb = ctr + (u64)b;
-  chacha20_block(key, k, (u32)domain, (u32)nb, (u32)(nb >> 32), w);
-}
 }  // namespace
 
 hipError_t launch_gsqnorm_i64(hipStream_t s, const i64* e, i64* out, i64 B, i64 n, const NormDims& nd) {
@@ -267,16 +261,6 @@ hipError_t launch_rlwe_as(hipStream_t s, const i64* a, const i64* b, const i64* 
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------
-// RRq (RRq.hs:47-84): reduce' x = x - q floor(x / q); x + y with one conditional subtraction; lift y = y + y < q ? y :
-// y - q.  xd = (double) x is exact below 2^53 and one rounding above.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double rrq_reduce(double x, double q) { return x - q * floor(x / q); }
-__device__ __forceinline__ double rrq_add(double x, double y, double q) {
-  const double z = x + y;
-  return z >= q ? z - q : z;
-}
-
 template <bool ERR>
 __global__ void __launch_bounds__(256)
 k_rlwe_cont(const i64* __restrict__ x, const double* __restrict__ in, double* __restrict__ out, i64 total, double q) {
@@ -305,30 +289,6 @@ hipError_t launch_rlwe_cont_error(hipStream_t s, const i64* x, const double* b, 
   if (!tiles_for(total, 256, &blocks)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_rlwe_cont<true>, dim3(blocks), dim3(256), 0, s, x, b, e, total, q);
   return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// RLWR: l = the centred lift of x (decode', ZqBasic.hs:92-94), r = floor((p l + floor(q/2)) / q) mod p (roundedProd:
-// rescaleMod, Prelude.hs:144-153 over divModCent, Numeric.hs:227-234), exact: the 64-bit division where p |l| + q/2
-// fits it, else the 128-bit one.  x in [0, q), 2 <= p < q < 2^62.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ i64 rlwr_round(u64 x, u64 q, u64 p) {
-  const bool neg = 2 * x >= q;
-  const u64 al = neg ? q - x : x;                              // |l| <= q/2
-  const u64 h = q >> 1;
-  const u128 pl = (u128)p * al;
-  i64 quo;                                                     // floor((+-pl + h) / q), |quo| <= p/2 + 1
-  if (!neg) {
-    const u128 num = pl + h;
-    quo = (num >> 64) == 0 ? (i64)((u64)num / q) : (i64)(u64)(num / q);
-  } else if (pl <= h) {
-    quo = 0;                                                   // 0 <= h - pl < q
-  } else {
-    const u128 num = pl - h + (q - 1);                         // -ceil((pl - h) / q)
-    quo = (num >> 64) == 0 ? -(i64)((u64)num / q) : -(i64)(u64)(num / q);
-  }
-  i64 r = quo % (i64)p;
-  return r < 0 ? r + (i64)p : r;
 }
 
 __global__ void __launch_bounds__(256)

@@ -1561,3 +1561,122 @@ class RLWE:
         out = C.c_double()
         _check(lib().lolhip_rlwe_error_bound(arr, npp, float(svar), float(eps), k, C.byref(out)))
         return int(out.value) if k == 0 else out.value
+
+
+class RingRLWE:
+    """RLWE / RLWR instances over ONE modulus without a CRT basis (lolhip_rlwe_ring_*): q = 2^k, p^e, 105, 500 ..., most
+    of rlwe-challenges' parameter list, where RLWE raises "no CRT basis".  a s is the exact ring product of RingMul
+    against a prepared secret.  plan_q: a one-modulus Plan; ring: the RingMul made from it (None: RingMul(plan_q)).  The
+    class mirrors RLWE with other bases: a [B][n], the secret [n] and Disc b [B][n] are in the POWERFUL basis; Cont b
+    float64 [B][n] and RLWR b int64 [B][n] stay in the decoding basis.  Every call takes the prepared secret shat [n][K]
+    (secret() returns it beside s_pow; prepare() makes it from a secret of the caller's).  Streams as for RLWE: never
+    reuse (key, ctr + b); advance ctr by B between calls."""
+
+    DISC, CONT, RLWR = RLWE.DISC, RLWE.CONT, RLWE.RLWR
+    errorBound = staticmethod(RLWE.errorBound)
+
+    def __init__(self, plan_q: Plan, ring=None):
+        self.plan = plan_q
+        self.ring = RingMul(plan_q) if ring is None else ring
+        self.K = self.ring.K
+
+    # ---- helpers ----------------------------------------------------------------------------------------------------
+    def _hp(self):
+        return self.ring._h, self.plan._h
+
+    def _batch(self, a):
+        return _count(a, self.plan.n, f"a is not a whole number of [n={self.plan.n}] polynomials")
+
+    def _work_len(self, kind, B):
+        return lambda: lib().lolhip_rlwe_ring_work_len(*self._hp(), kind, int(B))
+
+    def gSqNorm(self, e, stream=None):
+        """gSqNormDec of decoding-basis coefficients [B][n] -> [B] (RLWE.gSqNorm: the plan supplies the index only)"""
+        return RLWE(self.plan).gSqNorm(e, stream)
+
+    # ---- the secret ---------------------------------------------------------------------------------------------------
+    def secret(self, key=None, ctr=0, stream=None):
+        """(s_pow [n], shat [n][K]): a uniform secret in the powerful basis, item ctr of domain 7, and its prepared form"""
+        L, P, kb, (h, pq) = lib(), self.plan, _key(key), self._hp()
+        call = lambda st, i, o, w, b: L.lolhip_rlwe_ring_secret(h, pq, st, kb, int(ctr), o[0], o[1])
+        _dry(call, tolerate=(ERR_INVALID,))                          # no batch: the null outputs answer INVALID last
+        return tuple(_run(call, stream, (), 0, None, lambda: [((P.n,), "int64"), ((P.n, self.K), "int64")], dry=False))
+
+    def prepare(self, s_pow, stream=None):
+        """shat [n][K] of a secret [n] in the powerful basis, any int64 taken mod q (RingMul.prepare)"""
+        out = self.ring.prepare(s_pow, stream=stream)
+        return out.reshape(self.plan.n, self.K)
+
+    # ---- samplers: CUDA tensors out whatever the secret is given as ---------------------------------------------------
+    def _sample(self, kind, shat, B, svar, p, key, ctr, stream):
+        L, P, kb, B, (h, pq) = lib(), self.plan, _key(key), int(B), self._hp()
+        call = lambda st, i, o, w, nb: L.lolhip_rlwe_ring_sample_batch(h, pq, st, kind, int(p), i[0], float(svar), kb,
+                                                                       int(ctr), o[0], o[1], w, nb)
+        return tuple(_run(call, stream, (shat,), B, self._work_len(kind, B),
+                          lambda: [((B, P.n), "int64"), ((B, P.n), "float64" if kind == self.CONT else "int64")],
+                          unstage=False, min_work=2))
+
+    def sampleDisc(self, shat, B, svar, key=None, ctr=0, stream=None):
+        """B discrete samples (a, b = a s + l (errorRounded svar) mod q), both [B][n], powerful basis"""
+        return self._sample(self.DISC, shat, B, svar, 0, key, ctr, stream)
+
+    def sampleCont(self, shat, B, svar, key=None, ctr=0, stream=None):
+        """B continuous samples: a [B][n] powerful basis, b float64 [B][n] in [0, q), decoding basis"""
+        return self._sample(self.CONT, shat, B, svar, 0, key, ctr, stream)
+
+    def sampleRLWR(self, shat, B, p, key=None, ctr=0, stream=None):
+        """B RLWR samples: a [B][n] powerful basis, b = roundedProd s a [B][n] in [0, p), decoding basis"""
+        return self._sample(self.RLWR, shat, B, 1.0, p, key, ctr, stream)
+
+    # ---- error terms and norms ----------------------------------------------------------------------------------------
+    def _error(self, kind, shat, a, b, want_e, want_norm, stream):
+        L, P, (h, pq) = lib(), self.plan, self._hp()
+        call = lambda st, i, o, w, nb: L.lolhip_rlwe_ring_error_batch(h, pq, st, kind, i[0], i[1], i[2], o[0], o[1], w, nb)
+        _dry(call)                                                   # before the shape checks
+        dt = "float64" if kind == self.CONT else "int64"
+        B = self._batch(a)
+        if _size(b) != B * P.n:
+            raise ValueError("a and b are not the same number of samples")
+        out = _run(call, stream, (a, (b, dt), shat), B, self._work_len(kind, B),
+                   lambda: [((B, P.n), dt) if want_e else None, ((B,), dt) if want_norm else None], dry=False, min_work=2)
+        out = tuple(t for t in out if t is not None)
+        return out if len(out) > 1 else out[0]
+
+    def errorTermDisc(self, shat, a, b, norm=False, stream=None):
+        """the centred lift of lInv (b - a s): int64 [B][n], decoding basis; norm=True: (e, norm)"""
+        return self._error(self.DISC, shat, a, b, True, norm, stream)
+
+    def errorTermCont(self, shat, a, b, norm=False, stream=None):
+        """lift (b - a s) in K/(qR): float64 [B][n]; norm=True: (e, norm)"""
+        return self._error(self.CONT, shat, a, b, True, norm, stream)
+
+    def errorGSqNormDisc(self, shat, a, b, stream=None):
+        """gSqNorm . errorTerm: int64 [B], saturated; the error slab is not returned"""
+        return self._error(self.DISC, shat, a, b, False, True, stream)
+
+    def errorGSqNormCont(self, shat, a, b, stream=None):
+        """gSqNorm . errorTerm: float64 [B]"""
+        return self._error(self.CONT, shat, a, b, False, True, stream)
+
+    # ---- RLWR ---------------------------------------------------------------------------------------------------------
+    def roundedProd(self, shat, a, p, stream=None):
+        """roundedProd s a: [B][n] in [0, p), decoding basis"""
+        L, P, (h, pq) = lib(), self.plan, self._hp()
+        call = lambda st, i, o, w, b: L.lolhip_rlwr_ring_rounded_prod_batch(h, pq, int(p), st, i[0], i[1], o[0], w, b)
+        _dry(call)                                                   # before the shape check
+        B = self._batch(a)
+        return _run(call, stream, (a, shat), B, self._work_len(self.RLWR, B), lambda: (B, P.n), dry=False, min_work=2)
+
+    def mismatchRLWR(self, shat, a, b, p, stream=None):
+        """per sample, the coefficients where b differs from roundedProd s a: int32 [B]"""
+        L, P, (h, pq) = lib(), self.plan, self._hp()
+        call = lambda st, i, o, w, nb: L.lolhip_rlwr_ring_check_batch(h, pq, int(p), st, i[0], i[1], i[2], o[0], w, nb)
+        _dry(call)                                                   # before the shape checks
+        B = self._batch(a)
+        if _size(b) != B * P.n:
+            raise ValueError("a and b are not the same number of samples")
+        return _run(call, stream, (a, b, shat), B, self._work_len(self.RLWR, B), lambda: [((B,), "int32")], dry=False,
+                    min_work=2)[0]
+
+    # ---- instance verification: RLWE's comparisons over this class's norms ----------------------------------------------
+    validDisc, validCont, validRLWR = RLWE.validDisc, RLWE.validCont, RLWE.validRLWR

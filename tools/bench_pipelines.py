@@ -11,7 +11,8 @@ and of gadget error correction (`--gadget-correct`: that leg alone, also written
 and of L / divG over int64 and double slabs (`--eltops`: that leg alone, also written to profiles/eltops_bench.jsonl)
 and of the ciphertext product of any degree (`--ctmul`: that leg alone, also written to profiles/ctmul_bench.jsonl)
 and of the key-homomorphic lattice PRF, matrix-core route against VALU route (`--lprf`: that leg alone, also written to
-profiles/lprf_bench.jsonl).
+profiles/lprf_bench.jsonl) and of RLWE / RLWR instances over moduli without a CRT basis, fused tails against the general
+composition (`--rlwe-ring`: that leg alone, also written to profiles/rlwe_ring_bench.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -736,6 +737,80 @@ def ringmul_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def rlwe_ring_leg(gen):
+    """RLWE / RLWR instances over moduli without a CRT basis (lolhip_rlwe_ring_*) at (m, q) = (256, 512), (512, 2^17),
+    (1155, 2^18) and (2^14, 2^17), one slab of a of at least 1 GiB: RLWR sample, Disc sample and Disc error + norm, on the
+    route the library picks and, at the 2-power indices, on the general composition (debug switch RLWE_RING_UNFUSED),
+    beside lolhip_ringmul_prepared_batch (Bb = 1) on the same (m, q, B) and lolhip_copy_slab on a slab of a's size, all in
+    the same process.  yard_ms = the prepared product's time + `extra_words` slab words (read or written beyond the
+    prepared product's own traffic, counted from the launch plan) at the copy's measured rate; over_yard = ms / yard_ms.
+    Median of five rounds of ten calls.  Also written to profiles/rlwe_ring_bench.jsonl."""
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    lines = []
+    rounds = lambda fn: [timeit(fn) for _ in range(5)]
+
+    def rep(name, cfg, ts, items, **more):
+        ms = statistics.median(ts)
+        d = {"op": name, "config": cfg, "ms": round(ms, 4), "ms_min": round(min(ts), 4), "ms_max": round(max(ts), 4),
+             "items_per_s": round(items / ms * 1e3, 1)}
+        d.update(more)
+        lines.append(json.dumps(d))
+        print(lines[-1], flush=True)
+        return ms
+
+    # slab words moved beyond lolhip_ringmul_prepared_batch's own (lift: 1 + K, the transforms and the product: 6 K,
+    # fold: K + 1), by the launch plans of include/lolhip.h: (fused, general at a 2-power, general elsewhere)
+    EXTRA = {"rlwr_sample": (0, 2, 4), "disc_sample": (0, 2, 8), "disc_error_norm": (2, 4, 6)}
+    key, svar = bytes(range(32)), 7.8125e-3
+    for m, q in ((256, 512), (512, 2 ** 17), (1155, 2 ** 18), (2 ** 14, 2 ** 17)):
+        P = lol_amd.Plan.for_index(m, [q])
+        r = lol_amd.RingRLWE(P)
+        n, K, h = P.n, r.K, r.ring._h
+        two_power = m & (m - 1) == 0
+        B = -(-2 ** 30 // (n * 8))
+        words, slab = B * n, B * n * 8
+        cfg = f"m={m} n={n} q={q} K={K} B={B} ({slab >> 20} MiB)"
+        _, shat = r.secret(key=key, ctr=0)
+        a, b = (torch.empty((B, n), dtype=torch.int64, device="cuda") for _ in range(2))
+        e = torch.empty((B, n), dtype=torch.int64, device="cuda")
+        nm = torch.empty((B,), dtype=torch.int64, device="cuda")
+        work = torch.empty((max(L.lolhip_rlwe_ring_work_len(h, P._h, 0, B), r.ring.workLen(B)),), dtype=torch.int64, device="cuda")
+        t_copy = rep("  copy_slab", cfg, rounds(lambda: L.lolhip_copy_slab(st, ptr(e), ptr(b), slab, 0)), B,
+                     note="lolhip_copy_slab, the HBM yardstick: one slab word read and one written")
+        word_ms = t_copy / (2 * words)
+        assert L.lolhip_rlwe_ring_sample_batch(h, P._h, st, 0, 0, ptr(shat), svar, key, 0, ptr(a), ptr(b), ptr(work), B) == 0
+        t_prep = rep("  ringmul_prepared", cfg + " Bb=1",
+                     rounds(lambda: L.lolhip_ringmul_prepared_batch(h, st, ptr(e), ptr(a), ptr(shat), 1, ptr(work), B)), B,
+                     note="lift, crt, pointwise product, crtInv, fold")
+        calls = {
+            "rlwr_sample": lambda: L.lolhip_rlwe_ring_sample_batch(h, P._h, st, 2, 2, ptr(shat), 1.0, key, 0, ptr(a), ptr(b), ptr(work), B),
+            "disc_sample": lambda: L.lolhip_rlwe_ring_sample_batch(h, P._h, st, 0, 0, ptr(shat), svar, key, 0, ptr(a), ptr(b), ptr(work), B),
+            "disc_error_norm": lambda: L.lolhip_rlwe_ring_error_batch(h, P._h, st, 0, ptr(a), ptr(b), ptr(shat), ptr(e), ptr(nm), ptr(work), B),
+        }
+        for unfused in ((False, True) if two_power else (True,)):
+            lol_amd.debug_set("RLWE_RING_UNFUSED", unfused)
+            try:
+                for name in ("rlwr_sample", "disc_sample", "disc_error_norm"):    # the Disc sample leaves (a, b) for the error call
+                    extra = EXTRA[name][0 if not unfused else 1 if two_power else 2]
+                    assert calls[name]() == 0
+                    ts = rounds(calls[name])
+                    yard = t_prep + extra * words * word_ms
+                    rep(f"rlwe_ring_{name}" + ("(unfused)" if unfused and two_power else ""), cfg, ts, B,
+                        route="unfused" if unfused else "fused", extra_words=extra, yard_ms=round(yard, 4),
+                        over_yard=round(statistics.median(ts) / yard, 4))
+            finally:
+                lol_amd.debug_set("RLWE_RING_UNFUSED", False)
+        torch.cuda.synchronize()
+        del a, b, e, nm, work, shat, r, P
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "rlwe_ring_bench.jsonl"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def gadget_correct_leg(gen):
     """Gadget error correction (lolhip_gadget_correct_batch, decoding basis) at config 5's shape (m = 2048, q = (1017857,
     1032193), B = 8192) with base 256 and over one 61-bit modulus (q = 2^60 + 147457, m = 2^14, B = 64) with base 2: with
@@ -1071,6 +1146,9 @@ def main():
         return
     if "--ctmul" in sys.argv:            # the ciphertext product of any degree leg alone
         ctmul_leg(gen)
+        return
+    if "--rlwe-ring" in sys.argv:        # the RLWE / RLWR instances over moduli without a CRT basis leg alone
+        rlwe_ring_leg(gen)
         return
     if "--eltops" in sys.argv:           # the L / divG over Z and R leg alone
         eltops_leg(gen)
