@@ -907,6 +907,110 @@ LOLHIP_API int lolhip_rlwr_ring_check_batch(const lolhip_ringmul *h, const lolhi
                                             const int64_t *a_pow, const int64_t *b, const int64_t *shat, int32_t *mismatch,
                                             int64_t *work, int64_t B);
 
+/* --- whole RLWE / RLWR challenges (challenge_api.cpp, challenge.hip; rlwe-challenges Generate.hs:105-218,
+ * Verify.hs:236-366), device pointers -----------------------------------------------------------------
+ * A challenge is I instances of L samples, each instance under a secret of its own.  One call generates all of it and
+ * one call verifies all of it; item b = i L + l (sample l of instance i) uses secret i = b / L.  kind, p, svar and the
+ * arithmetic of every sample are those of lolhip_rlwe_* above.  These entries serve moduli WITH a CRT basis.
+ * Bases: every array is in the DECODING basis, the basis of the wire format (Cyc.hs toProto): s [I][n][T],
+ *   a [I L][n][T], residues in [0, q_t); b int64 [I L][n][T] residues (Disc), double [I L][n] in [0, q) (Cont), int64
+ *   [I L][n] in [0, p) (RLWR).
+ * lolhip_chall_generate_batch.  THE STREAM CONTRACT: secret i is what lolhip_rlwe_secret gives at counter ctr_s + i;
+ *   sample (i, l) is what lolhip_rlwe_sample_batch gives for that secret at counter ctr + i L + l; s, a and the Disc b
+ *   are then taken to the decoding basis with crtInv and lInv.  THE CALLER'S DUTY extends: a call uses the items
+ *   ctr_s .. ctr_s + I - 1 of domain 7 and ctr .. ctr + I L - 1 of domains 5 and 6.
+ *   Launch plan: the I secrets in one launch -> the plan of lolhip_rlwe_sample_batch over I L items, the pass with the
+ *   secret (k_chall_uniform) reading row b / L -> crtInv, lInv of the outputs.
+ * lolhip_chall_verify_batch.  Per instance i, over its L samples under s_dec[i]:
+ *     Disc  fails[i] = #{l : not (bound_disc > norm)}, worst[i] = the largest norm, int64; norm as
+ *           lolhip_rlwe_error_batch gives it, so a saturated norm (INT64_MAX) fails under every bound
+ *     Cont  the same with bound_cont in doubles, worst double; a NaN norm fails and makes worst[i] NaN
+ *     RLWR  fails[i] = #{l : a coefficient of sample l mismatches}, worst[i] = the largest per-sample mismatch count of
+ *           lolhip_rlwr_check_batch, int64
+ *   The comparison is strict (Verify.hs:350-356).  fails int32 [I]; an instance is valid when fails[i] = 0.  Only the
+ *   bound of the kind is read.  Inputs are any int64 (taken mod q_t) and are not written.
+ *   Launch plan: l, crt of s, a (and the Disc b) into work -> k_chall_as (a s_i, or b - a s_i) -> crtInv, lInv -> the
+ *   error and norm passes of lolhip_rlwe_error_batch, or the counting pass of lolhip_rlwr_check_batch ->
+ *   k_chall_verdict, one wave per instance, no atomics.
+ * work: lolhip_chall_work_len(pq, kind, I, L) int64 of device scratch (any 8-byte alignment), with B = I L and even(x) = x
+ *   rounded up to an even count:  even(I n T) + even(B n T) + (kind == 0 ? even(B n T) : 0) + (kind == 2 ? 0 :
+ *   even(B n)) + even(B).  It answers on host-only plans and serves both calls.
+ * Limits: I >= 0, L >= 1, I L <= 2^31 - 1; T <= 16, T = 1 for Cont and RLWR; 2 <= p < q; generate: the sampler's index
+ *   limits for Disc and Cont; verify: n <= 16384 for Disc and Cont.
+ * Status, decided on the host in this order before any launch (outputs are then not written): LOLHIP_ERR_INVALID for a
+ *   NULL pq, an unknown kind, I < 0, L < 1, I L too large, T beyond the limits, p outside [2, q), svar <= 0 or not
+ *   finite, an index beyond the limits; LOLHIP_ERR_NO_CRT when pq has no CRT basis; LOLHIP_ERR_MODULUS for a Disc
+ *   verification over moduli that are not pairwise coprime; LOLHIP_ERR_NO_DEVICE on a host-only plan;
+ *   LOLHIP_ERR_INVALID for NULL pointers at I > 0.  I = 0 returns LOLHIP_OK.  No call synchronises or allocates. */
+LOLHIP_API int64_t lolhip_chall_work_len(const lolhip_plan *pq, int kind, int64_t I, int64_t L);
+LOLHIP_API int lolhip_chall_generate_batch(const lolhip_plan *pq, void *stream, int kind, int64_t p, double svar,
+                                           const uint8_t key[32], uint64_t ctr_s, uint64_t ctr, int64_t I, int64_t L,
+                                           int64_t *s_out, int64_t *a_out, void *b_out, int64_t *work);
+LOLHIP_API int lolhip_chall_verify_batch(const lolhip_plan *pq, void *stream, int kind, int64_t p, int64_t bound_disc,
+                                         double bound_cont, int64_t I, int64_t L, const int64_t *s_dec,
+                                         const int64_t *a_dec, const void *b, int32_t *fails, void *worst, int64_t *work);
+
+/* lolhip_chall_ring_*: the same two calls for ANY single modulus 2 <= q < 2^62, on the plans of lolhip_rlwe_ring_*
+ * above: h the RingMul handle, pq the plan h was created from (T = 1).  Arrays, kinds, verdicts and bounds exactly as
+ * for lolhip_chall_*: everything in the DECODING basis, s [I][n], a [I L][n].
+ * THE STREAM CONTRACT: secret i is the s_pow of lolhip_rlwe_ring_secret at counter ctr_s + i; sample (i, l) is what
+ *   lolhip_rlwe_ring_sample_batch gives for its shat at counter ctr + i L + l; s, a and the Disc b are then taken from
+ *   the powerful to the decoding basis with lInv on pq.
+ * Launch plans: generate  k_rr_draw_lift of the I secrets, crt on pQ -> k_rr_draw_lift of a -> crt on pQ, k_chall_as
+ *   over rows of n K words (the product with shat_(b / L)), crtInv on pQ -> the way out of
+ *   lolhip_rlwe_ring_sample_batch (the fused tails of k_rr_fold at a 2-power index: they do not read the secret) ->
+ *   lInv.  verify  l on pq of s, a (and the Disc b) -> k_ring_lift of both, crt on pQ -> the same product -> the way
+ *   out of lolhip_rlwe_ring_error_batch, or k_ring_fold, lInv and the counting pass (RLWR) -> k_chall_verdict.
+ * work: lolhip_chall_ring_work_len(h, pq, kind, I, L) int64 of device scratch, 16-byte aligned, B = I L:
+ *   even(I n K) + even(B n K) + even(B n) + (kind == 2 ? 0 : even(B n)) + even(I n) + even(B n) +
+ *   (kind == 0 ? even(B n) : 0) + even(B).
+ * Limits and status as for lolhip_rlwe_ring_* with I, L in place of B (I >= 0, L >= 1, I L <= 2^31 - 1, and n K <= 2^31 - 1
+ *   whatever the item count, work_len included); verify needs
+ *   the sampler's index limits and n <= 16384 for Disc and Cont.  I = 0 returns LOLHIP_OK. */
+LOLHIP_API int64_t lolhip_chall_ring_work_len(const lolhip_ringmul *h, const lolhip_plan *pq, int kind, int64_t I, int64_t L);
+LOLHIP_API int lolhip_chall_ring_generate_batch(const lolhip_ringmul *h, const lolhip_plan *pq, void *stream, int kind,
+                                                int64_t p, double svar, const uint8_t key[32], uint64_t ctr_s, uint64_t ctr,
+                                                int64_t I, int64_t L, int64_t *s_out, int64_t *a_out, void *b_out,
+                                                int64_t *work);
+LOLHIP_API int lolhip_chall_ring_verify_batch(const lolhip_ringmul *h, const lolhip_plan *pq, void *stream, int kind,
+                                              int64_t p, int64_t bound_disc, double bound_cont, int64_t I, int64_t L,
+                                              const int64_t *s_dec, const int64_t *a_dec, const void *b, int32_t *fails,
+                                              void *worst, int64_t *work);
+
+/* --- the messages of rlwe-challenges (wire.cpp; lol/RLWE.proto, rlwe-challenges/Challenges.proto), host pointers ------
+ * Readers and writers with the two-pass / capacity convention of the wire entries below: a writer with out = NULL
+ * returns the length; a reader with NULL arrays answers the sizes.  kind: 0 = Disc, 1 = Cont, 2 = RLWR.
+ * The parameters of a kind travel as ip [4] = (m, q, x, numSamples), x = the int64 bound (Disc), unused (Cont) or p
+ * (RLWR), and dp [2] = (svar, the double bound of Cont); RLWRParams has no svar.
+ * lolhip_challenge_*: Challenge, hdr [4] = (challengeID, numInstances, beaconEpoch, beaconOffset) and the params oneof
+ *   (fields 5 / 6 / 7 = Cont / Disc / RLWR).  Returns 0 (read) or the length (write).
+ * lolhip_instance_*: Instance{Cont,Disc,RLWR} and their Product forms.  ids [2] = (challengeID, instanceID); a
+ *   [L][n][T] canonical residues, decoding basis; b [L][n][T] residues mod q_t (Disc) or mod p (RLWR, T = 1), or doubles
+ *   (Cont).  The reader takes both generations, as readInstanceU does (Verify.hs:199-232): it tells them apart by the
+ *   wire type of field 1 of the ring elements (varint m: legacy Rq / Kq; length-delimited rqlist: Product) and reports
+ *   product_out = 0 / 1; it returns n and count_out = L.  The writer emits the Product forms (what Generate.hs writes);
+ *   legacy != 0 selects the forms of the 2016 release (T = 1).  The moduli of an element must be the q of its
+ *   parameters (one modulus, or a tuple whose product is q); the RLWR b is over p.
+ * lolhip_secret_*: Secret / SecretProduct: ids, m, q, the seed bytes and s [n][T].  Returns n (read) or the length.
+ * Unknown fields are skipped.  LOLHIP_ERR_INVALID for truncated or malformed data, a missing required field, samples of
+ *   mixed generations or shapes, an m or q of an element that disagrees with its parameters, a capacity too small;
+ *   LOLHIP_ERR_MODULUS for a modulus outside [2, 2^62). */
+LOLHIP_API int64_t lolhip_challenge_read(const uint8_t *buf, int64_t len, int64_t *hdr, int *kind_out, int64_t *ip, double *dp);
+LOLHIP_API int64_t lolhip_challenge_write(const int64_t *hdr, int kind, const int64_t *ip, const double *dp, uint8_t *out,
+                                          int64_t cap);
+LOLHIP_API int64_t lolhip_instance_read(const uint8_t *buf, int64_t len, int kind, int64_t *ids, int64_t *ip, double *dp,
+                                        int *product_out, int *T_out, int64_t *qs, int cap_T, int64_t *count_out, int64_t *a,
+                                        int64_t cap_a, void *b, int64_t cap_b);
+LOLHIP_API int64_t lolhip_instance_write(int kind, int legacy, const int64_t *ids, const int64_t *ip, const double *dp,
+                                         const int64_t *qs, int T, int64_t L, int64_t n, const int64_t *a, const void *b,
+                                         uint8_t *out, int64_t cap);
+LOLHIP_API int64_t lolhip_secret_read(const uint8_t *buf, int64_t len, int64_t *ids, int64_t *m_out, int64_t *q_out,
+                                      uint8_t *seed, int64_t cap_seed, int64_t *seed_len_out, int *product_out, int *T_out,
+                                      int64_t *qs, int cap_T, int64_t *xs, int64_t cap_xs);
+LOLHIP_API int64_t lolhip_secret_write(int legacy, const int64_t *ids, int64_t m, int64_t q, const uint8_t *seed,
+                                       int64_t seed_len, const int64_t *qs, int T, const int64_t *xs, int64_t n, uint8_t *out,
+                                       int64_t cap);
+
 /* --- gadget error correction (gadget_api.cpp, gadget.hip) ----------------------------------------------------------
  * Correct gad (Cyc t m zq) (Cyc.hs:615-621 over Gadget.hs:84-134 and ZqBasic.hs:234-314), the inverse direction of
  * lolhip_gadget / lolhip_decompose_batch: from L = lolhip_decompose_len(p, base) noisy multiples xs_j = g_j s + e_j of

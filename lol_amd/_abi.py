@@ -156,6 +156,13 @@ ABI = _rows(
     ("rlwe_ring_error_batch", ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, i64),
     ("rlwr_ring_rounded_prod_batch", ci, vp, vp, i64, vp, vp, vp, vp, vp, i64),
     ("rlwr_ring_check_batch", ci, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64),
+    # whole RLWE / RLWR challenges
+    ("chall_work_len", i64, vp, ci, i64, i64),
+    ("chall_generate_batch", ci, vp, vp, ci, i64, f64, cstr, u64, u64, i64, i64, vp, vp, vp, vp),
+    ("chall_verify_batch", ci, vp, vp, ci, i64, i64, f64, i64, i64, vp, vp, vp, vp, vp, vp),
+    ("chall_ring_work_len", i64, vp, vp, ci, i64, i64),
+    ("chall_ring_generate_batch", ci, vp, vp, vp, ci, i64, f64, cstr, u64, u64, i64, i64, vp, vp, vp, vp),
+    ("chall_ring_verify_batch", ci, vp, vp, vp, ci, i64, i64, f64, i64, i64, vp, vp, vp, vp, vp, vp),
     # serialisation (lol_amd/wire.py)
     ("rqproduct_read", i64, _u8p, i64, u32p, _i64p, ci, cip, _i64p, i64),
     ("rqproduct_write", i64, u32, _i64p, ci, _i64p, i64, _u8p, i64),
@@ -172,6 +179,13 @@ ABI = _rows(
     ("tunnelhint_write", i64, _u8p, i64, u8pp, _i64p, ci, u32, u32, u32, u64, _u8p, i64),
     ("chain_read", i64, _u8p, i64, _i64p, _i64p, ci),
     ("chain_write", i64, u8pp, _i64p, ci, _u8p, i64),
+    # the messages of rlwe-challenges (lol_amd/challenges.py)
+    ("challenge_read", i64, _u8p, i64, _i64p, cip, _i64p, f64p),
+    ("challenge_write", i64, _i64p, ci, _i64p, f64p, _u8p, i64),
+    ("instance_read", i64, _u8p, i64, ci, _i64p, _i64p, f64p, cip, cip, _i64p, ci, _i64p, _i64p, i64, vp, i64),
+    ("instance_write", i64, ci, ci, _i64p, _i64p, f64p, _i64p, ci, i64, i64, _i64p, vp, _u8p, i64),
+    ("secret_read", i64, _u8p, i64, _i64p, _i64p, _i64p, _u8p, i64, _i64p, cip, cip, _i64p, ci, _i64p, i64),
+    ("secret_write", i64, ci, _i64p, i64, i64, _u8p, i64, _i64p, ci, _i64p, i64, _u8p, i64),
 )
 
 

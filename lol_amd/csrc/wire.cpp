@@ -558,3 +558,311 @@ int64_t lolhip_chain_write(const uint8_t* const* elems, const int64_t* elem_len,
 }
 
 }  // extern "C"
+
+// ---- rlwe-challenges: RLWE.proto (SampleCont/Disc/RLWR[Product]) and Challenges.proto (Challenge, *Params,
+// Instance*[Product], Secret[Product]) ----------------------------------------------------------------------------
+// kind: 0 = Disc, 1 = Cont, 2 = RLWR, as in lolhip_rlwe_*.  The parameters of a kind travel as ip [4] = (m, q, x,
+// numSamples) with x = the int64 bound (Disc), unused (Cont) or p (RLWR), and dp [2] = (svar, the double bound of Cont).
+// Ring elements are read in either generation (Verify.hs:199-232): the legacy forms hold one Rq / Kq, the Product
+// forms an RqProduct / KqProduct; the first field 1 of the element tells them apart (varint m, or length-delimited
+// rqlist).  Both are read through lolhip_rqproduct_read / lolhip_kqproduct_read, a legacy element as a list of one.
+
+namespace {
+
+typedef std::vector<uint8_t> Bytes;
+enum { CH_DISC = 0, CH_CONT = 1, CH_RLWR = 2, CH_MAX_T = 64 };
+
+void pv(Bytes& o, uint64_t v) { while (v >= 0x80) { o.push_back((uint8_t)(v | 0x80)); v >>= 7; } o.push_back((uint8_t)v); }
+void ptag(Bytes& o, uint32_t f, uint32_t wt) { pv(o, (uint64_t)f << 3 | wt); }
+void pint(Bytes& o, uint32_t f, int64_t v) { ptag(o, f, 0); pv(o, (uint64_t)v); }      // int32 / int64: two's complement
+void pdbl(Bytes& o, uint32_t f, double d) { ptag(o, f, 1); uint8_t b[8]; std::memcpy(b, &d, 8); o.insert(o.end(), b, b + 8); }
+void pbytes(Bytes& o, uint32_t f, const uint8_t* p, size_t n) { ptag(o, f, 2); pv(o, n); if (n) o.insert(o.end(), p, p + n); }
+void psub(Bytes& o, uint32_t f, const Bytes& s) { pbytes(o, f, s.data(), s.size()); }
+
+int64_t emit(const Bytes& o, uint8_t* out, int64_t cap) {
+  if (!out) return (int64_t)o.size();
+  if (cap < (int64_t)o.size()) return LOLHIP_ERR_INVALID;
+  if (!o.empty()) std::memcpy(out, o.data(), o.size());
+  return (int64_t)o.size();
+}
+
+bool kind_ok(int kind) { return kind >= CH_DISC && kind <= CH_RLWR; }
+
+void params_bytes(Bytes& o, int kind, const int64_t* ip, const double* dp) {
+  pint(o, 1, ip[0]); pint(o, 2, ip[1]);
+  if (kind == CH_RLWR) { pint(o, 3, ip[2]); pint(o, 4, ip[3]); return; }
+  pdbl(o, 3, dp[0]);
+  if (kind == CH_CONT) pdbl(o, 4, dp[1]); else pint(o, 4, ip[2]);
+  pint(o, 5, ip[3]);
+}
+
+// every field of the kind's message is `required`
+int params_read(const uint8_t* b, int64_t l, int kind, int64_t* ip, double* dp) {
+  Reader rd{b, b + l};
+  unsigned seen = 0;
+  ip[0] = ip[1] = ip[2] = ip[3] = 0; dp[0] = dp[1] = 0;
+  while (rd.p < rd.end) {
+    uint64_t key, v = 0;
+    if (!rd.varint(key)) return LOLHIP_ERR_INVALID;
+    const uint32_t f = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
+    const bool dbl = wt == 1 && rd.end - rd.p >= 8;
+    if (wt == 1 && !dbl) return LOLHIP_ERR_INVALID;
+    const int last = kind == CH_RLWR ? 4 : 5;
+    if (f == 1 && wt == 0) { if (!rd.varint(v)) return LOLHIP_ERR_INVALID; ip[0] = (int32_t)v; seen |= 1; }
+    else if (f == 2 && wt == 0) { if (!rd.varint(v)) return LOLHIP_ERR_INVALID; ip[1] = (int64_t)v; seen |= 2; }
+    else if ((int)f == last && wt == 0) { if (!rd.varint(v)) return LOLHIP_ERR_INVALID; ip[3] = (int32_t)v; seen |= 16; }
+    else if (kind == CH_RLWR && f == 3 && wt == 0) { if (!rd.varint(v)) return LOLHIP_ERR_INVALID; ip[2] = (int64_t)v; seen |= 4 | 8; }
+    else if (kind != CH_RLWR && f == 3 && dbl) { dp[0] = f64_at(rd.p); rd.p += 8; seen |= 4; }
+    else if (kind == CH_CONT && f == 4 && dbl) { dp[1] = f64_at(rd.p); rd.p += 8; seen |= 8; }
+    else if (kind == CH_DISC && f == 4 && wt == 0) { if (!rd.varint(v)) return LOLHIP_ERR_INVALID; ip[2] = (int64_t)v; seen |= 8; }
+    else if (!rd.skip(wt)) return LOLHIP_ERR_INVALID;
+  }
+  return seen == 31 ? LOLHIP_OK : LOLHIP_ERR_INVALID;
+}
+
+// one ring element of either generation
+struct Elem {
+  bool product = false;
+  uint32_t m = 0;
+  int T = 0;
+  int64_t n = 0;
+  std::vector<int64_t> qs, xi;      // xi [n][T] canonical residues (integer elements)
+  std::vector<double> xd;           // xd [n][T] (Kq elements)
+};
+
+int elem_read(const uint8_t* b, int64_t l, bool dbl, Elem& e) {
+  // the generation: the wire type of the first field 1
+  Reader rd{b, b + l};
+  int gen = -1;
+  while (rd.p < rd.end && gen < 0) {
+    uint64_t key;
+    if (!rd.varint(key)) return LOLHIP_ERR_INVALID;
+    if ((key >> 3) == 1) gen = (key & 7) == 0 ? 0 : (key & 7) == 2 ? 1 : 2;
+    else if (!rd.skip((uint32_t)(key & 7))) return LOLHIP_ERR_INVALID;
+  }
+  if (gen != 0 && gen != 1) return LOLHIP_ERR_INVALID;      // no field 1: m, or a non-empty list, is required
+  e.product = gen == 1;
+  Bytes wrapped;
+  if (!e.product) {                                         // a legacy element as a list of one
+    wrapped.push_back(0x0A); pv(wrapped, (uint64_t)l);
+    wrapped.insert(wrapped.end(), b, b + l);
+    b = wrapped.data(); l = (int64_t)wrapped.size();
+  }
+  e.qs.assign(CH_MAX_T, 0);
+  int64_t n = dbl ? lolhip_kqproduct_read(b, l, &e.m, e.qs.data(), CH_MAX_T, &e.T, nullptr, 0)
+                  : lolhip_rqproduct_read(b, l, &e.m, e.qs.data(), CH_MAX_T, &e.T, nullptr, 0);
+  if (n < 0) return (int)n;
+  e.n = n;
+  e.qs.resize((size_t)e.T);
+  if (dbl) { e.xd.assign((size_t)(n * e.T), 0.0); n = lolhip_kqproduct_read(b, l, nullptr, nullptr, 0, nullptr, e.xd.data(), n * e.T); }
+  else { e.xi.assign((size_t)(n * e.T), 0); n = lolhip_rqproduct_read(b, l, nullptr, nullptr, 0, nullptr, e.xi.data(), n * e.T); }
+  return n < 0 ? (int)n : LOLHIP_OK;
+}
+
+// the moduli of an element against the modulus q of its parameters: one modulus equal to q, or a tuple whose product is q
+bool moduli_are(const std::vector<int64_t>& qs, int64_t q) {
+  unsigned __int128 prod = 1;
+  for (int64_t v : qs) { if (v < 1) return false; prod *= (unsigned __int128)v; if (prod >> 64) return false; }
+  return q > 0 && prod == (unsigned __int128)q;
+}
+
+int elem_int_bytes(Bytes& o, bool legacy, uint32_t m, const int64_t* qs, int T, const int64_t* xs, int64_t n) {
+  if (legacy && T != 1) return LOLHIP_ERR_INVALID;
+  const int64_t len = lolhip_rqproduct_write(m, qs, T, xs, n, nullptr, 0);
+  if (len < 0) return (int)len;
+  Bytes tmp((size_t)len);
+  const int64_t w = lolhip_rqproduct_write(m, qs, T, xs, n, tmp.data(), len);
+  if (w != len) return LOLHIP_ERR_INVALID;
+  size_t skip = 0;
+  if (legacy) { skip = 1; while (tmp[skip] & 0x80) ++skip; ++skip; }        // the rqlist tag and its length
+  o.insert(o.end(), tmp.begin() + (long)skip, tmp.end());
+  return LOLHIP_OK;
+}
+
+int elem_dbl_bytes(Bytes& o, bool legacy, uint32_t m, const int64_t* qs, int T, const double* xs, int64_t n) {
+  if (legacy && T != 1) return LOLHIP_ERR_INVALID;
+  for (int t = 0; t < T; ++t) {
+    if (qs[t] < 2) return LOLHIP_ERR_MODULUS;
+    Bytes kq;
+    pint(kq, 1, m); pint(kq, 2, qs[t]);
+    for (int64_t j = 0; j < n; ++j) pdbl(kq, 3, xs[j * T + t]);
+    if (legacy) o.insert(o.end(), kq.begin(), kq.end()); else psub(o, 1, kq);
+  }
+  return LOLHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lolhip_challenge_read(const uint8_t* buf, int64_t len, int64_t* hdr, int* kind_out, int64_t* ip, double* dp) {
+  if (!buf || len < 0 || !hdr || !kind_out || !ip || !dp) return LOLHIP_ERR_INVALID;
+  Reader rd{buf, buf + len};
+  unsigned seen = 0;
+  int kind = -1;
+  const uint8_t* pb = nullptr; int64_t pl = 0;
+  while (rd.p < rd.end) {
+    uint64_t key, v = 0;
+    if (!rd.varint(key)) return LOLHIP_ERR_INVALID;
+    const uint32_t f = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
+    if (f >= 1 && f <= 4 && wt == 0) {
+      if (!rd.varint(v)) return LOLHIP_ERR_INVALID;
+      hdr[f - 1] = f == 3 ? (int64_t)v : (int64_t)(int32_t)v;
+      seen |= 1u << (f - 1);
+    } else if (f >= 5 && f <= 7 && wt == 2) {               // the oneof: the last arm on the wire wins
+      if (!sub(rd, pb, pl)) return LOLHIP_ERR_INVALID;
+      kind = f == 5 ? CH_CONT : f == 6 ? CH_DISC : CH_RLWR;
+    } else if (!rd.skip(wt)) return LOLHIP_ERR_INVALID;
+  }
+  if (seen != 15 || kind < 0) return LOLHIP_ERR_INVALID;
+  *kind_out = kind;
+  return params_read(pb, pl, kind, ip, dp);
+}
+
+int64_t lolhip_challenge_write(const int64_t* hdr, int kind, const int64_t* ip, const double* dp, uint8_t* out, int64_t cap) {
+  if (!hdr || !ip || !dp || !kind_ok(kind)) return LOLHIP_ERR_INVALID;
+  Bytes o, pr;
+  for (uint32_t f = 1; f <= 4; ++f) pint(o, f, hdr[f - 1]);
+  params_bytes(pr, kind, ip, dp);
+  psub(o, kind == CH_CONT ? 5 : kind == CH_DISC ? 6 : 7, pr);
+  return emit(o, out, cap);
+}
+
+// Instance{Cont,Disc,RLWR}[Product] -> ids [2] = (challengeID, instanceID), the parameters, and the samples: a
+// [L][n][T] residues, b [L][n][T] residues mod q (Disc) or mod p (RLWR), or doubles (Cont).  Pass a = b = NULL to
+// query count_out = L, T_out, qs and the return value n; product_out = 1 when the samples are the Product forms.
+// LOLHIP_ERR_INVALID for truncated data, a missing required field, samples of mixed generations or shapes, or an m or
+// q of a sample that disagrees with the parameters (b of an RLWR sample is over p).
+int64_t lolhip_instance_read(const uint8_t* buf, int64_t len, int kind, int64_t* ids, int64_t* ip, double* dp, int* product_out,
+                             int* T_out, int64_t* qs, int cap_T, int64_t* count_out, int64_t* a, int64_t cap_a, void* b,
+                             int64_t cap_b) {
+  if (!buf || len < 0 || !kind_ok(kind) || !ids || !ip || !dp) return LOLHIP_ERR_INVALID;
+  struct Span { const uint8_t* p; int64_t n; };
+  std::vector<Span> samples;
+  Reader rd{buf, buf + len};
+  unsigned seen = 0;
+  const uint8_t* pb = nullptr; int64_t pl = 0;
+  while (rd.p < rd.end) {
+    uint64_t key, v = 0;
+    if (!rd.varint(key)) return LOLHIP_ERR_INVALID;
+    const uint32_t f = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
+    if ((f == 1 || f == 2) && wt == 0) { if (!rd.varint(v)) return LOLHIP_ERR_INVALID; ids[f - 1] = (int32_t)v; seen |= f; }
+    else if (f == 3 && wt == 2) { if (!sub(rd, pb, pl)) return LOLHIP_ERR_INVALID; seen |= 4; }
+    else if (f == 4 && wt == 2) { Span s; if (!sub(rd, s.p, s.n)) return LOLHIP_ERR_INVALID; samples.push_back(s); }
+    else if (!rd.skip(wt)) return LOLHIP_ERR_INVALID;
+  }
+  if (seen != 7) return LOLHIP_ERR_INVALID;
+  int rc = params_read(pb, pl, kind, ip, dp); if (rc) return rc;
+  const int64_t L = (int64_t)samples.size();
+  int T = 0, product = -1;
+  int64_t n = 0;
+  std::vector<int64_t> q0;
+  for (int64_t i = 0; i < L; ++i) {
+    Reader sr{samples[(size_t)i].p, samples[(size_t)i].p + samples[(size_t)i].n};
+    const uint8_t *ab = nullptr, *bb = nullptr; int64_t al = 0, bl = 0;
+    while (sr.p < sr.end) {
+      uint64_t key;
+      if (!sr.varint(key)) return LOLHIP_ERR_INVALID;
+      const uint32_t f = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
+      if (f == 1 && wt == 2) { if (!sub(sr, ab, al)) return LOLHIP_ERR_INVALID; }
+      else if (f == 2 && wt == 2) { if (!sub(sr, bb, bl)) return LOLHIP_ERR_INVALID; }
+      else if (!sr.skip(wt)) return LOLHIP_ERR_INVALID;
+    }
+    if (!ab || !bb) return LOLHIP_ERR_INVALID;
+    Elem ea, eb;
+    rc = elem_read(ab, al, false, ea); if (rc) return rc;
+    rc = elem_read(bb, bl, kind == CH_CONT, eb); if (rc) return rc;
+    if (i == 0) { T = ea.T; n = ea.n; product = ea.product; q0 = ea.qs; }
+    if (ea.product != (product != 0) || eb.product != ea.product || ea.T != T || eb.T != T || ea.n != n || eb.n != n)
+      return LOLHIP_ERR_INVALID;
+    if ((int64_t)ea.m != ip[0] || (int64_t)eb.m != ip[0] || ea.qs != q0 || !moduli_are(ea.qs, ip[1])) return LOLHIP_ERR_INVALID;
+    if (kind == CH_RLWR ? !moduli_are(eb.qs, ip[2]) : eb.qs != q0) return LOLHIP_ERR_INVALID;
+    if (a) {
+      if (!b || cap_a < L * n * T || cap_b < L * n * T) return LOLHIP_ERR_INVALID;
+      std::memcpy(a + i * n * T, ea.xi.data(), sizeof(int64_t) * (size_t)(n * T));
+      if (kind == CH_CONT) std::memcpy(static_cast<double*>(b) + i * n * T, eb.xd.data(), sizeof(double) * (size_t)(n * T));
+      else std::memcpy(static_cast<int64_t*>(b) + i * n * T, eb.xi.data(), sizeof(int64_t) * (size_t)(n * T));
+    }
+  }
+  if (product_out) *product_out = product > 0;
+  if (T_out) *T_out = T;
+  if (count_out) *count_out = L;
+  if (qs) { if (cap_T < T) return LOLHIP_ERR_INVALID; for (int t = 0; t < T; ++t) qs[t] = q0[(size_t)t]; }
+  return n;
+}
+
+// the Product forms (what Generate.hs writes), or with legacy != 0 the forms of the 2016 release (T = 1).  qs [T]: the
+// moduli of a (and of the Disc / Cont b); the RLWR b is written over p = ip[2].
+int64_t lolhip_instance_write(int kind, int legacy, const int64_t* ids, const int64_t* ip, const double* dp, const int64_t* qs,
+                              int T, int64_t L, int64_t n, const int64_t* a, const void* b, uint8_t* out, int64_t cap) {
+  if (!kind_ok(kind) || !ids || !ip || !dp || !qs || T < 1 || T > CH_MAX_T || L < 0 || n < 0) return LOLHIP_ERR_INVALID;
+  if (L * n > 0 && (!a || !b)) return LOLHIP_ERR_INVALID;
+  if (kind == CH_RLWR && T != 1) return LOLHIP_ERR_INVALID;
+  Bytes o, pr;
+  pint(o, 1, ids[0]); pint(o, 2, ids[1]);
+  params_bytes(pr, kind, ip, dp);
+  psub(o, 3, pr);
+  const uint32_t m = (uint32_t)ip[0];
+  const int64_t pq[1] = {ip[2]};
+  for (int64_t i = 0; i < L; ++i) {
+    Bytes sa, sb, smp;
+    int rc = elem_int_bytes(sa, legacy != 0, m, qs, T, a + i * n * T, n); if (rc) return rc;
+    if (kind == CH_CONT) rc = elem_dbl_bytes(sb, legacy != 0, m, qs, T, static_cast<const double*>(b) + i * n * T, n);
+    else rc = elem_int_bytes(sb, legacy != 0, m, kind == CH_RLWR ? pq : qs, T, static_cast<const int64_t*>(b) + i * n * T, n);
+    if (rc) return rc;
+    psub(smp, 1, sa); psub(smp, 2, sb);
+    psub(o, 4, smp);
+  }
+  return emit(o, out, cap);
+}
+
+// Secret / SecretProduct -> ids [2], m, q, the seed bytes (seed_len_out; copied when cap_seed holds them) and s [n][T].
+// Returns n; xs = NULL queries.  LOLHIP_ERR_INVALID also when the element's m or moduli disagree with the message's.
+int64_t lolhip_secret_read(const uint8_t* buf, int64_t len, int64_t* ids, int64_t* m_out, int64_t* q_out, uint8_t* seed,
+                           int64_t cap_seed, int64_t* seed_len_out, int* product_out, int* T_out, int64_t* qs, int cap_T,
+                           int64_t* xs, int64_t cap_xs) {
+  if (!buf || len < 0 || !ids) return LOLHIP_ERR_INVALID;
+  Reader rd{buf, buf + len};
+  unsigned seen = 0;
+  int64_t m = 0, q = 0, sl = 0, el = 0;
+  const uint8_t *sb = nullptr, *eb = nullptr;
+  while (rd.p < rd.end) {
+    uint64_t key, v = 0;
+    if (!rd.varint(key)) return LOLHIP_ERR_INVALID;
+    const uint32_t f = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
+    if (f >= 1 && f <= 4 && wt == 0) {
+      if (!rd.varint(v)) return LOLHIP_ERR_INVALID;
+      if (f <= 2) ids[f - 1] = (int32_t)v; else if (f == 3) m = (int32_t)v; else q = (int64_t)v;
+      seen |= 1u << (f - 1);
+    } else if (f == 5 && wt == 2) { if (!sub(rd, sb, sl)) return LOLHIP_ERR_INVALID; seen |= 16; }
+    else if (f == 6 && wt == 2) { if (!sub(rd, eb, el)) return LOLHIP_ERR_INVALID; seen |= 32; }
+    else if (!rd.skip(wt)) return LOLHIP_ERR_INVALID;
+  }
+  if (seen != 63) return LOLHIP_ERR_INVALID;
+  Elem e;
+  const int rc = elem_read(eb, el, false, e); if (rc) return rc;
+  if ((int64_t)e.m != m || !moduli_are(e.qs, q)) return LOLHIP_ERR_INVALID;
+  if (m_out) *m_out = m;
+  if (q_out) *q_out = q;
+  if (seed_len_out) *seed_len_out = sl;
+  if (seed) { if (cap_seed < sl) return LOLHIP_ERR_INVALID; if (sl) std::memcpy(seed, sb, (size_t)sl); }
+  if (product_out) *product_out = e.product;
+  if (T_out) *T_out = e.T;
+  if (qs) { if (cap_T < e.T) return LOLHIP_ERR_INVALID; for (int t = 0; t < e.T; ++t) qs[t] = e.qs[(size_t)t]; }
+  if (xs) { if (cap_xs < e.n * e.T) return LOLHIP_ERR_INVALID; std::memcpy(xs, e.xi.data(), sizeof(int64_t) * (size_t)(e.n * e.T)); }
+  return e.n;
+}
+
+int64_t lolhip_secret_write(int legacy, const int64_t* ids, int64_t m, int64_t q, const uint8_t* seed, int64_t seed_len,
+                            const int64_t* qs, int T, const int64_t* xs, int64_t n, uint8_t* out, int64_t cap) {
+  if (!ids || !qs || T < 1 || T > CH_MAX_T || n < 0 || seed_len < 0 || (seed_len > 0 && !seed) || (n > 0 && !xs))
+    return LOLHIP_ERR_INVALID;
+  Bytes o, s;
+  pint(o, 1, ids[0]); pint(o, 2, ids[1]); pint(o, 3, m); pint(o, 4, q);
+  pbytes(o, 5, seed, (size_t)seed_len);
+  const int rc = elem_int_bytes(s, legacy != 0, (uint32_t)m, qs, T, xs, n); if (rc) return rc;
+  psub(o, 6, s);
+  return emit(o, out, cap);
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -1552,6 +1553,49 @@ class RLWE:
         mm = mm if isinstance(mm, np.ndarray) else mm.cpu().numpy()
         return mm == 0
 
+    # ---- whole challenges: I instances of L samples, each under its own secret (lolhip_chall_*) -----------------------
+    @staticmethod
+    def _kind(kind):
+        return {"disc": 0, "cont": 1, "rlwr": 2, 0: 0, 1: 1, 2: 2}[kind]
+
+    def instances(self, kind, I, L, svar=1.0, p=0, key=None, ctr_s=0, ctr=0, stream=None):
+        """I instances of L samples of `kind` ("disc", "cont", "rlwr" or 0 / 1 / 2) in one call (Generate.hs:105-218):
+        CUDA tensors (s [I][n][T], a [I L][n][T], b) in the DECODING basis, the basis of the wire format; b int64
+        [I L][n][T] (Disc), float64 [I L][n] (Cont), int64 [I L][n] in [0, p) (RLWR).  Secret i is secret(key, ctr_s + i)
+        and sample (i, l) is the single-secret sample at counter ctr + i L + l, taken to the decoding basis.  Never
+        reuse the counters ctr_s .. ctr_s + I - 1 and ctr .. ctr + I L - 1 under one key."""
+        Lb, P, kb, kind, I, L = lib(), self.plan, _key(key), self._kind(kind), int(I), int(L)
+        call = lambda st, i, o, w, nb: Lb.lolhip_chall_generate_batch(P._h, st, kind, int(p), float(svar), kb, int(ctr_s),
+                                                                      int(ctr), nb, L, o[0], o[1], o[2], w)
+        B = I * L
+        return tuple(_run(call, stream, (), I, lambda: Lb.lolhip_chall_work_len(P._h, kind, I, L),
+                          lambda: [((I, P.n, P.T), "int64"), ((B, P.n, P.T), "int64"),
+                                   ((B, P.n, P.T) if kind == self.DISC else (B, P.n),
+                                    "float64" if kind == self.CONT else "int64")], unstage=False))
+
+    def validInstances(self, kind, s_dec, a_dec, b, bound=0, p=0, stream=None):
+        """The verdict on I instances in one call (Verify.hs:346-366), all arrays in the decoding basis as instances()
+        returns them; L = the samples of a_dec over the secrets of s_dec.  Returns (fails int32 [I], worst [I]): the
+        samples of instance i that fail the strict comparison bound > norm (Disc: bound an int; Cont: a float) or
+        mismatch (RLWR), and the largest norm (int64, float64) or mismatch count (int64).  Instance i is valid when
+        fails[i] == 0."""
+        Lb, P, kind = lib(), self.plan, self._kind(kind)
+        # an integer norm is below `bound` exactly when it is below its ceiling; beyond int64 only a saturated norm fails
+        bd, bc = (max(-2 ** 63, min(2 ** 63 - 1, math.ceil(bound))), 0.0) if kind == self.DISC else (0, float(bound))
+        geom = {}
+        call = lambda st, i, o, w, nb: Lb.lolhip_chall_verify_batch(P._h, st, kind, int(p), bd, bc, nb, geom.get("L", 1),
+                                                                    i[0], i[1], i[2], o[0], o[1], w)
+        _dry(call)                                                   # before the shape checks
+        I, B = _count(s_dec, P.n * P.T, "s_dec is not [I][n][T]"), self._batch(a_dec)
+        if I < 1 or B < 1 or B % I:
+            raise ValueError("a_dec is not a whole number of samples per secret")
+        if _size(b) != B * P.n * (P.T if kind == self.DISC else 1):
+            raise ValueError("a and b are not the same number of samples")
+        geom["L"] = B // I
+        dt = "float64" if kind == self.CONT else "int64"
+        return tuple(_run(call, stream, (s_dec, a_dec, (b, dt)), I, lambda: Lb.lolhip_chall_work_len(P._h, kind, I, B // I),
+                          lambda: [((I,), "int32"), ((I,), dt)], dry=False))
+
     @staticmethod
     def errorBound(m, svar, eps=2.0 ** -25, kind="cont"):
         """errorBound svar eps over index m (host): kind "cont" (Continuous.hs:74-84) a float, "disc" (Discrete.hs:65-76)
@@ -1677,6 +1721,39 @@ class RingRLWE:
             raise ValueError("a and b are not the same number of samples")
         return _run(call, stream, (a, b, shat), B, self._work_len(self.RLWR, B), lambda: [((B,), "int32")], dry=False,
                     min_work=2)[0]
+
+    # ---- whole challenges: I instances of L samples, each under its own secret (lolhip_chall_ring_*) ------------------
+    def instances(self, kind, I, L, svar=1.0, p=0, key=None, ctr_s=0, ctr=0, stream=None):
+        """RLWE.instances over this class's moduli: CUDA tensors (s [I][n], a [I L][n], b [I L][n]) in the DECODING
+        basis, b int64 (Disc, RLWR) or float64 (Cont).  Secret i is the s_pow of secret(key, ctr_s + i) and sample (i, l)
+        the single-secret sample at counter ctr + i L + l, taken to the decoding basis with lInv."""
+        Lb, P, kb, kind, I, L, (h, pq) = lib(), self.plan, _key(key), RLWE._kind(kind), int(I), int(L), self._hp()
+        call = lambda st, i, o, w, nb: Lb.lolhip_chall_ring_generate_batch(h, pq, st, kind, int(p), float(svar), kb, int(ctr_s),
+                                                                           int(ctr), nb, L, o[0], o[1], o[2], w)
+        B = I * L
+        return tuple(_run(call, stream, (), I, lambda: Lb.lolhip_chall_ring_work_len(h, pq, kind, I, L),
+                          lambda: [((I, P.n), "int64"), ((B, P.n), "int64"),
+                                   ((B, P.n), "float64" if kind == self.CONT else "int64")], unstage=False, min_work=2))
+
+    def validInstances(self, kind, s_dec, a_dec, b, bound=0, p=0, stream=None):
+        """RLWE.validInstances over this class's moduli: (fails int32 [I], worst [I]) of I instances given in the
+        decoding basis, s_dec [I][n], a_dec [I L][n], b [I L][n]"""
+        Lb, P, kind, (h, pq) = lib(), self.plan, RLWE._kind(kind), self._hp()
+        bd, bc = (max(-2 ** 63, min(2 ** 63 - 1, math.ceil(bound))), 0.0) if kind == self.DISC else (0, float(bound))
+        geom = {}
+        call = lambda st, i, o, w, nb: Lb.lolhip_chall_ring_verify_batch(h, pq, st, kind, int(p), bd, bc, nb, geom.get("L", 1),
+                                                                         i[0], i[1], i[2], o[0], o[1], w)
+        _dry(call)                                                   # before the shape checks
+        I, B = _count(s_dec, P.n, "s_dec is not [I][n]"), self._batch(a_dec)
+        if I < 1 or B < 1 or B % I:
+            raise ValueError("a_dec is not a whole number of samples per secret")
+        if _size(b) != B * P.n:
+            raise ValueError("a and b are not the same number of samples")
+        geom["L"] = B // I
+        dt = "float64" if kind == self.CONT else "int64"
+        return tuple(_run(call, stream, (s_dec, a_dec, (b, dt)), I,
+                          lambda: Lb.lolhip_chall_ring_work_len(h, pq, kind, I, B // I),
+                          lambda: [((I,), "int32"), ((I,), dt)], dry=False, min_work=2))
 
     # ---- instance verification: RLWE's comparisons over this class's norms ----------------------------------------------
     validDisc, validCont, validRLWR = RLWE.validDisc, RLWE.validCont, RLWE.validRLWR

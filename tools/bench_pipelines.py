@@ -12,7 +12,9 @@ and of L / divG over int64 and double slabs (`--eltops`: that leg alone, also wr
 and of the ciphertext product of any degree (`--ctmul`: that leg alone, also written to profiles/ctmul_bench.jsonl)
 and of the key-homomorphic lattice PRF, matrix-core route against VALU route (`--lprf`: that leg alone, also written to
 profiles/lprf_bench.jsonl) and of RLWE / RLWR instances over moduli without a CRT basis, fused tails against the general
-composition (`--rlwe-ring`: that leg alone, also written to profiles/rlwe_ring_bench.jsonl).
+composition (`--rlwe-ring`: that leg alone, also written to profiles/rlwe_ring_bench.jsonl) and of whole RLWE challenges,
+one grouped call against 32 single-secret calls (`--challenge`: that leg alone, also written to
+profiles/challenge_bench.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -811,6 +813,118 @@ def rlwe_ring_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def challenge_leg(gen):
+    """One whole challenge of I = 32 instances, generate and verify (Disc and RLWR), at L = 3 and L = 100 on m = 256 /
+    q = 769 (lolhip_chall_*, a CRT basis) and m = 256 / q = 512 (lolhip_chall_ring_*): the grouped call against the same
+    work as 32 single-secret calls in the same process.  The single-secret generate is secret + sample per instance and
+    then the three basis changes over the whole arrays (the grouped call returns the decoding basis); the single-secret
+    verify is the basis changes, prepare (ring) and error + norm / check per instance.  Both verifies end with the copy of
+    their verdicts to the host (32 counts, or 32 L norms).  Times include the launch path: at L = 3 that is the point.
+    Median of five rounds of ten calls, HIP events.  Also written to profiles/challenge_bench.jsonl."""
+    import statistics
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    ptr = lambda t: t.data_ptr()
+    lines = []
+    key, svar, I, m, p = bytes(range(32)), 7.8125e-3, 32, 256, 2
+    i64 = lambda *sh: torch.empty(sh, dtype=torch.int64, device="cuda")
+
+    def rep(name, cfg, ts, **more):
+        d = {"op": name, "config": cfg, "ms": round(statistics.median(ts), 4), "ms_min": round(min(ts), 4),
+             "ms_max": round(max(ts), 4)}
+        d.update(more)
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+        return d["ms"]
+
+    def ok(rc):
+        assert rc == 0, rc
+
+    for q in (769, 512):
+        P = lol_amd.Plan.for_index(m, [q])
+        ring = not P.has_crt
+        r = lol_amd.RingRLWE(P) if ring else lol_amd.RLWE(P)
+        n, K = P.n, (r.K if ring else 1)
+        hp = (r.ring._h, P._h) if ring else (P._h,)
+        pre = "lolhip_chall_ring_" if ring else "lolhip_chall_"
+        one = "lolhip_rlwe_ring_" if ring else "lolhip_rlwe_"
+        for ell in (3, 100):
+            B = I * ell
+            for kind, kname in ((0, "disc"), (2, "rlwr")):
+                cfg = f"m={m} n={n} q={q} route={'ring' if ring else 'plan'} kind={kname} I={I} L={ell}"
+                bound = lol_amd.RLWE.errorBound(m, svar, kind="disc") if kind == 0 else 0
+                s, a, b = i64(I, n), i64(B, n), i64(B, n)
+                fails, worst = torch.empty((I,), dtype=torch.int32, device="cuda"), i64(I)
+                work = i64(max(getattr(L, pre + "work_len")(*hp, kind, I, ell), 2))
+                g_gen = lambda: ok(getattr(L, pre + "generate_batch")(*hp, st, kind, p, svar, key, 0, 0, I, ell, ptr(s), ptr(a),
+                                                                      ptr(b), ptr(work)))
+
+                def g_ver():
+                    ok(getattr(L, pre + "verify_batch")(*hp, st, kind, p, bound, 0.0, I, ell, ptr(s), ptr(a), ptr(b), ptr(fails),
+                                                        ptr(worst), ptr(work)))
+                    return fails.cpu()
+
+                # the single-secret calls: per-instance slabs of the same arrays
+                s1, a1, b1 = i64(I, n), i64(B, n), i64(B, n)
+                shat = i64(I, n, K)
+                nm, mm = i64(B), torch.empty((B,), dtype=torch.int32, device="cuda")
+                w1 = i64(max(getattr(L, one + "work_len")(*hp, kind, ell), 2))
+                row = lambda t, i, per: t.data_ptr() + 8 * i * per * n
+                to_dec = ((L.lolhip_linv_batch,) if ring else (L.lolhip_crtinv_batch, L.lolhip_linv_batch))
+                to_in = ((L.lolhip_l_batch,) if ring else (L.lolhip_l_batch, L.lolhip_crt_batch))
+
+                def s_gen():
+                    for i in range(I):
+                        if ring:
+                            ok(L.lolhip_rlwe_ring_secret(*hp, st, key, i, row(s1, i, 1), row(shat, i, K)))
+                            sec = row(shat, i, K)
+                        else:
+                            ok(L.lolhip_rlwe_secret(*hp, st, key, i, row(s1, i, 1)))
+                            sec = row(s1, i, 1)
+                        ok(getattr(L, one + "sample_batch")(*hp, st, kind, p, sec, svar, key, i * ell, row(a1, i, ell),
+                                                            row(b1, i, ell), ptr(w1), ell))
+                    for f in to_dec:
+                        ok(f(P._h, st, ptr(s1), I)); ok(f(P._h, st, ptr(a1), B))
+                        if kind == 0:
+                            ok(f(P._h, st, ptr(b1), B))
+
+                sc, ac, bc = i64(I, n), i64(B, n), i64(B, n)
+
+                def s_ver():
+                    sc.copy_(s1); ac.copy_(a1); bc.copy_(b1)
+                    for f in to_in:
+                        ok(f(P._h, st, ptr(sc), I)); ok(f(P._h, st, ptr(ac), B))
+                        if kind == 0:
+                            ok(f(P._h, st, ptr(bc), B))
+                    for i in range(I):
+                        sec = row(sc, i, 1)
+                        if ring:
+                            ok(L.lolhip_ringmul_prepare(r.ring._h, st, row(shat, i, K), sec, None, 1))
+                            sec = row(shat, i, K)
+                        if kind == 0:
+                            ok(getattr(L, one + "error_batch")(*hp, st, 0, row(ac, i, ell), row(bc, i, ell), sec, None,
+                                                               nm.data_ptr() + 8 * i * ell, ptr(w1), ell))
+                        else:
+                            chk = L.lolhip_rlwr_ring_check_batch if ring else L.lolhip_rlwr_check_batch
+                            ok(chk(*hp, p, st, row(ac, i, ell), row(bc, i, ell), sec, mm.data_ptr() + 4 * i * ell, ptr(w1), ell))
+                    return (nm if kind == 0 else mm).cpu()
+
+                g_gen(); s_gen()
+                torch.cuda.synchronize()
+                assert torch.equal(s, s1) and torch.equal(a, a1) and torch.equal(b, b1), cfg
+                f_g, v_s = g_ver(), s_ver()
+                assert not f_g.any() and ((v_s < bound).all() if kind == 0 else not v_s.any()), cfg
+                rounds = lambda fn: [timeit(fn) for _ in range(5)]
+                for what, gfn, sfn in (("generate", g_gen, s_gen), ("verify", g_ver, s_ver)):
+                    tg = rep(f"chall_{what}(grouped)", cfg, rounds(gfn))
+                    ts = rep(f"chall_{what}(32 single-secret calls)", cfg, rounds(sfn))
+                    rep(f"chall_{what} speedup", cfg, [ts / tg])
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    os.makedirs(os.path.join(root, "profiles"), exist_ok=True)
+    with open(os.path.join(root, "profiles", "challenge_bench.jsonl"), "w") as f:
+        f.write("\n".join(json.dumps(d) for d in lines) + "\n")
+
+
 def gadget_correct_leg(gen):
     """Gadget error correction (lolhip_gadget_correct_batch, decoding basis) at config 5's shape (m = 2048, q = (1017857,
     1032193), B = 8192) with base 256 and over one 61-bit modulus (q = 2^60 + 147457, m = 2^14, B = 64) with base 2: with
@@ -1141,6 +1255,9 @@ def ctmul_leg(gen):
 
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--challenge" in sys.argv:        # the whole-challenge leg alone
+        challenge_leg(gen)
+        return
     if "--lprf" in sys.argv:             # the key-homomorphic lattice PRF leg alone
         lprf_leg(gen)
         return
