@@ -101,6 +101,27 @@ LOLHIP_API int lolhip_plan_create(const lolhip_pp *pps, int npps, const int64_t 
 LOLHIP_API int lolhip_plan_create_roots(const lolhip_pp *pps, int npps, const int64_t *qs, int T,
                                         const int64_t *omega_pp, const int64_t *mhatinv,
                                         int host_only, lolhip_plan **out);
+/* lolhip_plan_create with options.  flags = 0 is lolhip_plan_create exactly; a bit that is not defined below answers
+ * LOLHIP_ERR_INVALID.
+ *   LOLHIP_PLAN_DENSE_GAUSS  the Gaussian map (lolhip_gaussian_dec_batch, and through it every sampler: encrypt,
+ *       errorRounded / genSK, key-switch and tunnel hints, the Cont and Disc instances of RLWE, RingRLWE and the
+ *       challenge entries) takes any index with n <= 8192 whose primes are below 2^15: an odd prime above 13 runs as
+ *       a dense stage (a batched FP64 matrix product out of a transposed copy of its (p-1) x (p-1) matrix, which only
+ *       such a plan builds), primes up to 13 keep their register stage.  Same summation order, so an index both
+ *       routes take gives the same bits on either.  The 2-power rule of the samplers and the limit of crtc / crtinvc
+ *       are unchanged. */
+#define LOLHIP_PLAN_DENSE_GAUSS 1u
+LOLHIP_API int lolhip_plan_create_flags(const lolhip_pp *pps, int npps, const int64_t *qs, int T,
+                                        int host_only, uint32_t flags, lolhip_plan **out);
+/* How lolhip_gaussian_dec_batch runs on this plan: 0 refused (LOLHIP_ERR_INVALID), 1 register stages only, 2 with a
+ * dense stage.  A function of the prime powers and the flags (and the GAUSS_DENSE debug switch at creation, which
+ * makes every odd prime of an opted-in plan dense), so host-only plans answer it too; 0 for a null plan. */
+LOLHIP_API int lolhip_plan_gauss_route(const lolhip_plan *p);
+/* The real matrix of tensorGaussianDec for prime power k of the plan (inspection, tests): row-major
+ * (p-1) x (p-1) entries 2 c(row * col mod p) (transposed == 0), or the transposed copy the dense stage reads
+ * (transposed != 0; empty unless that prime takes the dense stage).  Copies min(len, available) doubles and returns
+ * the available count; 0 for p = 2 or a k out of range. */
+LOLHIP_API int64_t lolhip_plan_gauss_table(const lolhip_plan *p, int k, int transposed, double *out, int64_t len);
 LOLHIP_API void lolhip_plan_destroy(lolhip_plan *p);
 
 LOLHIP_API int64_t lolhip_plan_n(const lolhip_plan *p);      /* totient(m) */
@@ -156,7 +177,8 @@ LOLHIP_API int lolhip_divgcrt_batch(const lolhip_plan *p, void *stream, int64_t 
  * gaussian_dec: replaces tensorGaussianDec (random.cpp:19-64; caller CPP.hs:376-389): y [B][n]
  *   doubles, on entry iid real Gaussians, on exit the sample in the decoding basis (the caller
  *   draws and scales the Gaussians and rounds the result, as cDispatchGaussian does).
- * Both need n <= 8192 and every prime of m <= 13, else LOLHIP_ERR_INVALID. */
+ * Both need n <= 8192 and every prime of m <= 13, else LOLHIP_ERR_INVALID.  On a plan created with
+ * LOLHIP_PLAN_DENSE_GAUSS, gaussian_dec takes every prime below 2^15 (n <= 8192 still); crtc / crtinvc do not. */
 LOLHIP_API int lolhip_crtc_batch        (const lolhip_plan *p, void *stream, double *y, int64_t B);
 LOLHIP_API int lolhip_crtinvc_batch     (const lolhip_plan *p, void *stream, double *y, int64_t B);
 LOLHIP_API int lolhip_gaussian_dec_batch(const lolhip_plan *p, void *stream, double *y, int64_t B);
@@ -309,11 +331,12 @@ LOLHIP_API int lolhip_decrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp
  *   decoding-basis coefficients rounded half to even; the plan supplies the index only.  work is not used (the sampler
  *   runs in place in z_dec) and may be NULL.
  * Limits: T <= 16; n' <= 16384 for m' = 2^k; otherwise the limits of lolhip_gaussian_dec_batch (n' <= 8192, primes
- *   <= 13).
+ *   <= 13; primes below 2^15 when the plan of index m' was created with LOLHIP_PLAN_DENSE_GAUSS).
  * Status: LOLHIP_ERR_INVALID for svar <= 0 or not finite, B < 0, pp not of index m' or not of one modulus, x_p not
  *   ending in pp's ring and modulus, T > 16, an index beyond the limits; LOLHIP_ERR_NO_CRT when pq has no CRT basis;
- *   LOLHIP_ERR_MODULUS for p < 2; LOLHIP_ERR_NO_DEVICE on a host-only plan.  Every one is decided on the host before
- *   any launch: the output is then not written.  No call synchronises or allocates. */
+ *   LOLHIP_ERR_MODULUS for p < 2; LOLHIP_ERR_NO_DEVICE on a host-only plan (an index beyond the limits is answered
+ *   first, there too: it is a property of the plan).  Every one is decided on the host before any launch: the output is
+ *   then not written.  No call synchronises or allocates. */
 LOLHIP_API int64_t lolhip_encrypt_work_len(const lolhip_plan *pq, int64_t B);
 LOLHIP_API int lolhip_encrypt_batch(const lolhip_plan *pq, const lolhip_plan *pp, const lolhip_ext *x_p, void *stream,
                                     const int64_t *pt_pow, const int64_t *s_crt, double svar, const uint8_t key[32],
@@ -1177,13 +1200,18 @@ LOLHIP_API int64_t lolhip_chain_write(const uint8_t *const *elems, const int64_t
 LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_t bytes, int variant);
 
 /* Test and A/B aid, not part of the drop-in surface: force a launch path.  `name` is one of
- * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL, LPRF_VALU and RLWE_RING_UNFUSED (each is
+ * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL, LPRF_VALU, RLWE_RING_UNFUSED and GAUSS_DENSE (read when a plan is built: every odd prime of a plan created with LOLHIP_PLAN_DENSE_GAUSS takes the dense stage of the Gaussian map) (each is
  * also read ONCE at first use from the environment variable LOLHIP_<name>); value 0 restores the
  * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID.
  * Two environment variables are test hooks of the persistent pipelined poly-mul, read at EVERY launch of it:
  *   LOLHIP_PIPE_GRID=<G>  its grid is G workgroups (clamped to the batch) instead of the resident-workgroup count;
  *   LOLHIP_PIPE_INFO      (set to anything) each launch prints one line to stderr, before the grid is clamped:
- *                         "k_pow2_pipe<L,AR>: lds <bytes> B, per_cu <w>, occupancy query <o> (err <e>), grid <G>". */
+ *                         "k_pow2_pipe<L,AR>: lds <bytes> B, per_cu <w>, occupancy query <o> (err <e>), grid <G>".
+ * One more is read at every launch of the Gaussian map:
+ *   LOLHIP_GAUSS_INFO     (set to anything) each launch prints one line to stderr naming the route of every stage:
+ *                         "k_gauss: n <n>, B <B>, stages reg" for a program of register stages, else
+ *                         "k_gauss_dense: n <n>, B <B>, items <I>, bufs <1|2>, lds <bytes> B, grid <G>, stages <route> ...",
+ *                         route one of reg, dense-rows (lanes along the rows, stride < 64), dense-cols (lanes along r). */
 LOLHIP_API int lolhip_debug_set(const char *name, int value);
 
 /* number of HIP devices visible (0 without a GPU); never initialises a context */

@@ -14,6 +14,7 @@ _ERRNAMES = {ERR_INVALID: "invalid argument", ERR_MODULUS: "modulus out of range
 OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC, OP_MULGCRT, OP_DIVGCRT = range(12)
 EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS = range(6)
 ELT_I64, ELT_F64, ELT_C64 = range(3)
+PLAN_DENSE_GAUSS = 1
 
 
 class LolHipError(RuntimeError):
@@ -67,6 +68,9 @@ ABI = _rows(
     # plans and the Tensor operations
     ("plan_create", ci, pp, ci, _i64p, ci, ci, vpp),
     ("plan_create_roots", ci, pp, ci, _i64p, ci, _i64p, _i64p, ci, vpp),
+    ("plan_create_flags", ci, pp, ci, _i64p, ci, ci, u32, vpp),
+    ("plan_gauss_route", ci, vp),
+    ("plan_gauss_table", i64, vp, ci, ci, f64p, i64),
     ("plan_destroy ext_destroy khprf_destroy tunnel_chain_destroy ptround_destroy pt_tunnel_destroy ringmul_destroy lprf_destroy", None, vp),
     ("plan_n plan_m", i64, vp),
     ("plan_T plan_has_crt", ci, vp),

@@ -174,9 +174,10 @@ def suppressed_secret_id(num_instances, beacon_byte):
 
 
 # ---- one challenge on the device ---------------------------------------------------------------------------------------------
-def route(cp, host_only=True):
-    """("plan" | "ring", Plan): lolhip_plan_has_crt decides, as for the single-secret entries"""
-    plan = Plan.for_index(cp.m, [cp.q], host_only=host_only)
+def route(cp, host_only=True, dense_gauss=False):
+    """("plan" | "ring", Plan): lolhip_plan_has_crt decides, as for the single-secret entries.  dense_gauss: the plan
+    opts in to the dense stage of the Gaussian map, which the error of a Cont or Disc challenge needs at a prime above 13"""
+    plan = Plan.for_index(cp.m, [cp.q], host_only=host_only, dense_gauss=dense_gauss)
     return ("plan" if plan.has_crt else "ring"), plan
 
 
@@ -188,7 +189,7 @@ def error_bound(cp):
 def _engine(cp):
     if not cp.supported:
         raise ParamsError(f"{challenge_name(cp)}: p = q is not supported (the rounding needs 2 <= p < q)")
-    which, plan = route(cp, host_only=False)
+    which, plan = route(cp, host_only=False, dense_gauss=cp.kind in ("Cont", "Disc"))
     return RLWE(plan) if which == "plan" else RingRLWE(plan)
 
 
@@ -325,10 +326,11 @@ def secret_read(data):
 
 # ---- the tree layer: Generate.hs / Verify.hs / Suppress.hs over files ---------------------------------------------------
 class DeviceEngine:
-    """the two batched calls on the GPU for one (m, q): RLWE or RingRLWE as lolhip_plan_has_crt decides"""
+    """the two batched calls on the GPU for one (m, q): RLWE or RingRLWE as lolhip_plan_has_crt decides.  The plan opts
+    in to the dense stage of the Gaussian map (a Cont or Disc error at a prime above 13; nothing changes elsewhere)"""
 
     def __init__(self, m, q):
-        plan = Plan.for_index(m, [q])
+        plan = Plan.for_index(m, [q], dense_gauss=True)
         self.r = RLWE(plan) if plan.has_crt else RingRLWE(plan)
         self.n = plan.n
 

@@ -23,7 +23,7 @@ using namespace lolhip;
 namespace lolhip {
 namespace {
 const char* const kSwitchNames[SW_COUNT] = {"GENERIC_SCALAR", "NO_FUSED2", "NO_POW2_PART", "POLYMUL_UNFUSED",
-                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED"};
+                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE"};
 std::atomic<int> g_switch[SW_COUNT];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -52,7 +52,7 @@ int device_count() {
 }
 
 int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const int64_t* omega_pp,
-              const int64_t* mhatinv, int host_only, lolhip_plan** out) {
+              const int64_t* mhatinv, int host_only, lolhip_plan** out, uint32_t flags = 0) {
   std::vector<PP> v;
   if (!out || T < 1 || !qs || !to_pps(pps, npps, v)) return LOLHIP_ERR_INVALID;
   *out = nullptr;
@@ -67,7 +67,7 @@ int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const in
     om.push_back((u64)(((omega_pp[i] % qq) + qq) % qq));
   }
   std::unique_ptr<lolhip_plan> p(new lolhip_plan());
-  int rc = plan_build_host(p->P, v, q, omega_pp ? om.data() : nullptr, mhatinv);
+  int rc = plan_build_host(p->P, v, q, omega_pp ? om.data() : nullptr, mhatinv, flags);
   if (rc != LOLHIP_OK) return rc;
   if (!host_only) {
     rc = plan_upload(p->P);
@@ -284,6 +284,23 @@ int lolhip_plan_create_roots(const lolhip_pp* pps, int npps, const int64_t* qs, 
                              const int64_t* mhatinv, int host_only, lolhip_plan** out) {
   return make_plan(pps, npps, qs, T, omega_pp, mhatinv, host_only, out);
 }
+int lolhip_plan_create_flags(const lolhip_pp* pps, int npps, const int64_t* qs, int T, int host_only, uint32_t flags,
+                             lolhip_plan** out) {
+  return make_plan(pps, npps, qs, T, nullptr, nullptr, host_only, out, flags);
+}
+int lolhip_plan_gauss_route(const lolhip_plan* p) { return p ? p->P.gauss_route : 0; }
+int64_t lolhip_plan_gauss_table(const lolhip_plan* p, int k, int transposed, double* out, int64_t len) {
+  if (!p || k < 0 || k >= (int)p->P.pps.size() || p->P.pps[(size_t)k].p == 2) return 0;
+  for (const Stage& st : p->P.prog_gauss.stages) {
+    if (st.p != p->P.pps[(size_t)k].p) continue;
+    const int off = transposed ? st.wp_off : st.mat_off;
+    if (off <= 0) return 0;
+    const int64_t avail = (int64_t)st.d * st.d;
+    if (out && len > 0) std::memcpy(out, p->P.host_rconsts.data() + off, sizeof(double) * (size_t)(len < avail ? len : avail));
+    return avail;
+  }
+  return 0;
+}
 void lolhip_plan_destroy(lolhip_plan* p) { delete p; }
 int64_t lolhip_plan_n(const lolhip_plan* p) { return p ? p->P.n : 0; }
 int64_t lolhip_plan_m(const lolhip_plan* p) { return p ? p->P.m : 0; }
@@ -429,25 +446,26 @@ int lolhip_divgcrt_batch(const lolhip_plan* p, void* stream, int64_t* y, int64_t
 
 // ---- floating-point members of the class ---------------------------------
 
-static int float_ready(const lolhip_plan* p) {
+static int cplx_ready(const lolhip_plan* p) {
   int rc = need_device(p); if (rc) return rc;
-  return p->P.float_ok ? LOLHIP_OK : LOLHIP_ERR_INVALID;      // n > 8192 or a prime > 13
+  return p->P.cplx_ok ? LOLHIP_OK : LOLHIP_ERR_INVALID;       // n > 8192 or a prime > 13
 }
 int lolhip_crtc_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
-  int rc = float_ready(p); if (rc) return rc;
+  int rc = cplx_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
   return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crt.d_stages, P.prog_crt.nstages, P.d_cconsts));
 }
 int lolhip_crtinvc_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
-  int rc = float_ready(p); if (rc) return rc;
+  int rc = cplx_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
   return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crtinv.d_stages, P.prog_crtinv.nstages,
                                 P.d_cconsts));
 }
 int lolhip_gaussian_dec_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
-  int rc = float_ready(p); if (rc) return rc;
+  int rc = need_device(p); if (rc) return rc;
+  if (!p->P.gauss_route) return LOLHIP_ERR_INVALID;           // n > 8192, or a prime > 13 on a plan that has not opted in
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
   return hip_status(launch_gauss((hipStream_t)stream, y, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages,

@@ -35,7 +35,8 @@ int64_t lolhip_encrypt_work_len(const lolhip_plan* pq, int64_t B) {
 int lolhip_encrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lolhip_ext* x_p, void* stream,
                          const int64_t* pt_pow, const int64_t* s_crt, double svar, const uint8_t key[32], uint64_t ctr,
                          int out_crt, int64_t* cs_out, int64_t* work, int64_t B) {
-  int rc = need_device(pq); if (rc) return rc;
+  int rc = index_status(pq); if (rc) return rc;
+  rc = need_device(pq); if (rc) return rc;
   if (!pp) return LOLHIP_ERR_INVALID;
   rc = need_device(pp); if (rc) return rc;
   const Plan &P = pq->P, &PP = pp->P;
@@ -91,7 +92,8 @@ int lolhip_encrypt_batch(const lolhip_plan* pq, const lolhip_plan* pp, const lol
 int lolhip_error_rounded_batch(const lolhip_plan* p, void* stream, double svar, const uint8_t key[32], uint64_t ctr,
                                int64_t* z_dec, int64_t* work, int64_t B) {
   (void)work;
-  int rc = need_device(p); if (rc) return rc;
+  int rc = index_status(p); if (rc) return rc;
+  rc = need_device(p); if (rc) return rc;
   const Plan& P = p->P;
   if (!svar_ok(svar) || B < 0) return LOLHIP_ERR_INVALID;
   rc = sampler_ok(P); if (rc) return rc;

@@ -109,6 +109,12 @@ hipError_t launch_mixed(const MixedLaunch& a);
 
 // floating-point side (floatpath.hip): y [B][n] complex doubles (re, im interleaved) / doubles, in place
 hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* cconsts);
+// launch_gauss: the low 8 bits of nstages are the number of stages; above them sit two bits per stage, its route
+// (gauss_stage_route).  A program of register stages therefore passes its plain count.  plan_upload packs the word
+// into StageProgram::nstages of prog_gauss: the launcher sees only device copies of the stages, and the routes are what
+// pick the kernel, its LDS tile and the info line (LOLHIP_GAUSS_INFO).
+enum GaussRoute : int { GAUSS_REG = 0, GAUSS_ROWS = 1, GAUSS_COLS = 2 };   // register vectors; dense, lanes along rows / along r
+inline int gauss_stage_route(int nstages, int s) { return (nstages >> (8 + 2 * s)) & 3; }
 hipError_t launch_gauss(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* rconsts);
 
 // 16-byte-per-lane copy of a slab: the measured ceiling of a read-once/write-once kernel (bench.py's yardstick)

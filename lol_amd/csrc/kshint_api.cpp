@@ -66,7 +66,8 @@ int64_t lolhip_kshint_work_len(const lolhip_plan* pq, int64_t base, int64_t B) {
 
 int lolhip_kshint_batch(const lolhip_plan* pq, void* stream, const int64_t* s_crt, const int64_t* vals_crt, double svar,
                         int64_t base, const uint8_t key[32], uint64_t ctr, int64_t* hints_out, int64_t* work, int64_t B) {
-  int rc = need_device(pq); if (rc) return rc;
+  int rc = index_status(pq); if (rc) return rc;
+  rc = need_device(pq); if (rc) return rc;
   DecompParams d;
   rc = hint_status(pq->P, svar, base, B, d); if (rc) return rc;
   if (B > 0 && (!s_crt || !vals_crt || !key || !hints_out || !work)) return LOLHIP_ERR_INVALID;

@@ -8,6 +8,7 @@
 #include <complex>
 #include <cstring>
 
+#include "kernels.h"
 #include "lolhip.h"
 
 namespace lolhip {
@@ -304,7 +305,9 @@ static bool merge_stages(std::vector<Stage>& st, PoolBuilder& pool, const std::v
 }
 
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
-                    const u64* omega_pp_in, const i64* mhatinv_in) {
+                    const u64* omega_pp_in, const i64* mhatinv_in, uint32_t flags) {
+  if (flags & ~(uint32_t)LOLHIP_PLAN_DENSE_GAUSS) return LOLHIP_ERR_INVALID;
+  P.flags = flags;
   if (!valid_pps(pps) || qs.empty() || qs.size() > 64) return LOLHIP_ERR_INVALID;
   for (u64 q : qs) if (q < 2 || q >= (1ull << 62)) return LOLHIP_ERR_MODULUS;
   P.pps = pps;
@@ -604,29 +607,46 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
   //   out[row] = (sum_{col=1}^{p-1} 2 c(row*col mod p) y[col-1]) / sqrt 2,
   //   c(k) = Re omega_p^k for col <= p/2, Im omega_p^k for col > p/2, omega_p = exp(2 pi i / p)
   // on every (p-1)-vector of axis k (lts * p^(e-1) blocks, stride rts: ppD, random.cpp:52-58).
+  // A plan created with LOLHIP_PLAN_DENSE_GAUSS runs an odd prime above 13 (every odd prime under the GAUSS_DENSE
+  // switch) as a dense stage out of a transposed copy, entry col * (p-1) + row, appended here; Stage::wp_off holds its
+  // offset (never 0: slot 0 is the constant 1).  Such a matrix takes (p-1)^2 doubles, so the primes stop below 2^15
+  // and, like every index of this path, at n <= 8192.
   {
     ProgBuilder pb;
     P.host_rconsts.assign(1, 1.0);
+    const bool opted = (flags & LOLHIP_PLAN_DENSE_GAUSS) != 0;
+    P.cplx_ok = P.n <= 8192;
+    P.gauss_route = P.n <= 8192 ? 1 : 0;
+    for (const auto& pe : pps) {
+      if (pe.p > 13) P.cplx_ok = false;
+      if (pe.p > 13 && !(opted && pe.p < (1 << 15))) P.gauss_route = 0;
+    }
     i64 rts = 1;
     for (int k = 0; k < K; ++k) {
       const int p = pps[(size_t)k].p, e = pps[(size_t)k].e;
       if (p != 2) {
-        const int off = (int)P.host_rconsts.size();
-        for (int row = 0; row < p - 1; ++row)
-          for (int col = 1; col <= p - 1; ++col) {
+        const int off = (int)P.host_rconsts.size(), d = p - 1;
+        for (int row = 0; row < d; ++row)
+          for (int col = 1; col <= d; ++col) {
             const double ang = 2.0 * M_PI * (double)((row * col) % p) / (double)p;
             P.host_rconsts.push_back(2.0 * (col <= (p >> 1) ? std::cos(ang) : std::sin(ang)));
           }
-        pb.dense(ST_GAUSS, p, p - 1, rts, 0);
+        pb.dense(ST_GAUSS, p, d, rts, 0);
         pb.st.back().mat_off = off;
+        if (P.gauss_route && opted && (p > 13 || sw(SW_GAUSS_DENSE))) {
+          const int offT = (int)P.host_rconsts.size();
+          P.host_rconsts.resize((size_t)offT + (size_t)d * d);
+          for (int row = 0; row < d; ++row)
+            for (int c = 0; c < d; ++c) P.host_rconsts[(size_t)offT + (size_t)c * d + row] = P.host_rconsts[(size_t)off + (size_t)row * d + c];
+          pb.st.back().wp_off = offT;
+          P.gauss_route = 2;
+        }
       }
       rts *= totient_pp(p, e);
     }
     finish(pb.st);
     P.prog_gauss.stages = pb.st;
   }
-  P.float_ok = P.n <= 8192;
-  for (const auto& pe : pps) if (pe.p > 13) P.float_ok = false;
 
   P.is_pow2 = P.has_crt && K == 1 && pps[0].p == 2 && pps[0].e >= 5 && pps[0].e <= 15;
   P.pow2_part = P.has_crt && K >= 2 && pps[0].p == 2 && pps[0].e >= 5 && pps[0].e <= 15;
@@ -684,6 +704,11 @@ int plan_upload(Plan& P) {
   for (auto* sp : progs) if ((rc = upload_prog(*sp))) return rc;
   if ((rc = P.d_cconsts.upload(P.host_cconsts))) return rc;
   if ((rc = P.d_rconsts.upload(P.host_rconsts))) return rc;
+  // the route word of launch_gauss (kernels.h): a dense stage runs with lanes along r where the stride fills a wave
+  for (size_t si = 0; si < P.prog_gauss.stages.size() && si < 12; ++si) {
+    const Stage& st = P.prog_gauss.stages[si];
+    if (st.wp_off) P.prog_gauss.nstages |= (st.rts >= 64 ? GAUSS_COLS : GAUSS_ROWS) << (8 + 2 * (int)si);
+  }
   if ((rc = P.d_gcrt.upload(P.gcrt))) return rc;
   if ((rc = P.d_ginvcrt.upload(P.ginvcrt))) return rc;
   if ((rc = P.d_lift.upload(P.lift_consts))) return rc;

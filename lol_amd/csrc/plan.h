@@ -44,7 +44,8 @@ struct Stage {
   int32_t p;        // prime
   int32_t d;        // vector length (p or p-1; 1 for DIAG/SCALE)
   int32_t rts;      // stride between vector elements
-  int32_t wp_off;   // offset (u64 units, per component) of omega_p^j table, j < p
+  int32_t wp_off;   // offset (u64 units, per component) of omega_p^j table, j < p; ST_GAUSS: offset of the transposed
+                    // matrix in the real pool when the stage takes the dense route (floatpath.hip), 0 for the register route
   int32_t tw_off;   // offset of diagonal table or -1
   int32_t tw_mod;   // diagonal index = (x / tw_div) % tw_mod
   int32_t tw_div;
@@ -139,7 +140,13 @@ struct Plan {
   std::vector<double> host_cconsts, host_rconsts;
   DevBuf<double> d_cconsts, d_rconsts;
   StageProgram prog_gauss;
-  bool float_ok = false;                    // n <= 8192 and every prime <= 13 (one LDS-resident polynomial, register vectors)
+  // one predicate per family (one LDS-resident polynomial each).  cplx_ok: n <= 8192 and every prime <= 13 (register
+  // vectors).  gauss_route: 0 refused; 1 n <= 8192 and register stages only (every odd prime <= 13); 2 n <= 8192, the
+  // plan was created with LOLHIP_PLAN_DENSE_GAUSS and an odd prime (below 2^15) takes the dense stage: a prime above
+  // 13, or every odd prime under the GAUSS_DENSE switch.  A function of (pps, flags, switch), so host-only plans have it.
+  uint32_t flags = 0;                       // LOLHIP_PLAN_* of lolhip_plan_create_flags
+  bool cplx_ok = false;
+  int gauss_route = 0;
   // Nothing in a plan is written after plan_upload(): per-call workspaces (the operand copy of the
   // unfused poly-mul, the HBM ping-pong ring of polynomials too large for LDS) are stream-ordered
   // allocations made by the call that needs them, so host threads and streams can share a plan.
@@ -158,13 +165,13 @@ struct ExtPlan {
 
 // plan.cpp
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
-                    const u64* omega_pp /* [npp*T] or null */, const i64* mhatinv /* [T] or null */);
+                    const u64* omega_pp /* [npp*T] or null */, const i64* mhatinv /* [T] or null */, uint32_t flags = 0);
 int plan_upload(Plan& P);
 
 // A/B switches of the launch paths (development and tests): read ONCE from the environment
 // (LOLHIP_<NAME>) into atomics; tests flip them through lolhip_debug_set, never through setenv
 // (getenv racing with setenv is undefined behaviour, and plans are used from concurrent threads).
-enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_COUNT };
+enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_COUNT };
 bool sw(Switch which);
 inline bool pow2_no_t1() { return sw(SW_NO_T1); }
 

@@ -23,8 +23,13 @@ inline bool two_power(const Plan& P) {
 // LOLHIP_OK when the sampler takes this index: a 2-power up to n' = 16384, else the limits of the Gaussian map
 inline int sampler_ok(const Plan& P) {
   if (two_power(P)) return P.n <= SAMPLER_POW2_MAX_N ? LOLHIP_OK : LOLHIP_ERR_INVALID;
-  return P.float_ok ? LOLHIP_OK : LOLHIP_ERR_INVALID;
+  return P.gauss_route ? LOLHIP_OK : LOLHIP_ERR_INVALID;
 }
+
+// The limit is a property of the plan's prime powers and flags alone, so the sampler entries that ask for the device
+// first (encrypt, errorRounded, ksHint) answer it before that: a host-only plan tells an index it will never take
+// (LOLHIP_ERR_INVALID) from one that only lacks a device.  A null plan is left to the caller's own check.
+inline int index_status(const lolhip_plan* p) { return p ? sampler_ok(p->P) : LOLHIP_OK; }
 
 // sigma = sqrt(v (m'/rad m') / 2 pi): the deviation of tGaussianDec v (scaled variance = 2 pi x variance,
 // GaussRandom.hs:27-44; CPP.hs:376-389)

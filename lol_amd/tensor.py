@@ -31,7 +31,7 @@ from ._abi import (  # noqa: F401  (the constants and types are part of this mod
     OK, ERR_INVALID, ERR_MODULUS, ERR_NO_CRT, ERR_ROOT, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_DIVISIBLE, ERR_DEVICE,
     OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC, OP_MULGCRT,
     OP_DIVGCRT, EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS,
-    ELT_I64, ELT_F64, ELT_C64, LolHipError, NoDeviceError, _PP, _i64p, _i32p, _check, _len, bind)
+    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, LolHipError, NoDeviceError, _PP, _i64p, _i32p, _check, _len, bind)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -296,13 +296,19 @@ class Plan(_Handle):
     list (CPP.hs:325-337) and the moduli (Backend.hs:195-199)."""
     _kind = "plan"
 
-    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None):
+    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False):
+        """dense_gauss: the Gaussian map (gaussianDec and every sampler behind it) also takes primes above 13, as dense
+        stages (LOLHIP_PLAN_DENSE_GAUSS; default roots only)."""
         self.pps, arr, npp = _pps(list(pps))
         self.qs = [int(q) for q in qs]
         self.host_only = bool(host_only)
         qa = (C.c_int64 * len(self.qs))(*self.qs)
         what = f"plan_create(pps={self.pps}, qs={self.qs})"
-        if omega_pp is None and mhatinv is None:
+        if dense_gauss:
+            if omega_pp is not None or mhatinv is not None:
+                raise ValueError("dense_gauss plans take the default roots")
+            self._create("plan_create_flags", arr, npp, qa, len(self.qs), int(host_only), PLAN_DENSE_GAUSS, what=what)
+        elif omega_pp is None and mhatinv is None:
             self._create("plan_create", arr, npp, qa, len(self.qs), int(host_only), what=what)
         else:
             om = None if omega_pp is None else (C.c_int64 * len(omega_pp))(*[int(v) for v in omega_pp])
@@ -313,6 +319,7 @@ class Plan(_Handle):
         self.m = int(L.lolhip_plan_m(h))
         self.T = int(L.lolhip_plan_T(h))
         self.has_crt = bool(L.lolhip_plan_has_crt(h))
+        self.dense_gauss = bool(dense_gauss)
 
     @classmethod
     def for_index(cls, m, qs, **kw):
@@ -332,6 +339,21 @@ class Plan(_Handle):
     def mhatInv(self): return self._table(2)
     def gCRT(self): return self._table(3).reshape(self.n, self.T)
     def gInvCRT(self): return self._table(4).reshape(self.n, self.T)
+
+    def gaussRoute(self):
+        """How gaussianDec runs on this plan: 0 refused, 1 register stages only, 2 with a dense stage."""
+        return int(lib().lolhip_plan_gauss_route(self._h))
+
+    def gaussTable(self, k, transposed=False):
+        """The (p-1) x (p-1) matrix of tensorGaussianDec for prime power k as the plan stores it: row-major, or the
+        transposed copy the dense stage reads (empty unless that prime takes the dense stage)."""
+        L = lib()
+        cnt = L.lolhip_plan_gauss_table(self._h, k, int(transposed), None, 0)
+        out = np.zeros(cnt, dtype=np.float64)
+        if cnt:
+            L.lolhip_plan_gauss_table(self._h, k, int(transposed), out.ctypes.data_as(C.POINTER(C.c_double)), cnt)
+        d = int(round(cnt ** 0.5))
+        return out.reshape(d, d)
 
     def liftConsts(self):
         """Constants of the lift to the integers (errorTerm / decrypt): dict of `pinv` [T] ((q_0...q_(i-1))^-1 mod q_i),

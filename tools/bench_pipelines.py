@@ -14,7 +14,8 @@ and of the key-homomorphic lattice PRF, matrix-core route against VALU route (`-
 profiles/lprf_bench.jsonl) and of RLWE / RLWR instances over moduli without a CRT basis, fused tails against the general
 composition (`--rlwe-ring`: that leg alone, also written to profiles/rlwe_ring_bench.jsonl) and of whole RLWE challenges,
 one grouped call against 32 single-secret calls (`--challenge`: that leg alone, also written to
-profiles/challenge_bench.jsonl).
+profiles/challenge_bench.jsonl) and of the Gaussian map at primes above 13, the dense stage against the register stage
+(`--gauss-dense`: that leg alone, also written to profiles/gauss_dense_bench.jsonl).
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -1253,8 +1254,98 @@ def ctmul_leg(gen):
         f.write("\n".join(lines) + "\n")
 
 
+def gauss_dense_leg(gen):
+    """The Gaussian map at a prime above 13 (k_gauss_dense, plans created with dense_gauss=True): gaussianDec at m = 179, 257,
+    797 and 2^9 17 on a slab of about 2^22 doubles, and RLWE.instances Disc at m = 257.  Two yardsticks from the same run,
+    at the index 13 2^k of nearest n: the register route (a default plan) and the dense route forced on that same index
+    (debug switch GAUSS_DENSE, read when the plan is built).  Three rounds, the routes alternating, ten timed calls each
+    after two warm-up calls; the median round, min and max beside it.  macs = B n sum (p - 1) over the odd primes, the
+    multiply-adds of the map; rated against the FP64 vector peak of 78.6 TFLOP/s = 3.93e13 multiply-adds/s.  `tile` is the
+    launcher's own line (LOLHIP_GAUSS_INFO).  Also written to profiles/gauss_dense_bench.jsonl."""
+    import statistics
+    import tempfile
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    FMA_PEAK = 78.6e12 / 2
+    lines = []
+
+    def plan(m, dense, forced=False):
+        if forced:
+            L.lolhip_debug_set(b"GAUSS_DENSE", 1)
+        try:
+            return lol_amd.Plan.for_index(m, [lol_amd.good_q(m, 2 ** 20)], dense_gauss=dense)
+        finally:
+            L.lolhip_debug_set(b"GAUSS_DENSE", 0)
+
+    def tile_of(call):
+        """the launcher's info line of one call (it goes to the C stderr)"""
+        sys.stderr.flush()
+        with tempfile.TemporaryFile() as f:
+            keep = os.dup(2)
+            os.environ["LOLHIP_GAUSS_INFO"] = "1"
+            os.dup2(f.fileno(), 2)
+            try:
+                call()
+                torch.cuda.synchronize()
+            finally:
+                os.dup2(keep, 2); os.close(keep)
+                del os.environ["LOLHIP_GAUSS_INFO"]
+            f.seek(0)
+            got = [ln for ln in f.read().decode().splitlines() if ln.startswith("k_gauss")]
+        return got[-1] if got else ""
+
+    def rounds(cases):
+        """cases: [(label, m, plan)] timed alternately; one JSON line each"""
+        slabs, calls = {}, {}
+        for label, m, P in cases:
+            B = max(64, 2 ** 22 // P.n)
+            src = torch.randn((B, P.n), dtype=torch.float64, device="cuda", generator=gen)
+            y = src.clone()
+            slabs[label] = (src, y, B)
+            calls[label] = (lambda P=P, y=y, B=B: L.lolhip_gaussian_dec_batch(P._h, st, y.data_ptr(), B))
+            assert calls[label]() == 0
+        ms = {label: [] for label, _, _ in cases}
+        for _ in range(3):
+            for label, _, _ in cases:
+                src, y, _ = slabs[label]
+                y.copy_(src)                       # in place: start every round from the same slab
+                ms[label].append(timeit(calls[label]))
+        for label, m, P in cases:
+            src, y, B = slabs[label]
+            y.copy_(src)
+            tile = tile_of(calls[label])
+            macs = B * P.n * sum(p - 1 for p, _ in P.pps if p != 2)
+            med = statistics.median(ms[label])
+            d = {"op": "gaussianDec", "route": label, "config": f"m={m} n={P.n} B={B}", "ms": round(med, 4),
+                 "ms_min": round(min(ms[label]), 4), "ms_max": round(max(ms[label]), 4), "macs": macs,
+                 "gmacs_per_s": round(macs / med / 1e6, 1), "frac_of_fp64_peak": round(macs / med * 1e3 / FMA_PEAK, 4),
+                 "alg_GBps": round(2 * B * P.n * 8 / med / 1e6, 1), "tile": tile}
+            lines.append(d)
+            print(json.dumps(d), flush=True)
+
+    # (index with a prime above 13, the index 13 2^k of nearest n)
+    for m, m13 in ((179, 13 * 2 ** 5), (257, 13 * 2 ** 6), (797, 13 * 2 ** 7), (2 ** 9 * 17, 13 * 2 ** 9)):
+        rounds([("dense", m, plan(m, True)), ("register", m13, plan(m13, False)), ("forced-dense", m13, plan(m13, True, forced=True))])
+    # whole Disc instances at m = 257: 32 secrets of 100 samples, as rlwe-challenges' lines ask
+    m, I, Ls = 257, 32, 100
+    r = lol_amd.RLWE(plan(m, True))
+    key = bytes(range(32))
+    ms = [timeit(lambda: r.instances("disc", I, Ls, svar=3.90625e-3, key=key, ctr_s=0, ctr=0), iters=5) for _ in range(3)]
+    med = statistics.median(ms)
+    d = {"op": "RLWE.instances", "route": "dense", "config": f"Disc m={m} q={r.plan.qs[0]} I={I} L={Ls}", "ms": round(med, 4),
+         "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "items_per_s": round(I * Ls / med * 1e3, 1)}
+    lines.append(d)
+    print(json.dumps(d), flush=True)
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gauss_dense_bench.jsonl")
+    with open(out, "w") as f:
+        f.write("".join(json.dumps(x) + "\n" for x in lines))
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--gauss-dense" in sys.argv:      # the dense Gaussian stage leg alone
+        gauss_dense_leg(gen)
+        return
     if "--challenge" in sys.argv:        # the whole-challenge leg alone
         challenge_leg(gen)
         return
