@@ -122,6 +122,44 @@ LOLHIP_API int lolhip_plan_gauss_route(const lolhip_plan *p);
  * (transposed != 0; empty unless that prime takes the dense stage).  Copies min(len, available) doubles and returns
  * the available count; 0 for p = 2 or a k out of range. */
 LOLHIP_API int64_t lolhip_plan_gauss_table(const lolhip_plan *p, int k, int transposed, double *out, int64_t len);
+/* lolhip_plan_create_flags with a route word.  A *flag* widens what a plan accepts; a *route* chooses among kernels
+ * that give the same bits, so a plan created with a route answers every call exactly as the plan without it does.
+ * routes = 0 is lolhip_plan_create_flags exactly; a bit that is not defined below answers LOLHIP_ERR_INVALID.
+ *   LOLHIP_ROUTE_DENSE_ZQ  the Z_q stage programs (crt, crtInv and what is composed of them: the poly-mul, RingMul,
+ *       the RLWE instances and challenges) run the stages of a prime above 13 as batched dense products out of an LDS
+ *       tile of polynomials instead of one scalar dot product per output element.  Taken when n <= 8192 and the
+ *       program about to be launched holds such a stage and at most 24 stages in all (every index of the reference's
+ *       range is far below that; a longer program keeps the scalar interpreter); every other launch of the plan is what
+ *       it was.  The cost is memory: per component and per such matrix the plan holds, on the host and on the device, a
+ *       transposed copy (8 d^2 bytes beside the 8 d^2 it had) and, where the moduli fit the matrix cores, W <= 4 int8
+ *       limb planes (W d'^2 bytes, d' = d rounded up to 32) - 15 MB per component for both directions at m = 797, about
+ *       1.6 GB at a prime index near 8192 (lolhip_plan_zq_table reads them back). */
+#define LOLHIP_ROUTE_DENSE_ZQ 1u
+LOLHIP_API int lolhip_plan_create_routes(const lolhip_pp *pps, int npps, const int64_t *qs, int T, int host_only,
+                                         uint32_t flags, uint32_t routes, lolhip_plan **out);
+/* Which kernel a Z_q transform of this plan launches.  what: 0 a lone crt, 1 a lone crtInv, 2 the poly-mul.
+ * Returns 0 for the launches of a plan without LOLHIP_ROUTE_DENSE_ZQ (whatever they are), 1 for the dense route on the
+ * vector ALU, 2 for the dense route on the matrix cores.  For what = 2 a value >= 1 means ONE launch; 0 means the
+ * poly-mul is composed of lone transforms, which may themselves be dense.  A function of the prime powers, the
+ * moduli, the route word and the debug switches (ZQ_DENSE_VALU, ZQ_DENSE_MFMA, GENERIC_SCALAR) only, so host-only
+ * plans answer it; 0 for a null plan.  Route 2 needs every modulus of the plan to fit W <= 4 balanced base-256 limbs
+ * after centring (floor(q/2) <= 127 (256^W - 1) / 255: q <= 65279, 16711423, 4278124287 for W = 2, 3, 4; one W per
+ * plan, the largest of its components) and a dense vector of at least 48 elements in the program: the vector ALU
+ * measured faster at 42 and below, the matrix cores at 52 and above.  The poly-mul (what = 2) takes one
+ * launch - both operands side by side in the LDS tile, the forward program over both, the pointwise product and the
+ * inverse program on the first; c may alias a or b and a may equal b - when the stage programs alone make the transform
+ * (no 2^e part, e >= 5, with kernels of its own), POLYMUL_UNFUSED is off, both programs take the dense route (route 2 only
+ * if both do), 4 n words fit 152 KiB of LDS (every n <= 8192 at 4-byte words, n <= 4864 at 8-byte words), and a 64 KiB
+ * tile leaves the inverse program, which runs on half of it, a whole register tile of columns (32 on the matrix cores,
+ * 8 / 4 on the vector ALU at 4- / 8-byte words); below that the composed form measured faster. */
+LOLHIP_API int lolhip_plan_zq_route(const lolhip_plan *p, int what);
+/* A dense stage's matrix as the device reads it (inspection, tests).  inverse: the lone crtInv's program, else the lone
+ * crt's; stage: index into that program (lolhip_plan_table 10 / 11); t: component.  limb = -1: the transposed word
+ * matrix of the vector-ALU route, d * d residues in [0, q_t), entry [c][row].  limb >= 0: that int8 limb plane of the
+ * matrix-core route, one int64 per entry, padded shape included.  Copies min(cap, available) values and returns the
+ * available count; 0 for a stage that is not dense on this plan, or a plane this plan does not hold. */
+LOLHIP_API int64_t lolhip_plan_zq_table(const lolhip_plan *p, int inverse, int stage, int t, int limb, int64_t *out,
+                                        int64_t cap);
 LOLHIP_API void lolhip_plan_destroy(lolhip_plan *p);
 
 LOLHIP_API int64_t lolhip_plan_n(const lolhip_plan *p);      /* totient(m) */
@@ -1200,7 +1238,7 @@ LOLHIP_API int64_t lolhip_chain_write(const uint8_t *const *elems, const int64_t
 LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_t bytes, int variant);
 
 /* Test and A/B aid, not part of the drop-in surface: force a launch path.  `name` is one of
- * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL, LPRF_VALU, RLWE_RING_UNFUSED and GAUSS_DENSE (read when a plan is built: every odd prime of a plan created with LOLHIP_PLAN_DENSE_GAUSS takes the dense stage of the Gaussian map) (each is
+ * GENERIC_SCALAR, NO_FUSED2, NO_POW2_PART, POLYMUL_UNFUSED, KEYSWITCH_UNFUSED, NO_T1, NO_PIPE, FORCE_PIPE, NO_OWN_DIAG, NO_MERGE, NO_KRON, NO_LAZY (these four read when a plan is built), NO_TRUNC, ELT_GLOBAL, LPRF_VALU, RLWE_RING_UNFUSED and GAUSS_DENSE (read when a plan is built: every odd prime of a plan created with LOLHIP_PLAN_DENSE_GAUSS takes the dense stage of the Gaussian map), and ZQ_DENSE_VALU (read at launch: a plan created with LOLHIP_ROUTE_DENSE_ZQ takes the vector-ALU form of its dense stages where it would take the matrix cores) and ZQ_DENSE_MFMA (read at launch: such a plan takes the matrix cores wherever its moduli fit, however short the dense vectors; ZQ_DENSE_VALU wins over it) (each is
  * also read ONCE at first use from the environment variable LOLHIP_<name>); value 0 restores the
  * default path.  Every path computes the same residues.  Returns LOLHIP_OK or LOLHIP_ERR_INVALID.
  * Two environment variables are test hooks of the persistent pipelined poly-mul, read at EVERY launch of it:
@@ -1211,7 +1249,14 @@ LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_
  *   LOLHIP_GAUSS_INFO     (set to anything) each launch prints one line to stderr naming the route of every stage:
  *                         "k_gauss: n <n>, B <B>, stages reg" for a program of register stages, else
  *                         "k_gauss_dense: n <n>, B <B>, items <I>, bufs <1|2>, lds <bytes> B, grid <G>, stages <route> ...",
- *                         route one of reg, dense-rows (lanes along the rows, stride < 64), dense-cols (lanes along r). */
+ *                         route one of reg, dense-rows (lanes along the rows, stride < 64), dense-cols (lanes along r).
+ * Two are read at every launch of the dense Z_q stages (plans created with LOLHIP_ROUTE_DENSE_ZQ):
+ *   LOLHIP_ZQ_DENSE_INFO  (set to anything) each launch prints one line to stderr:
+ *                         "k_zq_dense: route <r>, W <W>, n <n>, B <B>, T <T>, word <4|8>, items <I>, lds <bytes> B, grid <G>, polymul <0|1>, stages <kind> ...",
+ *                         kind one of elt (element-wise), dense-rows (lanes along the rows, stride < 64), dense-cols
+ *                         (lanes along r); the one-launch poly-mul lists the forward program, "*", the inverse program;
+ *   LOLHIP_ZQ_DENSE_GRID=<G>  the grid is G workgroups (at least 1) instead of one per (tile, component), so that a
+ *                         small batch exercises the grid-stride loop. */
 LOLHIP_API int lolhip_debug_set(const char *name, int value);
 
 /* number of HIP devices visible (0 without a GPU); never initialises a context */

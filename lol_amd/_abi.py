@@ -15,6 +15,7 @@ OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP
 EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS = range(6)
 ELT_I64, ELT_F64, ELT_C64 = range(3)
 PLAN_DENSE_GAUSS = 1
+ROUTE_DENSE_ZQ = 1
 
 
 class LolHipError(RuntimeError):
@@ -71,6 +72,9 @@ ABI = _rows(
     ("plan_create_flags", ci, pp, ci, _i64p, ci, ci, u32, vpp),
     ("plan_gauss_route", ci, vp),
     ("plan_gauss_table", i64, vp, ci, ci, f64p, i64),
+    ("plan_create_routes", ci, pp, ci, _i64p, ci, ci, u32, u32, vpp),
+    ("plan_zq_route", ci, vp, ci),
+    ("plan_zq_table", i64, vp, ci, ci, ci, ci, _i64p, i64),
     ("plan_destroy ext_destroy khprf_destroy tunnel_chain_destroy ptround_destroy pt_tunnel_destroy ringmul_destroy lprf_destroy", None, vp),
     ("plan_n plan_m", i64, vp),
     ("plan_T plan_has_crt", ci, vp),

@@ -26,7 +26,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._abi import _i64p, _len, _u8p
-from .tensor import RLWE, Plan, RingRLWE, lib
+from .tensor import RLWE, Plan, RingRLWE, factor_pps, lib
 
 EPS_DEF = 2.0 ** -25
 KINDS = ("Cont", "Disc", "RLWR")
@@ -174,10 +174,16 @@ def suppressed_secret_id(num_instances, beacon_byte):
 
 
 # ---- one challenge on the device ---------------------------------------------------------------------------------------------
+def large_prime(m):
+    """whether the index has a prime factor above 13: its Z_q transforms then take the dense route (Plan dense_zq)"""
+    return any(p > 13 for p, _ in factor_pps(m))
+
+
 def route(cp, host_only=True, dense_gauss=False):
     """("plan" | "ring", Plan): lolhip_plan_has_crt decides, as for the single-secret entries.  dense_gauss: the plan
-    opts in to the dense stage of the Gaussian map, which the error of a Cont or Disc challenge needs at a prime above 13"""
-    plan = Plan.for_index(cp.m, [cp.q], host_only=host_only, dense_gauss=dense_gauss)
+    opts in to the dense stage of the Gaussian map, which the error of a Cont or Disc challenge needs at a prime above 13.
+    At such an index the plan also routes its Z_q transforms (a s of every kind, RLWR included) to the dense stages."""
+    plan = Plan.for_index(cp.m, [cp.q], host_only=host_only, dense_gauss=dense_gauss, dense_zq=large_prime(cp.m))
     return ("plan" if plan.has_crt else "ring"), plan
 
 
@@ -330,7 +336,7 @@ class DeviceEngine:
     in to the dense stage of the Gaussian map (a Cont or Disc error at a prime above 13; nothing changes elsewhere)"""
 
     def __init__(self, m, q):
-        plan = Plan.for_index(m, [q], dense_gauss=True)
+        plan = Plan.for_index(m, [q], dense_gauss=True, dense_zq=large_prime(m))
         self.r = RLWE(plan) if plan.has_crt else RingRLWE(plan)
         self.n = plan.n
 

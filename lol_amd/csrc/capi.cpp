@@ -23,7 +23,7 @@ using namespace lolhip;
 namespace lolhip {
 namespace {
 const char* const kSwitchNames[SW_COUNT] = {"GENERIC_SCALAR", "NO_FUSED2", "NO_POW2_PART", "POLYMUL_UNFUSED",
-                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE"};
+                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE", "ZQ_DENSE_VALU", "ZQ_DENSE_MFMA"};
 std::atomic<int> g_switch[SW_COUNT];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -52,7 +52,7 @@ int device_count() {
 }
 
 int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const int64_t* omega_pp,
-              const int64_t* mhatinv, int host_only, lolhip_plan** out, uint32_t flags = 0) {
+              const int64_t* mhatinv, int host_only, lolhip_plan** out, uint32_t flags = 0, uint32_t routes = 0) {
   std::vector<PP> v;
   if (!out || T < 1 || !qs || !to_pps(pps, npps, v)) return LOLHIP_ERR_INVALID;
   *out = nullptr;
@@ -67,7 +67,7 @@ int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const in
     om.push_back((u64)(((omega_pp[i] % qq) + qq) % qq));
   }
   std::unique_ptr<lolhip_plan> p(new lolhip_plan());
-  int rc = plan_build_host(p->P, v, q, omega_pp ? om.data() : nullptr, mhatinv, flags);
+  int rc = plan_build_host(p->P, v, q, omega_pp ? om.data() : nullptr, mhatinv, flags, routes);
   if (rc != LOLHIP_OK) return rc;
   if (!host_only) {
     rc = plan_upload(p->P);
@@ -106,6 +106,41 @@ MixedLaunch mixed_launch(const Plan& P, hipStream_t s, int64_t* y, const int64_t
   m.consts = P.d_consts_mont ? P.d_consts_mont : P.d_consts; m.consts32 = P.d_consts32; m.cpc = P.consts_per_comp;
   m.mod = P.d_mod; m.cls = P.mixed_cls; m.fused = false;
   return m;
+}
+
+// Whether the launch of stage program sp takes the dense route (ZqDenseLaunch::route, kernels.h), and which.  ONE
+// decision, read by run_prog and by lolhip_plan_zq_route: the plan opted in (LOLHIP_ROUTE_DENSE_ZQ; plan_build_host
+// builds the copies for n <= 8192 only), GENERIC_SCALAR is off, the program would go to the scalar interpreter, and
+// it holds a stage of a prime above 13.
+constexpr int ZQ_MFMA_MIN_D = 48;
+int zq_dense_route(const Plan& P, const StageProgram& sp) {
+  if (!(P.routes & LOLHIP_ROUTE_DENSE_ZQ) || P.zq_mats.empty() || sw(SW_GENERIC_SCALAR)) return 0;
+  if (use_mixed(P, sp) || sp.stages.size() > (size_t)ZQ_MAX_STAGES) return 0;
+  int dmax = 0;
+  for (const Stage& st : sp.stages) if (zq_dense_stage(st) && st.d > dmax) dmax = st.d;
+  if (!dmax) return 0;
+  // the matrix cores where every modulus fits W <= 4 balanced limbs (Plan::zq_W) and the longest dense vector is worth
+  // a 32-deep unit (ZQ_MFMA_MIN_D, measured: DESIGN.md 3.4q), else the vector ALU
+  // (ZQ_DENSE_MFMA lifts the length condition, ZQ_DENSE_VALU wins over it: tests and measurements)
+  return (P.zq_W && (dmax >= ZQ_MFMA_MIN_D || sw(SW_ZQ_DENSE_MFMA)) && !sw(SW_ZQ_DENSE_VALU)) ? 2 : 1;
+}
+const ZqDenseMat* zq_mat_of(const Plan& P, const Stage& st) {
+  if (zq_dense_stage(st)) for (const ZqDenseMat& zm : P.zq_mats) if (zm.mat_off == st.mat_off) return &zm;
+  return nullptr;
+}
+
+// the per-stage fields of ZqDenseLaunch for program sp, written from slot `at` on; the longest dense vector goes to dmax
+void zq_fill(const Plan& P, const StageProgram& sp, size_t at, ZqDenseLaunch& z) {
+  z.W = P.zq_W; z.fold = P.zq_fold;
+  z.mt = P.d_zq_mt; z.mtpc = P.zq_mt_per_comp;
+  z.planes = P.d_zq_planes; z.plpc = P.zq_pl_per_comp;
+  for (size_t i = 0; i < sp.stages.size(); ++i) {
+    const Stage& st = sp.stages[i];
+    const ZqDenseMat* zm = zq_mat_of(P, st);
+    if (zm && st.d > z.dmax) z.dmax = st.d;
+    z.kind[at + i] = !zm ? ZQ_ELT : st.rts >= 64 ? ZQ_COLS : ZQ_ROWS;
+    z.mt_off[at + i] = zm ? zm->mt_off : -1; z.dp[at + i] = zm ? zm->dp : 0; z.pl_off[at + i] = zm ? zm->pl_off : -1;
+  }
 }
 
 bool q_below(const Plan& P, int bits) {
@@ -164,6 +199,12 @@ int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, i
   }
   a.q32 = true;
   for (u64 q : P.qs) if (q >= ((u64)1 << 32)) a.q32 = false;
+  a.zq.route = zq_dense_route(P, sp);
+  if (a.zq.route) {                     // the dense kernels read src themselves
+    zq_fill(P, sp, 0, a.zq);
+    a.zq.src = (src && src != y) ? src : nullptr;
+    return hip_status(launch_generic(a));
+  }
   if (src && src != y) {                // the scalar interpreter works in place
     if (hipMemcpyAsync(y, src, sizeof(int64_t) * (size_t)(B * P.n * P.T), hipMemcpyDeviceToDevice, s) != hipSuccess) return LOLHIP_ERR_HIP;
   }
@@ -208,6 +249,32 @@ bool polymul_one_launch(const Plan& P) {
 // lolhip_polymul_batch and for lolhip_plan_table 13 / 14
 const StageProgram& polymul_prog(const Plan& P, bool inverse) {
   return use_fused2(P) ? fused_crt(P, inverse) : zq_crt(P, inverse);
+}
+
+// The poly-mul of an opted-in plan as ONE launch of the dense kernels (zqdense.hip): both operands side by side in the
+// LDS tile, the forward program over both, the pointwise product and the inverse program on the first.  Taken when the
+// stage programs alone make the transform (no 2-power part with kernels of its own), both take the dense route, they
+// hold at most ZQ_MAX_STAGES stages together, and 4 n words (two operands, two ping-pong buffers) fit the LDS budget:
+// every n <= 8192 at 4-byte words, n <= 4864 at 8-byte words; and the inverse program, which runs on half the tile, still
+// has a whole register tile of columns to work on in a 64 KiB tile (32 columns on the matrix cores, 8 / 4 on the vector
+// ALU at 4- / 8-byte words): below that the composed form measured faster.  Returns the route (the vector ALU unless both programs
+// take the matrix cores) or 0: composed of lone transforms.  ONE decision, for lolhip_polymul_batch and
+// lolhip_plan_zq_route(p, 2).
+int zq_polymul_route(const Plan& P) {
+  if (P.is_pow2 || !P.has_crt || sw(SW_POLYMUL_UNFUSED) || polymul_one_launch(P)) return 0;
+  if (P.pow2_part && !sw(SW_NO_POW2_PART)) return 0;
+  const StageProgram& pf = zq_crt(P, false);
+  const StageProgram& pi = zq_crt(P, true);
+  const int rf = zq_dense_route(P, pf), ri = zq_dense_route(P, pi);
+  if (!rf || !ri || pf.stages.size() + pi.stages.size() > (size_t)ZQ_MAX_STAGES) return 0;
+  const size_t per = 4 * (size_t)P.n * (q_below(P, 32) ? 4 : 8);
+  if (per > ZQ_LDS_BUDGET) return 0;
+  const int route = rf == 2 && ri == 2 ? 2 : 1;
+  int dmax = 0;
+  for (const StageProgram* sp : {&pf, &pi}) for (const Stage& st : sp->stages) if (zq_dense_stage(st) && st.d > dmax) dmax = st.d;
+  const size_t items = 64 * 1024 / per > 0 ? 64 * 1024 / per : 1;
+  const size_t want = route == 2 ? 32 : q_below(P, 32) ? 8 : 4;
+  return items * (size_t)(P.n / dmax) >= want ? route : 0;
 }
 
 // crt / crtInv of B polynomials through whichever path the plan has (crt_route)
@@ -287,6 +354,37 @@ int lolhip_plan_create_roots(const lolhip_pp* pps, int npps, const int64_t* qs, 
 int lolhip_plan_create_flags(const lolhip_pp* pps, int npps, const int64_t* qs, int T, int host_only, uint32_t flags,
                              lolhip_plan** out) {
   return make_plan(pps, npps, qs, T, nullptr, nullptr, host_only, out, flags);
+}
+int lolhip_plan_create_routes(const lolhip_pp* pps, int npps, const int64_t* qs, int T, int host_only, uint32_t flags,
+                              uint32_t routes, lolhip_plan** out) {
+  return make_plan(pps, npps, qs, T, nullptr, nullptr, host_only, out, flags, routes);
+}
+int lolhip_plan_zq_route(const lolhip_plan* p, int what) {
+  if (!p || what < 0 || what > 2) return 0;
+  if (what == 2) return zq_polymul_route(p->P);
+  const CrtRoute r = crt_route(p->P);
+  return r == ROUTE_POW2 ? 0 : zq_dense_route(p->P, crt_route_prog(p->P, r, what == 1));
+}
+int64_t lolhip_plan_zq_table(const lolhip_plan* p, int inverse, int stage, int t, int limb, int64_t* out, int64_t cap) {
+  if (!p || t < 0 || t >= p->P.T || stage < 0 || limb < -1) return 0;
+  const Plan& P = p->P;
+  const CrtRoute r = crt_route(P);
+  if (r == ROUTE_POW2) return 0;
+  const StageProgram& sp = crt_route_prog(P, r, inverse != 0);
+  if (stage >= (int)sp.stages.size() || !zq_dense_route(P, sp)) return 0;
+  const ZqDenseMat* zm = zq_mat_of(P, sp.stages[(size_t)stage]);
+  if (!zm) return 0;
+  if (limb < 0) {
+    const int64_t avail = (int64_t)zm->d * zm->d;
+    const u64* src = P.host_zq_mt.data() + (size_t)t * P.zq_mt_per_comp + zm->mt_off;
+    for (int64_t i = 0; out && i < cap && i < avail; ++i) out[i] = (int64_t)src[i];
+    return avail;
+  }
+  if (limb >= P.zq_W || zm->pl_off < 0) return 0;
+  const int64_t avail = (int64_t)zm->dp * zm->dp;
+  const int8_t* src = P.host_zq_planes.data() + (size_t)t * P.zq_pl_per_comp + zm->pl_off + (size_t)limb * avail;
+  for (int64_t i = 0; out && i < cap && i < avail; ++i) out[i] = src[i];
+  return avail;
 }
 int lolhip_plan_gauss_route(const lolhip_plan* p) { return p ? p->P.gauss_route : 0; }
 int64_t lolhip_plan_gauss_table(const lolhip_plan* p, int k, int transposed, double* out, int64_t len) {
@@ -381,6 +479,23 @@ int lolhip_polymul_batch(const lolhip_plan* p, void* stream, int64_t* c, const i
     MixedLaunch m = mixed_launch(P, s, c, a, B, pf);
     m.b = b; m.st_b = pi.d_stages; m.n_b = pi.nstages; m.fused = true; m.big = pf.big || pi.big;
     return hip_status(launch_mixed(m));
+  }
+  if (const int zr = zq_polymul_route(P)) {
+    // one launch of the dense kernels: a and b side by side in the tile, 3 slab passes (zqdense.hip)
+    const StageProgram& pf = zq_crt(P, false);
+    const StageProgram& pi = zq_crt(P, true);
+    GenericLaunch g;
+    g.stream = s; g.y = c; g.B = B; g.T = P.T; g.n = P.n;
+    g.stages = pf.d_stages; g.nstages = pf.nstages;
+    g.consts = P.d_consts; g.cpc = P.consts_per_comp; g.mod = P.d_mod;
+    g.scratch = nullptr; g.scratch_bytes = 0;
+    g.q32 = q_below(P, 32);
+    g.zq.route = zr;
+    zq_fill(P, pf, 0, g.zq);
+    zq_fill(P, pi, pf.stages.size(), g.zq);
+    g.zq.src = a != c ? a : nullptr;
+    g.zq.b = b; g.zq.stages_inv = pi.d_stages; g.zq.nstages_inv = pi.nstages;
+    return hip_status(launch_generic(g));
   }
   // otherwise: crt(a) -> c, crt(b) -> temp, multiply, crtInv.  c may alias a or b.  The temp is a
   // stream-ordered allocation of this call (the pool recycles it: no device synchronisation).

@@ -47,6 +47,36 @@ struct KeySwitchLaunch {
 };
 hipError_t launch_keyswitch_fused(const KeySwitchLaunch& a);
 
+// The dense route of a stage program at primes above 13 (zqdense.hip; plans created with LOLHIP_ROUTE_DENSE_ZQ).  It rides
+// in GenericLaunch, so the host translation units reference no launcher of its own: launch_generic dispatches on `route`.
+constexpr int ZQ_MAX_STAGES = 24;
+constexpr size_t ZQ_LDS_BUDGET = 152 * 1024;      // dynamic LDS of a workgroup: what launch_generic requests for k_generic
+// element-wise on the tile (the arithmetic of k_generic); dense with lanes along the output rows (stride below a wave);
+// dense with lanes along r (stride of at least a wave)
+enum ZqStageKind : uint8_t { ZQ_ELT = 0, ZQ_ROWS = 1, ZQ_COLS = 2 };
+struct ZqDenseLaunch {
+  int route = 0;                 // 0: k_generic (everything below unused); 1: dense stages on the vector ALU; 2: on the matrix cores
+  int W = 0;                     // route 2: balanced base-256 limbs per residue (2..4)
+  int dmax = 0;                  // route 2: the longest dense vector of the program(s) (tile sizing)
+  int fold = 0;                  // every modulus < 2^32: products a 64-bit accumulator takes between folds (Plan::zq_fold)
+  const i64* src = nullptr;      // input slab when it is not y (null: in place)
+  // one-launch poly-mul: y = crtInv(crt(src or y) * crt(b)).  The tile holds both operands side by side as twice the
+  // columns; GenericLaunch::stages is the forward program, stages_inv the inverse one, run on the pointwise product
+  const i64* b = nullptr;
+  const Stage* stages_inv = nullptr;
+  int nstages_inv = 0;
+  const u64* mt = nullptr;       // transposed word matrices [T][mtpc] (Plan::d_zq_mt)
+  i64 mtpc = 0;
+  const int8_t* planes = nullptr;      // limb planes [T][plpc] bytes (Plan::d_zq_planes), route 2
+  i64 plpc = 0;
+  // per stage of the program (the one-launch poly-mul: of `stages`, then of `stages_inv`): how it runs (the host decides, the kernel and the info line obey), the
+  // offset into mt / planes of its dense copies and the padded size of a plane (mt_off -1 for an element-wise stage)
+  uint8_t kind[ZQ_MAX_STAGES];   // ZqStageKind
+  int32_t mt_off[ZQ_MAX_STAGES];
+  int32_t dp[ZQ_MAX_STAGES];
+  i64 pl_off[ZQ_MAX_STAGES];
+};
+
 struct GenericLaunch {
   hipStream_t stream;
   i64* y;
@@ -61,8 +91,10 @@ struct GenericLaunch {
   u64* scratch;
   size_t scratch_bytes;
   bool q32;          // every modulus < 2^32: 32-bit operand products in the dot-product stages
+  ZqDenseLaunch zq;  // route 0 unless the plan opted in and the program holds a dense stage of a prime above 13
 };
 hipError_t launch_generic(const GenericLaunch& a);
+hipError_t launch_zq_dense(const GenericLaunch& a);   // zqdense.hip; called by launch_generic only
 
 // vector-per-thread interpreter + fused mixed-radix poly-mul (mixed.hip); every prime <= 13, n <= 8192
 struct MixedLaunch {

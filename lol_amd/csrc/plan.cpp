@@ -305,9 +305,11 @@ static bool merge_stages(std::vector<Stage>& st, PoolBuilder& pool, const std::v
 }
 
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
-                    const u64* omega_pp_in, const i64* mhatinv_in, uint32_t flags) {
+                    const u64* omega_pp_in, const i64* mhatinv_in, uint32_t flags, uint32_t routes) {
   if (flags & ~(uint32_t)LOLHIP_PLAN_DENSE_GAUSS) return LOLHIP_ERR_INVALID;
+  if (routes & ~(uint32_t)LOLHIP_ROUTE_DENSE_ZQ) return LOLHIP_ERR_INVALID;
   P.flags = flags;
+  P.routes = routes;
   if (!valid_pps(pps) || qs.empty() || qs.size() > 64) return LOLHIP_ERR_INVALID;
   for (u64 q : qs) if (q < 2 || q >= (1ull << 62)) return LOLHIP_ERR_MODULUS;
   P.pps = pps;
@@ -677,6 +679,78 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
     for (u64 q : P.qs) if (q >= ((u64)1 << 27)) below27 = false;
     if (below27) P.mixed_cls = 4;
   }
+
+  // ---- dense Z_q stages at primes above 13 (LOLHIP_ROUTE_DENSE_ZQ; zqdense.hip) ---------------------------------
+  // One transposed copy per distinct matrix, entry c * d + row, residues in [0, q): a lane per output row then reads
+  // consecutive words.  Every program a launch may hand to the scalar interpreter is scanned, so a stage finds its
+  // copy by its mat_off whichever program it sits in.  Only opted-in plans with n <= 8192 build them.
+  P.zq_mats.clear(); P.host_zq_mt.clear(); P.host_zq_planes.clear();
+  P.zq_mt_per_comp = P.zq_pl_per_comp = 0; P.zq_W = P.zq_fold = 0;
+  if ((routes & LOLHIP_ROUTE_DENSE_ZQ) && P.has_crt && P.n <= 8192) {
+    // W: the least number of balanced base-256 limbs that hold every centred residue, floor(q/2) <= 127 (256^W - 1) / 255
+    int W = 2;
+    for (u64 q : P.qs) {
+      int w = 1;
+      u128 top = 127;
+      while (top < (u128)(q / 2)) { top = top * 256 + 127; ++w; }
+      if (w > W) W = w;
+    }
+    P.zq_W = W <= 4 ? W : 0;
+    if (fits32) {
+      u64 fold = (u64)1 << 20;
+      for (u64 q : P.qs) {
+        const u128 sq = (u128)(q - 1) * (q - 1);
+        const u128 f = sq ? (((u128)~(u64)0 - (q - 1)) / sq) : fold;
+        if (f < fold) fold = (u64)f;
+      }
+      P.zq_fold = (int)fold;      // >= 1: (q-1) + (q-1)^2 < 2^64 for q <= 2^32
+    }
+    std::vector<std::vector<u64>> mt((size_t)T);
+    std::vector<std::vector<int8_t>> pl((size_t)T);
+    const StageProgram* scan[] = {&P.prog_crt, &P.prog_crtinv, &P.prog_crt_odd, &P.prog_crtinv_odd, &P.prog_crt_mg,
+                                  &P.prog_crtinv_mg, &P.prog_crt_mg_big, &P.prog_crtinv_mg_big};
+    for (const StageProgram* sp : scan)
+      for (const Stage& s : sp->stages) {
+        if (!zq_dense_stage(s)) continue;
+        bool seen = false;
+        for (const ZqDenseMat& zm : P.zq_mats) if (zm.mat_off == s.mat_off) seen = true;
+        if (seen) continue;
+        ZqDenseMat zm;
+        zm.mat_off = s.mat_off; zm.d = s.d; zm.dp = (s.d + 31) / 32 * 32;
+        zm.mt_off = (int32_t)mt[0].size();
+        zm.pl_off = P.zq_W ? (int64_t)pl[0].size() : -1;
+        const size_t d = (size_t)s.d, dp = (size_t)zm.dp;
+        for (int t = 0; t < T; ++t) {
+          const u64 q = qs[(size_t)t];
+          const u64* M = P.host_consts.data() + (size_t)t * P.consts_per_comp + s.mat_off;
+          std::vector<u64>& o = mt[(size_t)t];
+          o.resize((size_t)zm.mt_off + d * d);
+          for (size_t row = 0; row < d; ++row)
+            for (size_t c = 0; c < d; ++c) o[(size_t)zm.mt_off + c * d + row] = M[row * d + c] % q;
+          if (!P.zq_W) continue;
+          // W int8 planes [dp][dp] of the centred matrix, row-major, rows and depth zero padded
+          std::vector<int8_t>& b = pl[(size_t)t];
+          b.resize((size_t)zm.pl_off + (size_t)P.zq_W * dp * dp, 0);
+          for (size_t row = 0; row < d; ++row)
+            for (size_t c = 0; c < d; ++c) {
+              const u64 r = M[row * d + c] % q;
+              i64 v = r > q / 2 ? (i64)r - (i64)q : (i64)r;
+              for (int w = 0; w < P.zq_W; ++w) {
+                const i64 l = ((v + 128) & 255) - 128;
+                b[(size_t)zm.pl_off + ((size_t)w * dp + row) * dp + c] = (int8_t)l;
+                v = (v - l) / 256;
+              }
+              if (v != 0) return LOLHIP_ERR_INVALID;     // W limbs hold every centred residue: a bug, not a status
+            }
+        }
+        P.zq_mats.push_back(zm);
+      }
+    P.zq_mt_per_comp = (i64)mt[0].size(); P.zq_pl_per_comp = (i64)pl[0].size();
+    for (int t = 0; t < T; ++t) {
+      P.host_zq_mt.insert(P.host_zq_mt.end(), mt[(size_t)t].begin(), mt[(size_t)t].end());
+      P.host_zq_planes.insert(P.host_zq_planes.end(), pl[(size_t)t].begin(), pl[(size_t)t].end());
+    }
+  }
   return LOLHIP_OK;
 }
 
@@ -704,6 +778,8 @@ int plan_upload(Plan& P) {
   for (auto* sp : progs) if ((rc = upload_prog(*sp))) return rc;
   if ((rc = P.d_cconsts.upload(P.host_cconsts))) return rc;
   if ((rc = P.d_rconsts.upload(P.host_rconsts))) return rc;
+  if (!P.host_zq_mt.empty() && (rc = P.d_zq_mt.upload(P.host_zq_mt))) return rc;
+  if (!P.host_zq_planes.empty() && (rc = P.d_zq_planes.upload(P.host_zq_planes))) return rc;
   // the route word of launch_gauss (kernels.h): a dense stage runs with lanes along r where the stride fills a wave
   for (size_t si = 0; si < P.prog_gauss.stages.size() && si < 12; ++si) {
     const Stage& st = P.prog_gauss.stages[si];

@@ -78,6 +78,17 @@ struct Pow2Tables {
   int arith32 = 0;                 // 4: every q_t < 2^27; 2: < 2^30; 3: < 2^31; 0: no 32-bit tables
 };
 
+// One dense matrix of a prime above 13 as the dense Z_q stages read it (zqdense.hip; plans created with
+// LOLHIP_ROUTE_DENSE_ZQ only): every stage of any program whose mat_off is `mat_off` takes these copies.
+//   mt_off  offset (u64 units, per component, into host_zq_mt) of the transposed word matrix [d][d], residues in [0, q)
+//   pl_off  offset (bytes, per component, into host_zq_planes) of the first of W int8 limb planes [dp][dp], dp = d
+//           rounded up to a multiple of 32, zero padded: sum_w 256^w plane_w = the centred residue; -1: no planes
+struct ZqDenseMat { int32_t mat_off, d, dp, mt_off; int64_t pl_off; };
+// the stages the dense route runs as matrix products: a DFT_p / CRT_p / CRT_p^-1 of a prime above 13
+inline bool zq_dense_stage(const Stage& s) {
+  return (s.kind == ST_DFTP || s.kind == ST_CRTP || s.kind == ST_CRTPINV) && s.p > 13;
+}
+
 struct Plan {
   std::vector<PP> pps;
   int T = 0;
@@ -145,6 +156,18 @@ struct Plan {
   // plan was created with LOLHIP_PLAN_DENSE_GAUSS and an odd prime (below 2^15) takes the dense stage: a prime above
   // 13, or every odd prime under the GAUSS_DENSE switch.  A function of (pps, flags, switch), so host-only plans have it.
   uint32_t flags = 0;                       // LOLHIP_PLAN_* of lolhip_plan_create_flags
+  // dense Z_q stages at primes above 13 (lolhip_plan_create_routes, LOLHIP_ROUTE_DENSE_ZQ).  Built by plan_build_host for
+  // opted-in plans with n <= 8192 only; empty otherwise.  zq_W: limbs of the matrix-core form (2..4), 0 when a modulus
+  // is too wide for it.  zq_fold: how many products of two residues a 64-bit accumulator that starts below q takes
+  // before it has to be folded (every modulus below 2^32), 0 otherwise.
+  uint32_t routes = 0;
+  std::vector<ZqDenseMat> zq_mats;
+  std::vector<u64> host_zq_mt;              // [T][zq_mt_per_comp]
+  std::vector<int8_t> host_zq_planes;       // [T][zq_pl_per_comp]
+  i64 zq_mt_per_comp = 0, zq_pl_per_comp = 0;
+  int zq_W = 0, zq_fold = 0;
+  DevBuf<u64> d_zq_mt;
+  DevBuf<int8_t> d_zq_planes;
   bool cplx_ok = false;
   int gauss_route = 0;
   // Nothing in a plan is written after plan_upload(): per-call workspaces (the operand copy of the
@@ -165,13 +188,13 @@ struct ExtPlan {
 
 // plan.cpp
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
-                    const u64* omega_pp /* [npp*T] or null */, const i64* mhatinv /* [T] or null */, uint32_t flags = 0);
+                    const u64* omega_pp /* [npp*T] or null */, const i64* mhatinv /* [T] or null */, uint32_t flags = 0, uint32_t routes = 0);
 int plan_upload(Plan& P);
 
 // A/B switches of the launch paths (development and tests): read ONCE from the environment
 // (LOLHIP_<NAME>) into atomics; tests flip them through lolhip_debug_set, never through setenv
 // (getenv racing with setenv is undefined behaviour, and plans are used from concurrent threads).
-enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_COUNT };
+enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_ZQ_DENSE_VALU, SW_ZQ_DENSE_MFMA, SW_COUNT };
 bool sw(Switch which);
 inline bool pow2_no_t1() { return sw(SW_NO_T1); }
 

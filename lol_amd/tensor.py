@@ -31,7 +31,7 @@ from ._abi import (  # noqa: F401  (the constants and types are part of this mod
     OK, ERR_INVALID, ERR_MODULUS, ERR_NO_CRT, ERR_ROOT, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_DIVISIBLE, ERR_DEVICE,
     OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC, OP_MULGCRT,
     OP_DIVGCRT, EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS,
-    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, LolHipError, NoDeviceError, _PP, _i64p, _i32p, _check, _len, bind)
+    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, ROUTE_DENSE_ZQ, LolHipError, NoDeviceError, _PP, _i64p, _i32p, _check, _len, bind)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -296,15 +296,22 @@ class Plan(_Handle):
     list (CPP.hs:325-337) and the moduli (Backend.hs:195-199)."""
     _kind = "plan"
 
-    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False):
+    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False, dense_zq=False):
         """dense_gauss: the Gaussian map (gaussianDec and every sampler behind it) also takes primes above 13, as dense
-        stages (LOLHIP_PLAN_DENSE_GAUSS; default roots only)."""
+        stages (LOLHIP_PLAN_DENSE_GAUSS; default roots only).  dense_zq: crt, crtInv and what is composed of them run the
+        stages of a prime above 13 as dense products out of an LDS tile (LOLHIP_ROUTE_DENSE_ZQ; default roots only): the
+        same residues from another kernel.  The two compose."""
         self.pps, arr, npp = _pps(list(pps))
         self.qs = [int(q) for q in qs]
         self.host_only = bool(host_only)
         qa = (C.c_int64 * len(self.qs))(*self.qs)
         what = f"plan_create(pps={self.pps}, qs={self.qs})"
-        if dense_gauss:
+        if dense_zq:
+            if omega_pp is not None or mhatinv is not None:
+                raise ValueError("dense_zq plans take the default roots")
+            self._create("plan_create_routes", arr, npp, qa, len(self.qs), int(host_only),
+                         PLAN_DENSE_GAUSS if dense_gauss else 0, ROUTE_DENSE_ZQ, what=what)
+        elif dense_gauss:
             if omega_pp is not None or mhatinv is not None:
                 raise ValueError("dense_gauss plans take the default roots")
             self._create("plan_create_flags", arr, npp, qa, len(self.qs), int(host_only), PLAN_DENSE_GAUSS, what=what)
@@ -320,6 +327,7 @@ class Plan(_Handle):
         self.T = int(L.lolhip_plan_T(h))
         self.has_crt = bool(L.lolhip_plan_has_crt(h))
         self.dense_gauss = bool(dense_gauss)
+        self.dense_zq = bool(dense_zq)
 
     @classmethod
     def for_index(cls, m, qs, **kw):
@@ -352,6 +360,24 @@ class Plan(_Handle):
         out = np.zeros(cnt, dtype=np.float64)
         if cnt:
             L.lolhip_plan_gauss_table(self._h, k, int(transposed), out.ctypes.data_as(C.POINTER(C.c_double)), cnt)
+        d = int(round(cnt ** 0.5))
+        return out.reshape(d, d)
+
+    def zqRoute(self, what=0):
+        """Which kernel a lone crt (what=0), a lone crtInv (1) or the poly-mul (2) launches: 0 what a plan without dense_zq
+        launches, 1 the dense stages on the vector ALU, 2 on the matrix cores.  For the poly-mul 0 also means composed of
+        lone transforms, which may themselves be dense."""
+        return int(lib().lolhip_plan_zq_route(self._h, int(what)))
+
+    def zqTable(self, stage, t=0, limb=-1, inverse=False):
+        """A dense stage's matrix as the device reads it, for stage `stage` of program(inverse) and component t: the
+        transposed word matrix [d][d] (limb=-1) or int8 limb plane `limb`, padded shape included.  Empty for a stage that
+        is not dense on this plan."""
+        L = lib()
+        cnt = L.lolhip_plan_zq_table(self._h, int(inverse), int(stage), int(t), int(limb), None, 0)
+        out = np.zeros(cnt, dtype=np.int64)
+        if cnt:
+            L.lolhip_plan_zq_table(self._h, int(inverse), int(stage), int(t), int(limb), out.ctypes.data_as(_i64p), cnt)
         d = int(round(cnt ** 0.5))
         return out.reshape(d, d)
 
@@ -1180,9 +1206,11 @@ class RingMul(_WorkHandle):
     (taken mod q_t), results lie in [0, q_t)."""
     _kind = "ringmul"
 
-    def __init__(self, plan_q, plan_Q=None):
+    def __init__(self, plan_q, plan_Q=None, dense_zq=None):
+        """dense_zq: passed to the plan_Q made here (None: what plan_q has)"""
         if plan_Q is None:
-            plan_Q = Plan(plan_q.pps, self.moduli(plan_q.pps, plan_q.qs), host_only=plan_q.host_only)
+            plan_Q = Plan(plan_q.pps, self.moduli(plan_q.pps, plan_q.qs), host_only=plan_q.host_only,
+                          dense_zq=plan_q.dense_zq if dense_zq is None else dense_zq)
         self.plan_q, self.plan_Q = plan_q, plan_Q
         self.n, self.T, self.K = plan_q.n, plan_q.T, plan_Q.T
         self._create("ringmul_create", plan_q._h, plan_Q._h)

@@ -16,6 +16,7 @@ composition (`--rlwe-ring`: that leg alone, also written to profiles/rlwe_ring_b
 one grouped call against 32 single-secret calls (`--challenge`: that leg alone, also written to
 profiles/challenge_bench.jsonl) and of the Gaussian map at primes above 13, the dense stage against the register stage
 (`--gauss-dense`: that leg alone, also written to profiles/gauss_dense_bench.jsonl).
+`--zq-dense`: the dense Z_q stages at primes above 13 alone, also written to profiles/zq_dense_bench.jsonl.
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -1341,8 +1342,132 @@ def gauss_dense_leg(gen):
         f.write("".join(json.dumps(x) + "\n" for x in lines))
 
 
+def zq_dense_leg(gen):
+    """The dense Z_q stages at a prime above 13 (zqdense.hip, plans created with dense_zq=True): crt, crtInv and the
+    poly-mul on slabs of about 2^22 words at m = 179, 257 and 797 (a list modulus with a CRT basis each, and the NTT prime
+    RingMul picks for a list modulus without one), at 2^9 17, at the short vectors 17 .. 97 that decide where the matrix
+    cores start, and at the index 13 2^k of nearest n for scale.  Per case four routes of the same parameters alternate
+    in one process: the opted-in plan as it routes itself (`dense`), the same plan on the vector ALU (switch
+    ZQ_DENSE_VALU), on the matrix cores whatever the vector length (ZQ_DENSE_MFMA, where the moduli fit), and a default
+    plan (`scalar`: the launches of a plan without the route); where the poly-mul takes one launch, also the same plan
+    with the poly-mul composed of its dense transforms (`composed`, switch POLYMUL_UNFUSED).  Three rounds, ten timed calls each after two warm-up
+    calls; the median round with min and max beside it.  macs = B n T sum d over the dense stages.  `tile` is the launcher's
+    own line (LOLHIP_ZQ_DENSE_INFO).  Then RLWE.instances Disc at m = 257, q = 1056271, 32 x 100, dense against default.
+    Also written to profiles/zq_dense_bench.jsonl."""
+    import statistics
+    import tempfile
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    lines = []
+
+    def tile_of(call):
+        sys.stderr.flush()
+        with tempfile.TemporaryFile() as f:
+            keep = os.dup(2)
+            os.environ["LOLHIP_ZQ_DENSE_INFO"] = "1"
+            os.dup2(f.fileno(), 2)
+            try:
+                call()
+                torch.cuda.synchronize()
+            finally:
+                os.dup2(keep, 2); os.close(keep)
+                del os.environ["LOLHIP_ZQ_DENSE_INFO"]
+            f.seek(0)
+            got = [ln for ln in f.read().decode().splitlines() if ln.startswith("k_zq_dense")]
+        return got[0] if got else ""
+
+    def case(m, qs, note):
+        pps = lol_amd.factor_pps(m)
+        P, D = lol_amd.Plan(pps, qs, dense_zq=True), lol_amd.Plan(pps, qs)
+        B = max(8, 2 ** 22 // (P.n * P.T))
+        a, b = rnd(gen, qs, B, P.n), rnd(gen, qs, B, P.n)
+        y, c = a.clone(), torch.empty_like(a)
+        ops = {"crt": lambda Q: L.lolhip_crt_batch(Q._h, st, y.data_ptr(), B),
+               "crtInv": lambda Q: L.lolhip_crtinv_batch(Q._h, st, y.data_ptr(), B),
+               "polymul": lambda Q: L.lolhip_polymul_batch(Q._h, st, c.data_ptr(), a.data_ptr(), b.data_ptr(), B)}
+        routes = [("dense", P, None), ("valu", P, b"ZQ_DENSE_VALU"), ("mfma", P, b"ZQ_DENSE_MFMA"), ("scalar", D, None)]
+        one_launch = P.zqRoute(2) > 0        # then also the poly-mul composed of the plan's dense transforms (POLYMUL_UNFUSED)
+        if P.zqRoute(0) == 0:
+            routes = routes[-1:]
+        else:
+            L.lolhip_debug_set(b"ZQ_DENSE_MFMA", 1)
+            can_mfma = P.zqRoute(0) == 2
+            L.lolhip_debug_set(b"ZQ_DENSE_MFMA", 0)
+            if not can_mfma:
+                routes = [r for r in routes if r[0] != "mfma"]
+        dsum = sum(int(s[2]) for s in P.program() if s[0] in (1, 2, 3) and s[1] > 13)
+        for op, fn in ops.items():
+            routes = [r for r in routes if r[0] != "composed"]
+            if op == "polymul" and one_launch:
+                routes = routes[:1] + [("composed", P, b"POLYMUL_UNFUSED")] + routes[1:]
+            ms = {r[0]: [] for r in routes}
+            tiles, which = {}, {}
+
+            def run(label, Q, sw):
+                if sw:
+                    L.lolhip_debug_set(sw, 1)
+                try:
+                    which[label] = Q.zqRoute(0)
+                    assert fn(Q) == 0
+                    if label not in tiles:
+                        tiles[label] = tile_of(lambda: fn(Q))
+                    return timeit(lambda: fn(Q))
+                finally:
+                    if sw:
+                        L.lolhip_debug_set(sw, 0)
+            for _ in range(3):
+                for label, Q, sw in routes:
+                    y.copy_(a)
+                    ms[label].append(run(label, Q, sw))
+            for label, Q, sw in routes:
+                med = statistics.median(ms[label])
+                macs = B * P.n * P.T * dsum * (3 if op == "polymul" else 1)
+                d = {"op": op, "route": label, "zq_route": which[label], "one_launch": bool(op == "polymul" and one_launch and label not in ("composed", "scalar")), "config": f"m={m} n={P.n} qs={qs} B={B}", "note": note,
+                     "ms": round(med, 4), "ms_min": round(min(ms[label]), 4), "ms_max": round(max(ms[label]), 4),
+                     "gmacs_per_s": round(macs / med / 1e6, 1), "alg_GBps": round(2 * B * P.n * P.T * 8 / med / 1e6, 1),
+                     "tile": tiles[label]}
+                lines.append(d)
+                print(json.dumps(d), flush=True)
+
+    ntt = lambda m, q: [int(v) for v in lol_amd.RingMul.moduli(lol_amd.factor_pps(m), [q])]
+    case(179, [8382929], "list modulus, W = 3")
+    case(179, ntt(179, 65536), "NTT primes of RingMul for q = 65536")
+    case(257, [15802417], "list modulus, W = 3")
+    case(257, ntt(257, 131072), "NTT primes of RingMul for q = 131072")
+    case(797, [741587779], "list modulus, W = 4")
+    case(797, [44633], "list modulus, W = 2")
+    case(797, ntt(797, 65536), "NTT primes of RingMul for q = 65536")
+    case(2 ** 9 * 17, [lol_amd.good_q(2 ** 9 * 17, 2 ** 20)], "split route, odd part d = 16 at stride 256")
+    for m in (17, 31, 37, 43, 53, 61, 67, 97, 323):
+        case(m, [lol_amd.good_q(m, 2 ** 20)], "short vectors: where the matrix cores start")
+    for m13 in (13 * 2 ** 5, 13 * 2 ** 6, 13 * 2 ** 7):
+        case(m13, [lol_amd.good_q(m13, 2 ** 20)], "scale: the vector interpreter at the nearest n")
+    # whole Disc instances at m = 257: 32 secrets of 100 samples, as rlwe-challenges' lines ask
+    m, q, I, Ls = 257, 1056271, 32, 100
+    key = bytes(range(32))
+    rs = {"dense": lol_amd.RLWE(lol_amd.Plan.for_index(m, [q], dense_gauss=True, dense_zq=True)),
+          "scalar": lol_amd.RLWE(lol_amd.Plan.for_index(m, [q], dense_gauss=True))}
+    ms = {k: [] for k in rs}
+    for _ in range(3):
+        for k, r in rs.items():
+            ms[k].append(timeit(lambda: r.instances("disc", I, Ls, svar=3.90625e-3, key=key, ctr_s=0, ctr=0), iters=5))
+    for k, r in rs.items():
+        med = statistics.median(ms[k])
+        d = {"op": "RLWE.instances", "route": k, "zq_route": r.plan.zqRoute(0), "config": f"Disc m={m} q={q} I={I} L={Ls}",
+             "ms": round(med, 4), "ms_min": round(min(ms[k]), 4), "ms_max": round(max(ms[k]), 4),
+             "items_per_s": round(I * Ls / med * 1e3, 1)}
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "zq_dense_bench.jsonl")
+    with open(out, "w") as f:
+        f.write("".join(json.dumps(x) + "\n" for x in lines))
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--zq-dense" in sys.argv:         # the dense Z_q stages leg alone
+        zq_dense_leg(gen)
+        return
     if "--gauss-dense" in sys.argv:      # the dense Gaussian stage leg alone
         gauss_dense_leg(gen)
         return
