@@ -160,6 +160,37 @@ LOLHIP_API int lolhip_plan_zq_route(const lolhip_plan *p, int what);
  * available count; 0 for a stage that is not dense on this plan, or a plane this plan does not hold. */
 LOLHIP_API int64_t lolhip_plan_zq_table(const lolhip_plan *p, int inverse, int stage, int t, int limb, int64_t *out,
                                         int64_t cap);
+/* The creator with an options block: what lolhip_plan_create_routes takes, in a struct that carries its own size, so a
+ * later option is a new bit or a new field and not another creator.  size must be sizeof(lolhip_plan_opts); a flag or
+ * route bit that is not defined answers LOLHIP_ERR_INVALID.  Without LOLHIP_PLAN_DENSE_CPLX the plan is exactly the one
+ * lolhip_plan_create_routes(flags, routes) builds.  Default roots only.
+ *   LOLHIP_PLAN_DENSE_CPLX  (this creator only; lolhip_plan_create_flags / _routes refuse the bit)  crtc / crtinvc take
+ *       indices with a prime above 13: the stages of such a prime (DFT_p, CRT_p, CRT_p^-1) run as batched dense complex
+ *       products out of an LDS tile of polynomials, on the FP64 matrix cores (v_mfma_f64_16x16x4_f64; where the vector has
+ *       at least 16 elements and a 64 KiB tile holds at least 16 of them, measured: DESIGN.md 3.4r) or the vector ALU,
+ *       in the same launch as the register stages of the primes up to 13.  Accepted: every prime <= 1021, at most 12
+ *       stages per program, and 16 n bytes (the one dense stage is the last stage of both programs: 2^e p up to
+ *       n = 8192) or 32 n bytes (otherwise: every n <= 4864, so every n <= 4096 and 32 17 19) within 152 KiB of LDS.
+ *       Everything else keeps the answer of a default plan.  The cost is memory: per dense matrix a transposed copy and
+ *       three real planes, 40 d^2 bytes beside the 16 d^2 it had (84 MB for both directions at p = 1021).  A plan
+ *       without the flag launches what it always did. */
+typedef struct { uint32_t size; uint32_t flags; uint32_t routes; } lolhip_plan_opts;
+#define LOLHIP_PLAN_DENSE_CPLX 2u
+LOLHIP_API int lolhip_plan_create_opts(const lolhip_pp *pps, int npps, const int64_t *qs, int T, int host_only,
+                                       const lolhip_plan_opts *opts, lolhip_plan **out);
+/* How lolhip_crtc_batch / lolhip_crtinvc_batch run on this plan: 0 refused (LOLHIP_ERR_INVALID), 1 register stages only
+ * (n <= 8192, every prime <= 13), 2 at least one dense stage (see LOLHIP_PLAN_DENSE_CPLX).  A function of the prime
+ * powers, the flag and two debug switches read when the plan is built (CPLX_DENSE: every odd prime of an opted-in plan
+ * is dense; CPLX_DENSE_VALU: no stage takes the matrix cores), so host-only plans answer it; 0 for a null plan. */
+LOLHIP_API int lolhip_plan_cplx_route(const lolhip_plan *p);
+/* A dense stage's matrix in the extra forms the device reads (inspection, tests).  inverse: crtinvc's program, else
+ * crtc's; stage: index into it (the stage list is lolhip_plan_table 20 / 21's).  form 0: the transposed copy,
+ * d * d complex entries [c][row], (re, im) interleaved: 2 d^2 doubles.  form 1, 2, 3: the planes M_re, M_im, -M_im of
+ * the matrix route, row-major [d rounded up to 16][d rounded up to 4], zero padded (the device holds the same planes
+ * tile by tile in lane order).  Copies min(cap, available) doubles and returns the available count; 0 for a stage
+ * that is not dense on this plan. */
+LOLHIP_API int64_t lolhip_plan_cplx_table(const lolhip_plan *p, int inverse, int stage, int form, double *out,
+                                          int64_t cap);
 LOLHIP_API void lolhip_plan_destroy(lolhip_plan *p);
 
 LOLHIP_API int64_t lolhip_plan_n(const lolhip_plan *p);      /* totient(m) */
@@ -177,6 +208,9 @@ LOLHIP_API int lolhip_plan_has_crt(const lolhip_plan *p);
  *          where the 2-power factor goes through the m = 2^k kernels, the whole stage program otherwise
  *          13 / 14 (inspection, tests): the forward / inverse program of a poly-mul that runs as one launch of the
  *          vector interpreter, same four values per stage; empty when the poly-mul is composed of lone transforms
+ *          20 / 21 (inspection, tests): the stage program of crtc / crtinvc, five values per stage: kind, prime, vector
+ *          length, stride and route (0 register stage or diagonal, 1 dense on the vector ALU, 2 dense on the matrix
+ *          cores; the launcher's LOLHIP_CPLX_INFO line prints the same); empty when lolhip_plan_cplx_route is 0
  *          12 (inspection, tests): the lift constants of errorTerm / decrypt, [T + T*T + T]: (q_0 ... q_{i-1})^-1
  *          mod q_i (1 for i = 0); q_j mod q_i at [T + i*T + j]; the mixed-radix digits of floor((Q-1)/2),
  *          Q = prod q_t, least significant first                                  */
@@ -216,7 +250,9 @@ LOLHIP_API int lolhip_divgcrt_batch(const lolhip_plan *p, void *stream, int64_t 
  *   doubles, on entry iid real Gaussians, on exit the sample in the decoding basis (the caller
  *   draws and scales the Gaussians and rounds the result, as cDispatchGaussian does).
  * Both need n <= 8192 and every prime of m <= 13, else LOLHIP_ERR_INVALID.  On a plan created with
- * LOLHIP_PLAN_DENSE_GAUSS, gaussian_dec takes every prime below 2^15 (n <= 8192 still); crtc / crtinvc do not. */
+ * LOLHIP_PLAN_DENSE_GAUSS, gaussian_dec takes every prime below 2^15 (n <= 8192 still); on a plan created with
+ * LOLHIP_PLAN_DENSE_CPLX (lolhip_plan_create_opts), crtc / crtinvc take primes up to 1021 within the LDS rule stated
+ * there (lolhip_plan_cplx_route says which indices). */
 LOLHIP_API int lolhip_crtc_batch        (const lolhip_plan *p, void *stream, double *y, int64_t B);
 LOLHIP_API int lolhip_crtinvc_batch     (const lolhip_plan *p, void *stream, double *y, int64_t B);
 LOLHIP_API int lolhip_gaussian_dec_batch(const lolhip_plan *p, void *stream, double *y, int64_t B);

@@ -16,6 +16,7 @@ EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EX
 ELT_I64, ELT_F64, ELT_C64 = range(3)
 PLAN_DENSE_GAUSS = 1
 ROUTE_DENSE_ZQ = 1
+PLAN_DENSE_CPLX = 2          # honoured by lolhip_plan_create_opts only
 
 
 class LolHipError(RuntimeError):
@@ -43,6 +44,11 @@ def _len(rc, what=""):
 
 class _PP(C.Structure):
     _fields_ = [("prime", C.c_int16), ("exponent", C.c_int16)]
+
+
+class _PlanOpts(C.Structure):
+    """lolhip_plan_opts"""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("routes", C.c_uint32)]
 
 
 _i64p = C.POINTER(C.c_int64)
@@ -73,6 +79,9 @@ ABI = _rows(
     ("plan_gauss_route", ci, vp),
     ("plan_gauss_table", i64, vp, ci, ci, f64p, i64),
     ("plan_create_routes", ci, pp, ci, _i64p, ci, ci, u32, u32, vpp),
+    ("plan_create_opts", ci, pp, ci, _i64p, ci, ci, C.POINTER(_PlanOpts), vpp),
+    ("plan_cplx_route", ci, vp),
+    ("plan_cplx_table", i64, vp, ci, ci, ci, f64p, i64),
     ("plan_zq_route", ci, vp, ci),
     ("plan_zq_table", i64, vp, ci, ci, ci, ci, _i64p, i64),
     ("plan_destroy ext_destroy khprf_destroy tunnel_chain_destroy ptround_destroy pt_tunnel_destroy ringmul_destroy lprf_destroy", None, vp),

@@ -23,7 +23,7 @@ using namespace lolhip;
 namespace lolhip {
 namespace {
 const char* const kSwitchNames[SW_COUNT] = {"GENERIC_SCALAR", "NO_FUSED2", "NO_POW2_PART", "POLYMUL_UNFUSED",
-                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE", "ZQ_DENSE_VALU", "ZQ_DENSE_MFMA"};
+                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE", "ZQ_DENSE_VALU", "ZQ_DENSE_MFMA", "CPLX_DENSE", "CPLX_DENSE_VALU"};
 std::atomic<int> g_switch[SW_COUNT];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -52,9 +52,10 @@ int device_count() {
 }
 
 int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const int64_t* omega_pp,
-              const int64_t* mhatinv, int host_only, lolhip_plan** out, uint32_t flags = 0, uint32_t routes = 0) {
+              const int64_t* mhatinv, int host_only, lolhip_plan** out, uint32_t flags = 0, uint32_t routes = 0,
+              uint32_t known_flags = LOLHIP_PLAN_DENSE_GAUSS) {      // the flag bits the calling creator honours
   std::vector<PP> v;
-  if (!out || T < 1 || !qs || !to_pps(pps, npps, v)) return LOLHIP_ERR_INVALID;
+  if (!out || T < 1 || !qs || !to_pps(pps, npps, v) || (flags & ~known_flags)) return LOLHIP_ERR_INVALID;
   *out = nullptr;
   std::vector<u64> q;
   for (int t = 0; t < T; ++t) {
@@ -359,6 +360,27 @@ int lolhip_plan_create_routes(const lolhip_pp* pps, int npps, const int64_t* qs,
                               uint32_t routes, lolhip_plan** out) {
   return make_plan(pps, npps, qs, T, nullptr, nullptr, host_only, out, flags, routes);
 }
+int lolhip_plan_create_opts(const lolhip_pp* pps, int npps, const int64_t* qs, int T, int host_only, const lolhip_plan_opts* opts,
+                            lolhip_plan** out) {
+  if (out) *out = nullptr;
+  if (!opts || opts->size != sizeof(lolhip_plan_opts)) return LOLHIP_ERR_INVALID;
+  return make_plan(pps, npps, qs, T, nullptr, nullptr, host_only, out, opts->flags, opts->routes,
+                   LOLHIP_PLAN_DENSE_GAUSS | LOLHIP_PLAN_DENSE_CPLX);
+}
+int lolhip_plan_cplx_route(const lolhip_plan* p) { return p ? p->P.cplx_route : 0; }
+int64_t lolhip_plan_cplx_table(const lolhip_plan* p, int inverse, int stage, int form, double* out, int64_t cap) {
+  if (!p || p->P.cplx_route != 2 || stage < 0 || form < 0 || form > 3) return 0;
+  const Plan& P = p->P;
+  const std::vector<Stage>& st = P.prog_crtc[inverse ? 1 : 0].stages;
+  if (stage >= (int)st.size() || cplx_stage_route(P.cplx_word[inverse ? 1 : 0], stage) == CPLX_REG) return 0;
+  const Stage& s = st[(size_t)stage];
+  if (s.kind == ST_DIAG || s.kind == ST_SCALE) return 0;
+  const int64_t d = s.d, dpr = (d + 15) / 16 * 16, dpc = (d + 3) / 4 * 4;
+  const int64_t avail = form == 0 ? 2 * d * d : dpr * dpc;
+  const double* src = P.host_cconsts.data() + (form == 0 ? 2 * (int64_t)s.wp_off : (int64_t)s.pad[0] + (form - 1) * dpr * dpc);
+  if (out && cap > 0) std::memcpy(out, src, sizeof(double) * (size_t)(cap < avail ? cap : avail));
+  return avail;
+}
 int lolhip_plan_zq_route(const lolhip_plan* p, int what) {
   if (!p || what < 0 || what > 2) return 0;
   if (what == 2) return zq_polymul_route(p->P);
@@ -424,6 +446,18 @@ int64_t lolhip_plan_table(const lolhip_plan* p, int which, int k, int64_t* out, 
       if (which <= 11) sp = &crt_route_prog(P, crt_route(P), inv);
       else if (polymul_one_launch(P)) sp = &polymul_prog(P, inv);
       if (sp) for (const Stage& st : sp->stages) { tmp.push_back(st.kind); tmp.push_back(st.p); tmp.push_back(st.d); tmp.push_back(st.rts); }
+      src = &tmp;
+      break;
+    }
+    case 20: case 21: {      // the stage program of crtc (20) / crtinvc (21), five values per stage, the route last
+      const int dir = which - 20;
+      if (P.cplx_route) {
+        const std::vector<Stage>& st = (dir ? P.prog_crtinv : P.prog_crt).stages;
+        for (size_t i = 0; i < st.size(); ++i) {
+          tmp.push_back(st[i].kind); tmp.push_back(st[i].p); tmp.push_back(st[i].d); tmp.push_back(st[i].rts);
+          tmp.push_back(P.cplx_route == 2 ? cplx_stage_route(P.cplx_word[dir], (int)i) : 0);
+        }
+      }
       src = &tmp;
       break;
     }
@@ -563,20 +597,24 @@ int lolhip_divgcrt_batch(const lolhip_plan* p, void* stream, int64_t* y, int64_t
 
 static int cplx_ready(const lolhip_plan* p) {
   int rc = need_device(p); if (rc) return rc;
-  return p->P.cplx_ok ? LOLHIP_OK : LOLHIP_ERR_INVALID;       // n > 8192 or a prime > 13
+  return p->P.cplx_route ? LOLHIP_OK : LOLHIP_ERR_INVALID;    // n > 8192, or a prime > 13 on a plan that has not opted in
+}
+// the program and stage word of crtC / crtInvC: the plan's own stage list on k_cplx, or the copy with the offsets of the
+// dense forms on k_cplx_dense (Plan::cplx_route)
+static int run_cplx(const Plan& P, void* stream, double* y, int64_t B, int dir) {
+  const StageProgram& sp = P.cplx_route == 2 ? P.prog_crtc[dir] : (dir ? P.prog_crtinv : P.prog_crt);
+  const int word = P.cplx_route == 2 ? P.cplx_word[dir] : sp.nstages;
+  return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, sp.d_stages, word, P.d_cconsts));
 }
 int lolhip_crtc_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
   int rc = cplx_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
-  const Plan& P = p->P;
-  return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crt.d_stages, P.prog_crt.nstages, P.d_cconsts));
+  return run_cplx(p->P, stream, y, B, 0);
 }
 int lolhip_crtinvc_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
   int rc = cplx_ready(p); if (rc) return rc;
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
-  const Plan& P = p->P;
-  return hip_status(launch_cplx((hipStream_t)stream, y, B, P.n, P.prog_crtinv.d_stages, P.prog_crtinv.nstages,
-                                P.d_cconsts));
+  return run_cplx(p->P, stream, y, B, 1);
 }
 int lolhip_gaussian_dec_batch(const lolhip_plan* p, void* stream, double* y, int64_t B) {
   int rc = need_device(p); if (rc) return rc;

@@ -17,6 +17,11 @@
 // no longer fits one thread, so the stage is a batched dense product out of LDS: a workgroup holds a tile of items
 // (polynomials), and every (p-1)-vector of the tile (item, block, r) is a column.  Same accumulator, same order of
 // summation and the same fused multiply-add as the register stage, so both routes give the same bits.
+//
+// tensorCRTC / tensorCRTInvC at a prime above 13 (plans created with LOLHIP_PLAN_DENSE_CPLX): k_cplx_dense.  The same tile
+// of items, over C: the DFT_p, CRT_p and CRT_p^-1 stages of such a prime are batched dense complex products, on the FP64
+// matrix cores or on the vector ALU (the route of every stage rides in the stage word: kernels.h), between the register
+// stages of the small primes, in one launch.  Tolerance contract, so each route sums in its own order.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -92,7 +97,7 @@ k_cplx(cd* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages, int n
             case 11: cplx_stage_vec<11>(st, buf, vec, cst); break;
             case 12: cplx_stage_vec<12>(st, buf, vec, cst); break;
             case 13: cplx_stage_vec<13>(st, buf, vec, cst); break;
-            default: break;   // excluded on the host (Plan::cplx_ok)
+            default: break;   // excluded on the host (Plan::cplx_route)
           }
         }
       }
@@ -280,17 +285,250 @@ k_gauss_dense(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ st
   }
 }
 
+// ---- dense stages of tensorCRTC / tensorCRTInvC -------------------------------------------------
+// out[col, row] = tw(row) * sum_c M[row][c] v[col, c] over the columns col = (item, blk, r) of the tile, as for the
+// Gaussian map above, over C: a DFT_p (d = p), CRT_p or CRT_p^-1 (d = p - 1) of a prime no register vector holds.  src
+// is the LDS tile; dst is the other LDS buffer or, for the last stage of the program, the slab.  The contract of this
+// path is a tolerance, not a bit pattern (include/lolhip.h), so the order of summation is each route's own.
+constexpr int CD_J = 4;          // register tile of the vector-ALU routes: 4 complex accumulators per thread
+
+// column col of the tile: tile-relative (base) and polynomial-relative (loc) position of its element 0
+__device__ __forceinline__ void cplx_col(const Stage& st, int col, int n, int nq, u64 m_nq, int& base, int& loc) {
+  const int item = fdiv40(col, m_nq), q = col - item * nq;
+  const int blk = fdiv40(q, st.m_rts), r = q - blk * st.rts;
+  loc = blk * st.d * st.rts + r;
+  base = item * n + loc;
+}
+// entry of the stage's folded diagonal at position x of the polynomial (as cplx_stage_vec applies it)
+__device__ __forceinline__ cd cplx_tw(const Stage& st, const cd* __restrict__ cst, int x) {
+  const int xd = fdiv40(x, st.m_twdiv);
+  return cst[st.tw_off + xd - fdiv40(xd, st.m_twmod) * st.tw_mod];
+}
+__device__ __forceinline__ void cplx_fma(cd& acc, cd m, cd v) {
+  acc.re = fma(m.re, v.re, fma(-m.im, v.im, acc.re));
+  acc.im = fma(m.re, v.im, fma(m.im, v.re, acc.im));
+}
+
+// Vector ALU, lanes along the rows (stride below a wave): a thread owns one output row across CD_J columns; the matrix
+// element comes from the transposed copy (consecutive lanes, consecutive entries).
+__device__ __forceinline__ void cplx_dense_rows(const Stage& st, const cd* __restrict__ src, cd* __restrict__ dst, int n, int items,
+                                                const cd* __restrict__ cst) {
+  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq, ngroups = (ncols + CD_J - 1) / CD_J;
+  const u64 m_nq = magic40_dev(nq);
+  const cd* __restrict__ Mt = cst + st.wp_off;
+  for (int w = threadIdx.x; w < d * ngroups; w += blockDim.x) {
+    const int cg = fdiv40(w, st.m_d), row = w - cg * d;
+    int base[CD_J], loc[CD_J];
+    cd acc[CD_J];
+#pragma unroll
+    for (int j = 0; j < CD_J; ++j) {
+      const int col = cg * CD_J + j;
+      cplx_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq, base[j], loc[j]);       // a dead column re-reads the last live one
+      acc[j] = cd{0.0, 0.0};
+    }
+    for (int c = 0; c < d; ++c) {
+      const cd m = Mt[c * d + row];
+#pragma unroll
+      for (int j = 0; j < CD_J; ++j) cplx_fma(acc[j], m, src[base[j] + c * rts]);
+    }
+#pragma unroll
+    for (int j = 0; j < CD_J; ++j)
+      if (cg * CD_J + j < ncols) {
+        cd o = acc[j];
+        if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc[j] + row * rts));
+        dst[base[j] + row * rts] = o;
+      }
+  }
+}
+
+// Vector ALU, lanes along r (stride of at least a wave): a wave owns CD_J rows of 64 consecutive columns; the matrix
+// elements are wave-uniform.
+__device__ __forceinline__ void cplx_dense_cols(const Stage& st, const cd* __restrict__ src, cd* __restrict__ dst, int n, int items,
+                                                const cd* __restrict__ cst) {
+  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq;
+  const int nrg = (d + CD_J - 1) / CD_J, nchunks = (ncols + 63) >> 6;
+  const u64 m_nq = magic40_dev(nq);
+  const cd* __restrict__ M = cst + st.mat_off;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  const int nwaves = (int)(blockDim.x >> 6);
+  for (int wi = wave; wi < nrg * nchunks; wi += nwaves) {
+    const int rg = wi / nchunks, chunk = wi - rg * nchunks, row0 = rg * CD_J;
+    const int col = chunk * 64 + lane;
+    int base, loc;
+    cplx_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq, base, loc);
+    int moff[CD_J];
+    cd acc[CD_J];
+#pragma unroll
+    for (int j = 0; j < CD_J; ++j) {
+      moff[j] = (row0 + j < d ? row0 + j : d - 1) * d;                                // a dead row re-reads the last live one
+      acc[j] = cd{0.0, 0.0};
+    }
+    for (int c = 0; c < d; ++c) {
+      const cd v = src[base + c * rts];
+#pragma unroll
+      for (int j = 0; j < CD_J; ++j) cplx_fma(acc[j], M[moff[j] + c], v);
+    }
+    if (col < ncols) {
+#pragma unroll
+      for (int j = 0; j < CD_J; ++j)
+        if (row0 + j < d) {
+          cd o = acc[j];
+          if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc + (row0 + j) * rts));
+          dst[base + (row0 + j) * rts] = o;
+        }
+    }
+  }
+}
+
+// Matrix cores: v_mfma_f64_16x16x4_f64, D (16 x 16) += A (16 x 4) B (4 x 16).  Lane l holds A[l & 15][l >> 4],
+// B[l >> 4][l & 15] and D[(l >> 4) + 4 reg][l & 15], reg < 4.  One complex product is four real ones:
+//   out_re = M_re v_re + (-M_im) v_im,   out_im = M_im v_re + M_re v_im,
+// from the planes M_re, M_im, -M_im (rows padded to 16, depth to 4 with zeros; tile by tile in lane order, plan.cpp
+// plan_upload), so the inner loop is three plane loads, one 16-byte LDS read per column tile and four MFMAs per column
+// tile.  A wave owns 16 rows of CM_CT tiles of 16 columns.  Lane l feeds matrix entry [row l & 15][depth l >> 4] and the
+// element of depth l >> 4 of column l & 15 either way round:
+//   stride >= 16  A = M, B = V: lane l gets rows (l >> 4) + 4 reg of column l & 15 - consecutive lanes, consecutive r;
+//   stride < 16   A = V^T, B = M^T: lane l gets row l & 15 of columns (l >> 4) + 4 reg - consecutive lanes, consecutive
+//                 rows, which at stride 1 are consecutive words.
+// A depth past d re-reads element d - 1 against a zero of the plane; a column past the tile re-reads the last live one
+// and is not stored.
+typedef double cplx_d4 __attribute__((ext_vector_type(4)));
+constexpr int CM_CT = 2;
+
+__device__ __forceinline__ void cplx_dense_mfma(const Stage& st, const cd* __restrict__ src, cd* __restrict__ dst, int n, int items,
+                                                const cd* __restrict__ cst) {
+  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq;
+  const int nrt = (d + 15) >> 4, nks = (d + 3) >> 2;
+  const int nct = (ncols + 15) >> 4, ncg = (nct + CM_CT - 1) / CM_CT;
+  const u64 m_nq = magic40_dev(nq);
+  const size_t plane = (size_t)nrt * nks * 64;
+  const double* __restrict__ pl = reinterpret_cast<const double*>(cst) + st.pad[0];
+  const bool tr = rts < 16;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
+  const int nwaves = (int)(blockDim.x >> 6);
+  const int li = lane & 15, lk = lane >> 4;
+  for (int wi = wave; wi < nrt * ncg; wi += nwaves) {
+    const int rt = wi / ncg, cg = wi - rt * ncg;
+    int base[CM_CT];
+    cplx_d4 are[CM_CT], aim[CM_CT];
+#pragma unroll
+    for (int t = 0; t < CM_CT; ++t) {
+      const int col = (cg * CM_CT + t) * 16 + li;
+      int loc;
+      cplx_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq, base[t], loc);
+      are[t] = cplx_d4{0.0, 0.0, 0.0, 0.0};
+      aim[t] = cplx_d4{0.0, 0.0, 0.0, 0.0};
+    }
+    const double* __restrict__ pr = pl + (size_t)rt * nks * 64 + lane;
+    for (int ks = 0; ks < nks; ++ks) {
+      const double mre = pr[(size_t)ks * 64], mim = pr[plane + (size_t)ks * 64], mni = pr[2 * plane + (size_t)ks * 64];
+      int c = ks * 4 + lk;
+      if (c > d - 1) c = d - 1;
+#pragma unroll
+      for (int t = 0; t < CM_CT; ++t) {
+        const cd v = src[base[t] + c * rts];
+        if (!tr) {
+          are[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(mre, v.re, are[t], 0, 0, 0);
+          are[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(mni, v.im, are[t], 0, 0, 0);
+          aim[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(mim, v.re, aim[t], 0, 0, 0);
+          aim[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(mre, v.im, aim[t], 0, 0, 0);
+        } else {
+          are[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.re, mre, are[t], 0, 0, 0);
+          are[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.im, mni, are[t], 0, 0, 0);
+          aim[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.re, mim, aim[t], 0, 0, 0);
+          aim[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.im, mre, aim[t], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < CM_CT; ++t) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int row = rt * 16 + (tr ? li : lk + 4 * reg);
+        const int col = (cg * CM_CT + t) * 16 + (tr ? lk + 4 * reg : li);
+        if (row < d && col < ncols) {
+          int b, loc;
+          cplx_col(st, col, n, nq, m_nq, b, loc);
+          cd o = cd{are[t][reg], aim[t][reg]};
+          if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc + row * rts));
+          dst[b + row * rts] = o;
+        }
+      }
+    }
+  }
+}
+
+// One tile of `items` polynomials per workgroup pass.  word: the stage word of launch_cplx (kernels.h).  The launcher
+// gives two LDS buffers when a dense stage is followed by another stage; the last stage, when dense, writes the slab.
+__global__ void __launch_bounds__(256)
+k_cplx_dense(cd* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages, int word, const cd* __restrict__ cst, int items) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nstages = word & 255;
+  const i64 ntiles = (B + items - 1) / items;
+  const u64 m_n = magic40_dev(n);
+  for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const i64 b0 = t * items;
+    const int live = (int)(B - b0 < items ? B - b0 : items);
+    cd* yt = y + (size_t)b0 * n;
+    cd* cur = reinterpret_cast<cd*>(smem);
+    cd* oth = cur + (size_t)items * n;
+    for (int x = threadIdx.x; x < live * n; x += blockDim.x) cur[x] = yt[x];
+    __syncthreads();
+    bool in_lds = true;
+    for (int s = 0; s < nstages; ++s) {
+      const Stage st = stages[s];
+      const int route = (word >> (8 + 2 * s)) & 3;              // cplx_stage_route (kernels.h)
+      if (st.kind == ST_DIAG || st.kind == ST_SCALE) {
+        for (int x = threadIdx.x; x < live * n; x += blockDim.x)
+          cur[x] = cmul(cur[x], cplx_tw(st, cst, x - fdiv40(x, m_n) * n));
+      } else if (route == CPLX_REG) {
+        const int nvec = n / st.d;
+        const u64 m_nvec = magic40_dev(nvec);
+        for (int w = threadIdx.x; w < live * nvec; w += blockDim.x) {
+          const int item = fdiv40(w, m_nvec), vec = w - item * nvec;
+          cd* buf = cur + item * n;
+          switch (st.d) {
+            case 2: cplx_stage_vec<2>(st, buf, vec, cst); break;
+            case 3: cplx_stage_vec<3>(st, buf, vec, cst); break;
+            case 4: cplx_stage_vec<4>(st, buf, vec, cst); break;
+            case 5: cplx_stage_vec<5>(st, buf, vec, cst); break;
+            case 6: cplx_stage_vec<6>(st, buf, vec, cst); break;
+            case 7: cplx_stage_vec<7>(st, buf, vec, cst); break;
+            case 10: cplx_stage_vec<10>(st, buf, vec, cst); break;
+            case 11: cplx_stage_vec<11>(st, buf, vec, cst); break;
+            case 12: cplx_stage_vec<12>(st, buf, vec, cst); break;
+            case 13: cplx_stage_vec<13>(st, buf, vec, cst); break;
+            default: break;   // excluded on the host (plan.cpp: such a stage is dense or the plan is refused)
+          }
+        }
+      } else {
+        const bool last = s == nstages - 1;
+        cd* dst = last ? yt : oth;
+        if (route == CPLX_MFMA) cplx_dense_mfma(st, cur, dst, n, live, cst);
+        else if (st.rts >= 64) cplx_dense_cols(st, cur, dst, n, live, cst);
+        else cplx_dense_rows(st, cur, dst, n, live, cst);
+        if (last) in_lds = false;
+        else { cd* t2 = cur; cur = oth; oth = t2; }
+      }
+      __syncthreads();
+    }
+    if (in_lds)
+      for (int x = threadIdx.x; x < live * n; x += blockDim.x) yt[x] = cur[x];
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
-// k_cplx / k_gauss_dense with more than 64 KiB of dynamic LDS: the attribute, once per device
+// k_cplx / k_gauss_dense / k_cplx_dense with more than 64 KiB of dynamic LDS: the attribute, once per device
 template <typename K>
-static hipError_t allow_big_lds(K kernel, std::atomic<unsigned long long>& done) {
+static hipError_t allow_big_lds(K kernel, std::atomic<unsigned long long>& done, int bytes = 128 * 1024) {
   int dev = -1;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
   if (!(done.load(std::memory_order_acquire) >> dev & 1)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return e;
     done.fetch_or(1ull << dev, std::memory_order_release);
   }
@@ -298,16 +536,55 @@ static hipError_t allow_big_lds(K kernel, std::atomic<unsigned long long>& done)
 }
 
 hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* cconsts) {
-  if (B == 0 || nstages == 0) return hipSuccess;
-  const size_t lds = (size_t)n * sizeof(cd);
+  const int ns = nstages & 255;
+  if (B == 0 || ns == 0) return hipSuccess;
+  const bool info = getenv("LOLHIP_CPLX_INFO") != nullptr;
+  if ((nstages >> 8) == 0) {                                // register stages only
+    const size_t lds = (size_t)n * sizeof(cd);
+    if (lds > 64 * 1024) {
+      static std::atomic<unsigned long long> done{0};
+      hipError_t e = allow_big_lds(&k_cplx, done);
+      if (e != hipSuccess) return e;
+    }
+    i64 grid = B < 4096 ? B : 4096;
+    if (info)
+      fprintf(stderr, "k_cplx: n %lld, B %lld, items 1, bufs 1, lds %zu B, grid %lld, stages reg\n", (long long)n, (long long)B, lds,
+              (long long)grid);
+    hipLaunchKernelGGL(k_cplx, dim3((unsigned)grid), dim3(256), lds, s, reinterpret_cast<cd*>(y), B, (int)n, stages, ns,
+                       reinterpret_cast<const cd*>(cconsts));
+    return hipGetLastError();
+  }
+  // The tile: as many items as 64 KiB of LDS hold (two workgroups per CU) but no more than leave about 512 tiles to the
+  // batch; one item where a polynomial (or its ping-pong pair) is larger than that (up to CPLX_LDS_BUDGET: plan.cpp).
+  int nbuf = 1;
+  for (int i = 0; i + 1 < ns; ++i)
+    if (cplx_stage_route(nstages, i) != CPLX_REG) nbuf = 2;
+  const size_t per = (size_t)nbuf * (size_t)n * sizeof(cd);
+  i64 cap = (i64)(64 * 1024 / per);
+  i64 items = (B + 511) / 512;
+  if (items > cap) items = cap;
+  if (items > B) items = B;
+  if (items < 1) items = 1;
+  const size_t lds = per * (size_t)items;
+  if (lds > CPLX_LDS_BUDGET) return hipErrorInvalidValue;   // excluded on the host (Plan::cplx_route)
   if (lds > 64 * 1024) {
     static std::atomic<unsigned long long> done{0};
-    hipError_t e = allow_big_lds(&k_cplx, done);
+    hipError_t e = allow_big_lds(&k_cplx_dense, done, (int)CPLX_LDS_BUDGET);
     if (e != hipSuccess) return e;
   }
-  i64 grid = B < 4096 ? B : 4096;
-  hipLaunchKernelGGL(k_cplx, dim3((unsigned)grid), dim3(256), lds, s, reinterpret_cast<cd*>(y), B, (int)n, stages, nstages,
-                     reinterpret_cast<const cd*>(cconsts));
+  const i64 ntiles = (B + items - 1) / items;
+  const i64 grid = ntiles < 4096 ? ntiles : 4096;
+  if (info) {
+    char line[320];
+    int at = snprintf(line, sizeof(line), "k_cplx_dense: n %lld, B %lld, items %lld, bufs %d, lds %zu B, grid %lld, stages",
+                      (long long)n, (long long)B, (long long)items, nbuf, lds, (long long)grid);
+    static const char* const names[4] = {"reg", "dense-valu", "dense-mfma", "?"};
+    for (int i = 0; i < ns && at > 0 && at < (int)sizeof(line); ++i)
+      at += snprintf(line + at, sizeof(line) - (size_t)at, " %s", names[cplx_stage_route(nstages, i)]);
+    fprintf(stderr, "%s\n", line);
+  }
+  hipLaunchKernelGGL(k_cplx_dense, dim3((unsigned)grid), dim3(256), lds, s, reinterpret_cast<cd*>(y), B, (int)n, stages, nstages,
+                     reinterpret_cast<const cd*>(cconsts), (int)items);
   return hipGetLastError();
 }
 

@@ -140,6 +140,12 @@ hipError_t launch_mixed_keyswitch(const MixedKeySwitchLaunch& a);
 hipError_t launch_mixed(const MixedLaunch& a);
 
 // floating-point side (floatpath.hip): y [B][n] complex doubles (re, im interleaved) / doubles, in place
+// launch_cplx: as launch_gauss below, the low 8 bits of nstages are the number of stages and above them sit two bits per
+// stage, its route.  A plain count (every stage CPLX_REG) launches k_cplx, as it always did; a word with a dense stage
+// launches k_cplx_dense over Plan::prog_crtc (plan.h), whose dense stages carry the offsets of their matrix forms in
+// the complex pool.  LOLHIP_CPLX_INFO prints one line per launch.
+enum CplxRoute : int { CPLX_REG = 0, CPLX_VALU = 1, CPLX_MFMA = 2 };      // register vectors; dense on the vector ALU / on the matrix cores
+inline int cplx_stage_route(int nstages, int s) { return (nstages >> (8 + 2 * s)) & 3; }
 hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* cconsts);
 // launch_gauss: the low 8 bits of nstages are the number of stages; above them sit two bits per stage, its route
 // (gauss_stage_route).  A program of register stages therefore passes its plain count.  plan_upload packs the word

@@ -306,7 +306,7 @@ static bool merge_stages(std::vector<Stage>& st, PoolBuilder& pool, const std::v
 
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
                     const u64* omega_pp_in, const i64* mhatinv_in, uint32_t flags, uint32_t routes) {
-  if (flags & ~(uint32_t)LOLHIP_PLAN_DENSE_GAUSS) return LOLHIP_ERR_INVALID;
+  if (flags & ~(uint32_t)(LOLHIP_PLAN_DENSE_GAUSS | LOLHIP_PLAN_DENSE_CPLX)) return LOLHIP_ERR_INVALID;
   if (routes & ~(uint32_t)LOLHIP_ROUTE_DENSE_ZQ) return LOLHIP_ERR_INVALID;
   P.flags = flags;
   P.routes = routes;
@@ -605,6 +605,78 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
     P.host_cconsts.clear();
     for (const auto& z : cpool.pool[0]) { P.host_cconsts.push_back(z.real()); P.host_cconsts.push_back(z.imag()); }
   }
+  // How crtC / crtInvC run (plan.h cplx_route).  A plan created with LOLHIP_PLAN_DENSE_CPLX runs the stages of an odd
+  // prime above 13 (of every odd prime under the CPLX_DENSE switch) as batched dense products out of an LDS tile; the
+  // forms of their matrices that k_cplx_dense reads are appended to the complex pool here, one set per distinct matrix.
+  {
+    bool small = true;
+    int pmax = 0;
+    for (const auto& pe : pps) { if (pe.p > 13) small = false; if (pe.p > pmax) pmax = pe.p; }
+    P.cplx_route = (P.n <= 8192 && small) ? 1 : 0;
+    P.cplx_word[0] = P.cplx_word[1] = 0;
+    P.prog_crtc[0].stages.clear(); P.prog_crtc[1].stages.clear();
+    P.cplx_mats.clear();
+    const bool force = sw(SW_CPLX_DENSE), valu = sw(SW_CPLX_DENSE_VALU);
+    auto dense = [&](const Stage& s) {
+      return (s.kind == ST_DFTP || s.kind == ST_CRTP || s.kind == ST_CRTPINV) && s.p > 2 && (s.p > 13 || force);
+    };
+    bool fits = (flags & LOLHIP_PLAN_DENSE_CPLX) && P.n <= 8192 && pmax <= CPLX_DENSE_MAX_P, any = false;
+    const std::vector<Stage>* both[2] = {&P.prog_crt.stages, &P.prog_crtinv.stages};
+    size_t nbufs[2] = {1, 1};
+    for (int dir = 0; dir < 2 && fits; ++dir) {
+      const std::vector<Stage>& st = *both[dir];
+      if (st.size() > (size_t)CPLX_MAX_STAGES) fits = false;
+      size_t nbuf = 1;
+      for (size_t i = 0; i < st.size(); ++i)
+        if (dense(st[i])) { any = true; if (i + 1 < st.size()) nbuf = 2; }
+      if (nbuf * (size_t)P.n * 16 > CPLX_LDS_BUDGET) fits = false;
+      nbufs[dir] = nbuf;
+    }
+    if (fits && any) {
+      P.cplx_route = 2;
+      for (int dir = 0; dir < 2; ++dir) {
+        std::vector<Stage> st = *both[dir];
+        int word = (int)st.size();
+        for (size_t i = 0; i < st.size(); ++i) {
+          Stage& s = st[i];
+          if (!dense(s)) continue;
+          const Plan::CplxDenseMat* have = nullptr;
+          for (const auto& cm : P.cplx_mats) if (cm.mat_off == s.mat_off) have = &cm;
+          if (!have) {
+            const size_t d = (size_t)s.d, dpr = (d + 15) / 16 * 16, dpc = (d + 3) / 4 * 4;
+            Plan::CplxDenseMat cm;
+            cm.mat_off = s.mat_off; cm.d = s.d;
+            cm.mt_off = (int64_t)(P.host_cconsts.size() / 2);
+            cm.pl_off = (int64_t)(P.host_cconsts.size() + 2 * d * d);
+            if ((size_t)cm.pl_off + 3 * dpr * dpc >= ((size_t)1 << 31)) return LOLHIP_ERR_INVALID;   // offsets are int32: far above the cap's 11 M
+            P.host_cconsts.resize((size_t)cm.pl_off + 3 * dpr * dpc, 0.0);
+            double* C = P.host_cconsts.data();
+            const double* M = C + 2 * (size_t)s.mat_off;
+            double* Mt = C + 2 * (size_t)cm.mt_off;
+            double* re = C + cm.pl_off, *im = re + dpr * dpc, *ni = im + dpr * dpc;
+            for (size_t row = 0; row < d; ++row)
+              for (size_t c = 0; c < d; ++c) {
+                const double a = M[2 * (row * d + c)], b = M[2 * (row * d + c) + 1];
+                Mt[2 * (c * d + row)] = a; Mt[2 * (c * d + row) + 1] = b;
+                re[row * dpc + c] = a; im[row * dpc + c] = b; ni[row * dpc + c] = -b;
+              }
+            P.cplx_mats.push_back(cm);
+            have = &P.cplx_mats.back();
+          }
+          s.wp_off = (int32_t)have->mt_off;
+          s.pad[0] = (int32_t)have->pl_off;
+          // The matrix cores where the vector fills a 16-row tile and the largest LDS tile the launcher makes (64 KiB, or
+          // one item) holds 16 columns of this stage, n / d per item (both measured: plan.h).  CPLX_DENSE lifts the two
+          // conditions, so that every stage has both dense routes to compare; CPLX_DENSE_VALU wins over everything.
+          const size_t per = nbufs[dir] * (size_t)P.n * 16, items = per < 64 * 1024 ? 64 * 1024 / per : 1;
+          const bool wide = s.d >= CPLX_MFMA_MIN_D && items * (size_t)(P.n / s.d) >= (size_t)CPLX_MFMA_MIN_COLS;
+          word |= ((!valu && (force || wide)) ? CPLX_MFMA : CPLX_VALU) << (8 + 2 * (int)i);
+        }
+        P.prog_crtc[dir].stages = st;
+        P.cplx_word[dir] = word;
+      }
+    }
+  }
   // tensorGaussianDec (random.cpp:19-64): per odd prime p the real (p-1) x (p-1) map
   //   out[row] = (sum_{col=1}^{p-1} 2 c(row*col mod p) y[col-1]) / sqrt 2,
   //   c(k) = Re omega_p^k for col <= p/2, Im omega_p^k for col > p/2, omega_p = exp(2 pi i / p)
@@ -617,12 +689,9 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
     ProgBuilder pb;
     P.host_rconsts.assign(1, 1.0);
     const bool opted = (flags & LOLHIP_PLAN_DENSE_GAUSS) != 0;
-    P.cplx_ok = P.n <= 8192;
     P.gauss_route = P.n <= 8192 ? 1 : 0;
-    for (const auto& pe : pps) {
-      if (pe.p > 13) P.cplx_ok = false;
+    for (const auto& pe : pps)
       if (pe.p > 13 && !(opted && pe.p < (1 << 15))) P.gauss_route = 0;
-    }
     i64 rts = 1;
     for (int k = 0; k < K; ++k) {
       const int p = pps[(size_t)k].p, e = pps[(size_t)k].e;
@@ -776,7 +845,26 @@ int plan_upload(Plan& P) {
                            &P.prog_crt_odd, &P.prog_crtinv_odd, &P.prog_gauss, &P.prog_crt_fused, &P.prog_crtinv_fused,
                            &P.prog_crt_mg, &P.prog_crtinv_mg, &P.prog_crt_mg_big, &P.prog_crtinv_mg_big, &P.prog_crt_fused_big, &P.prog_crtinv_fused_big};
   for (auto* sp : progs) if ((rc = upload_prog(*sp))) return rc;
-  if ((rc = P.d_cconsts.upload(P.host_cconsts))) return rc;
+  if (P.cplx_mats.empty()) {
+    if ((rc = P.d_cconsts.upload(P.host_cconsts))) return rc;
+  } else {
+    // the planes of the matrix route go up tile by tile in lane order: entry ((rt * nks + ks) * 64 + lane) of a plane is
+    // M[16 rt + (lane & 15)][4 ks + (lane >> 4)], what lane `lane` feeds v_mfma_f64_16x16x4_f64 - one 512-byte read per wave
+    std::vector<double> dev(P.host_cconsts);
+    for (const auto& cm : P.cplx_mats) {
+      const size_t d = (size_t)cm.d, dpr = (d + 15) / 16 * 16, dpc = (d + 3) / 4 * 4, nks = dpc / 4;
+      for (int pl = 0; pl < 3; ++pl) {
+        const double* src = P.host_cconsts.data() + cm.pl_off + (size_t)pl * dpr * dpc;
+        double* dst = dev.data() + cm.pl_off + (size_t)pl * dpr * dpc;
+        for (size_t rt = 0; rt < dpr / 16; ++rt)
+          for (size_t ks = 0; ks < nks; ++ks)
+            for (size_t lane = 0; lane < 64; ++lane)
+              dst[(rt * nks + ks) * 64 + lane] = src[(16 * rt + (lane & 15)) * dpc + 4 * ks + (lane >> 4)];
+      }
+    }
+    if ((rc = P.d_cconsts.upload(dev))) return rc;
+    for (int dir = 0; dir < 2; ++dir) if ((rc = upload_prog(P.prog_crtc[dir]))) return rc;
+  }
   if ((rc = P.d_rconsts.upload(P.host_rconsts))) return rc;
   if (!P.host_zq_mt.empty() && (rc = P.d_zq_mt.upload(P.host_zq_mt))) return rc;
   if (!P.host_zq_planes.empty() && (rc = P.d_zq_planes.upload(P.host_zq_planes))) return rc;

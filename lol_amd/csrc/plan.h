@@ -89,6 +89,16 @@ inline bool zq_dense_stage(const Stage& s) {
   return (s.kind == ST_DFTP || s.kind == ST_CRTP || s.kind == ST_CRTPINV) && s.p > 13;
 }
 
+// dense complex stages at primes above 13 (plans created with LOLHIP_PLAN_DENSE_CPLX; floatpath.hip k_cplx_dense)
+constexpr int CPLX_DENSE_MAX_P = 1021;              // 84 MB of matrix forms for both directions at the cap
+constexpr int CPLX_MAX_STAGES = 12;                 // two route bits per stage above the count in launch_cplx's word
+constexpr size_t CPLX_LDS_BUDGET = 152 * 1024;      // dynamic LDS of one workgroup of k_cplx_dense
+// The least vector length and the least number of columns in an LDS tile at which a stage takes the matrix cores: one
+// whole 16 x 16 output tile.  Measured: ahead of the vector ALU at every d from 16 to 256 where the
+// tile holds 16 columns, behind it at m = 797 where it holds 5.
+constexpr int CPLX_MFMA_MIN_D = 16;
+constexpr int CPLX_MFMA_MIN_COLS = 16;
+
 struct Plan {
   std::vector<PP> pps;
   int T = 0;
@@ -151,8 +161,7 @@ struct Plan {
   std::vector<double> host_cconsts, host_rconsts;
   DevBuf<double> d_cconsts, d_rconsts;
   StageProgram prog_gauss;
-  // one predicate per family (one LDS-resident polynomial each).  cplx_ok: n <= 8192 and every prime <= 13 (register
-  // vectors).  gauss_route: 0 refused; 1 n <= 8192 and register stages only (every odd prime <= 13); 2 n <= 8192, the
+  // one predicate per family (one LDS-resident polynomial each).  gauss_route: 0 refused; 1 n <= 8192 and register stages only (every odd prime <= 13); 2 n <= 8192, the
   // plan was created with LOLHIP_PLAN_DENSE_GAUSS and an odd prime (below 2^15) takes the dense stage: a prime above
   // 13, or every odd prime under the GAUSS_DENSE switch.  A function of (pps, flags, switch), so host-only plans have it.
   uint32_t flags = 0;                       // LOLHIP_PLAN_* of lolhip_plan_create_flags
@@ -168,8 +177,21 @@ struct Plan {
   int zq_W = 0, zq_fold = 0;
   DevBuf<u64> d_zq_mt;
   DevBuf<int8_t> d_zq_planes;
-  bool cplx_ok = false;
   int gauss_route = 0;
+  // crtC / crtInvC (floatpath.hip).  cplx_route: 0 refused; 1 n <= 8192 and every prime <= 13: k_cplx, register stages
+  // only; 2 the plan was created with LOLHIP_PLAN_DENSE_CPLX and at least one stage is dense (a DFT_p, CRT_p or CRT_p^-1 of a prime above 13): every
+  // prime <= CPLX_DENSE_MAX_P, both programs <= CPLX_MAX_STAGES stages and nbuf * 16 n <= CPLX_LDS_BUDGET bytes, nbuf = 2
+  // when a dense stage is followed by another stage (LDS ping-pong), else 1 (the last stage writes the slab).  A function
+  // of (pps, flags, CPLX_DENSE / CPLX_DENSE_VALU at creation), so host-only plans have it.  Route 2 only: prog_crtc[dir]
+  // is the copy of prog_crt / prog_crtinv k_cplx_dense reads - a dense stage's wp_off is the offset (complex units) of
+  // the transposed matrix [c][row] in the complex pool, pad[0] the offset (doubles) of its planes M_re, M_im, -M_im,
+  // each [d rounded up to 16][d rounded up to 4], zero padded; the forms are appended to host_cconsts (row-major there,
+  // tile by tile in lane order on the device: plan_upload) - and cplx_word[dir] is launch_cplx's stage word (kernels.h).
+  int cplx_route = 0;
+  int cplx_word[2] = {0, 0};
+  StageProgram prog_crtc[2];
+  struct CplxDenseMat { int32_t mat_off, d; int64_t mt_off, pl_off; };     // mt_off: complex units; pl_off: doubles
+  std::vector<CplxDenseMat> cplx_mats;
   // Nothing in a plan is written after plan_upload(): per-call workspaces (the operand copy of the
   // unfused poly-mul, the HBM ping-pong ring of polynomials too large for LDS) are stream-ordered
   // allocations made by the call that needs them, so host threads and streams can share a plan.
@@ -194,7 +216,7 @@ int plan_upload(Plan& P);
 // A/B switches of the launch paths (development and tests): read ONCE from the environment
 // (LOLHIP_<NAME>) into atomics; tests flip them through lolhip_debug_set, never through setenv
 // (getenv racing with setenv is undefined behaviour, and plans are used from concurrent threads).
-enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_ZQ_DENSE_VALU, SW_ZQ_DENSE_MFMA, SW_COUNT };
+enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_ZQ_DENSE_VALU, SW_ZQ_DENSE_MFMA, SW_CPLX_DENSE, SW_CPLX_DENSE_VALU, SW_COUNT };
 bool sw(Switch which);
 inline bool pow2_no_t1() { return sw(SW_NO_T1); }
 

@@ -31,7 +31,7 @@ from ._abi import (  # noqa: F401  (the constants and types are part of this mod
     OK, ERR_INVALID, ERR_MODULUS, ERR_NO_CRT, ERR_ROOT, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_DIVISIBLE, ERR_DEVICE,
     OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC, OP_MULGCRT,
     OP_DIVGCRT, EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS,
-    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, ROUTE_DENSE_ZQ, LolHipError, NoDeviceError, _PP, _i64p, _i32p, _check, _len, bind)
+    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, ROUTE_DENSE_ZQ, PLAN_DENSE_CPLX, LolHipError, NoDeviceError, _PP, _PlanOpts, _i64p, _i32p, _check, _len, bind)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -296,17 +296,25 @@ class Plan(_Handle):
     list (CPP.hs:325-337) and the moduli (Backend.hs:195-199)."""
     _kind = "plan"
 
-    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False, dense_zq=False):
+    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False, dense_zq=False, dense_cplx=False):
         """dense_gauss: the Gaussian map (gaussianDec and every sampler behind it) also takes primes above 13, as dense
         stages (LOLHIP_PLAN_DENSE_GAUSS; default roots only).  dense_zq: crt, crtInv and what is composed of them run the
         stages of a prime above 13 as dense products out of an LDS tile (LOLHIP_ROUTE_DENSE_ZQ; default roots only): the
-        same residues from another kernel.  The two compose."""
+        same residues from another kernel.  dense_cplx: crtC / crtInvC also take primes above 13 (up to 1021), as dense
+        stages on the FP64 matrix cores or the vector ALU (LOLHIP_PLAN_DENSE_CPLX, lolhip_plan_create_opts; default roots
+        only; cplxRoute() says whether the index is served).  The three compose."""
         self.pps, arr, npp = _pps(list(pps))
         self.qs = [int(q) for q in qs]
         self.host_only = bool(host_only)
         qa = (C.c_int64 * len(self.qs))(*self.qs)
         what = f"plan_create(pps={self.pps}, qs={self.qs})"
-        if dense_zq:
+        if dense_cplx:
+            if omega_pp is not None or mhatinv is not None:
+                raise ValueError("dense_cplx plans take the default roots")
+            opts = _PlanOpts(C.sizeof(_PlanOpts), (PLAN_DENSE_GAUSS if dense_gauss else 0) | PLAN_DENSE_CPLX,
+                             ROUTE_DENSE_ZQ if dense_zq else 0)
+            self._create("plan_create_opts", arr, npp, qa, len(self.qs), int(host_only), C.byref(opts), what=what)
+        elif dense_zq:
             if omega_pp is not None or mhatinv is not None:
                 raise ValueError("dense_zq plans take the default roots")
             self._create("plan_create_routes", arr, npp, qa, len(self.qs), int(host_only),
@@ -328,6 +336,7 @@ class Plan(_Handle):
         self.has_crt = bool(L.lolhip_plan_has_crt(h))
         self.dense_gauss = bool(dense_gauss)
         self.dense_zq = bool(dense_zq)
+        self.dense_cplx = bool(dense_cplx)
 
     @classmethod
     def for_index(cls, m, qs, **kw):
@@ -362,6 +371,29 @@ class Plan(_Handle):
             L.lolhip_plan_gauss_table(self._h, k, int(transposed), out.ctypes.data_as(C.POINTER(C.c_double)), cnt)
         d = int(round(cnt ** 0.5))
         return out.reshape(d, d)
+
+    def cplxRoute(self):
+        """How crtC / crtInvC run on this plan: 0 refused, 1 register stages only, 2 at least one dense stage."""
+        return int(lib().lolhip_plan_cplx_route(self._h))
+
+    def cplxProgram(self, inverse=False):
+        """The stage program of crtC / crtInvC: rows (kind, prime, length, stride, route), route 0 a register stage or a
+        diagonal, 1 dense on the vector ALU, 2 dense on the matrix cores.  No rows when cplxRoute() is 0."""
+        return self._table(21 if inverse else 20).reshape(-1, 5)
+
+    def cplxTable(self, stage, form, inverse=False):
+        """A dense stage's matrix as the device reads it: form 0 the transposed copy (complex [d][d], entry [c][row]),
+        forms 1, 2, 3 the planes M_re, M_im, -M_im, padded to multiples of 16 rows and 4 columns.  Empty for a stage that
+        is not dense on this plan."""
+        L = lib()
+        cnt = L.lolhip_plan_cplx_table(self._h, int(inverse), int(stage), int(form), None, 0)
+        out = np.zeros(cnt, dtype=np.float64)
+        if cnt:
+            L.lolhip_plan_cplx_table(self._h, int(inverse), int(stage), int(form), out.ctypes.data_as(C.POINTER(C.c_double)), cnt)
+        if form == 0:
+            d = int(round((cnt // 2) ** 0.5))
+            return out.view(np.complex128).reshape(d, d)
+        return out
 
     def zqRoute(self, what=0):
         """Which kernel a lone crt (what=0), a lone crtInv (1) or the poly-mul (2) launches: 0 what a plan without dense_zq

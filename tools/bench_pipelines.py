@@ -15,7 +15,8 @@ profiles/lprf_bench.jsonl) and of RLWE / RLWR instances over moduli without a CR
 composition (`--rlwe-ring`: that leg alone, also written to profiles/rlwe_ring_bench.jsonl) and of whole RLWE challenges,
 one grouped call against 32 single-secret calls (`--challenge`: that leg alone, also written to
 profiles/challenge_bench.jsonl) and of the Gaussian map at primes above 13, the dense stage against the register stage
-(`--gauss-dense`: that leg alone, also written to profiles/gauss_dense_bench.jsonl).
+(`--gauss-dense`: that leg alone, also written to profiles/gauss_dense_bench.jsonl; `--cplx-dense`: the dense complex
+CRT leg alone, written to profiles/cplx_dense_bench.jsonl).
 `--zq-dense`: the dense Z_q stages at primes above 13 alone, also written to profiles/zq_dense_bench.jsonl.
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
@@ -1342,6 +1343,101 @@ def gauss_dense_leg(gen):
         f.write("".join(json.dumps(x) + "\n" for x in lines))
 
 
+def cplx_dense_leg(gen):
+    """crtC at a prime above 13 (k_cplx_dense, plans created with dense_cplx=True) on slabs of about 2^22 complex doubles:
+    m = 179, 257, 797, 17^2, 2^9 17, 2^10 17, the short vectors 17 .. 97 and the long ones 331 .. 509 (12, 10 and 8 columns
+    per tile) that decide where the matrix cores start and stop, each
+    on the matrix route and on the vector-ALU route (debug switch CPLX_DENSE_VALU, read when the plan is built); the
+    indices 13 2^k of nearest n on the register route (k_cplx, a default plan) and with the dense routes forced on them
+    (CPLX_DENSE).  Three rounds, the routes alternating, ten timed calls each after two warm-up calls; the median round, min
+    and max beside it.  macs = 4 B n sum d over the stages, the real multiply-adds; rated against the FP64 peak of
+    78.6 TFLOP/s = 3.93e13 multiply-adds/s (vector and matrix alike on this part).  `tile` is the launcher's own line
+    (LOLHIP_CPLX_INFO).  Then the issue rate of v_mfma_f64_16x16x4_f64 from tools/mfma_f64_rate.hip, built on first use.
+    Written to profiles/cplx_dense_bench.jsonl."""
+    import statistics
+    import subprocess
+    import tempfile
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    FMA_PEAK = 78.6e12 / 2
+    lines = []
+
+    def plan(m, dense, forced=False, valu=False):
+        L.lolhip_debug_set(b"CPLX_DENSE", int(forced))
+        L.lolhip_debug_set(b"CPLX_DENSE_VALU", int(valu))
+        try:
+            return lol_amd.Plan.for_index(m, [12289], dense_cplx=dense)
+        finally:
+            L.lolhip_debug_set(b"CPLX_DENSE", 0)
+            L.lolhip_debug_set(b"CPLX_DENSE_VALU", 0)
+
+    def tile_of(call):
+        sys.stderr.flush()
+        with tempfile.TemporaryFile() as f:
+            keep = os.dup(2)
+            os.environ["LOLHIP_CPLX_INFO"] = "1"
+            os.dup2(f.fileno(), 2)
+            try:
+                call()
+                torch.cuda.synchronize()
+            finally:
+                os.dup2(keep, 2); os.close(keep)
+                del os.environ["LOLHIP_CPLX_INFO"]
+            f.seek(0)
+            got = [ln for ln in f.read().decode().splitlines() if ln.startswith("k_cplx")]
+        return got[-1] if got else ""
+
+    def rounds(cases):
+        slabs, calls = {}, {}
+        for label, m, P in cases:
+            B = max(64, 2 ** 22 // P.n)
+            src = torch.randn((B, P.n, 2), dtype=torch.float64, device="cuda", generator=gen)
+            y = src.clone()
+            slabs[label] = (src, y, B)
+            calls[label] = (lambda P=P, y=y, B=B: L.lolhip_crtc_batch(P._h, st, y.data_ptr(), B))
+            assert calls[label]() == 0
+        ms = {label: [] for label, _, _ in cases}
+        for _ in range(3):
+            for label, _, _ in cases:
+                src, y, _ = slabs[label]
+                y.copy_(src)
+                ms[label].append(timeit(calls[label]))
+        for label, m, P in cases:
+            src, y, B = slabs[label]
+            y.copy_(src)
+            tile = tile_of(calls[label])
+            prog = P.cplxProgram()
+            sum_d = int(sum(int(r[2]) for r in prog if int(r[0]) in (1, 2, 3)))
+            macs = 4 * B * P.n * sum_d
+            med = statistics.median(ms[label])
+            d = {"op": "crtC", "route": label, "config": f"m={m} n={P.n} B={B}", "ms": round(med, 4),
+                 "ms_min": round(min(ms[label]), 4), "ms_max": round(max(ms[label]), 4), "sum_d": sum_d, "macs": macs,
+                 "gmacs_per_s": round(macs / med / 1e6, 1), "frac_of_fp64_peak": round(macs / med * 1e3 / FMA_PEAK, 4),
+                 "alg_GBps": round(2 * B * P.n * 16 / med / 1e6, 1), "tile": tile}
+            lines.append(d)
+            print(json.dumps(d), flush=True)
+
+    # (CPLX_DENSE lifts the route rule's conditions, so "dense-mfma" is the matrix route wherever the rule would put the stage)
+    for m in (17, 19, 23, 29, 37, 53, 97, 179, 257, 331, 397, 509, 797, 17 ** 2, 2 ** 9 * 17, 2 ** 10 * 17):
+        rounds([("dense-mfma", m, plan(m, True, forced=True)), ("dense-valu", m, plan(m, True, valu=True))])
+    for m13 in (13 * 2 ** 5, 13 * 2 ** 6, 13 * 2 ** 7, 13 * 2 ** 9):
+        rounds([("register", m13, plan(m13, False)), ("forced-mfma", m13, plan(m13, True, forced=True)),
+                ("forced-valu", m13, plan(m13, True, forced=True, valu=True))])
+    # the issue rate of the f64 MFMA itself: a program of its own, in a process of its own
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = os.path.join(here, "_build", "mfma_f64_rate")
+    if not os.path.exists(exe):
+        os.makedirs(os.path.dirname(exe), exist_ok=True)
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-o", exe, os.path.join(here, "mfma_f64_rate.hip")])
+    for ln in subprocess.run([exe], capture_output=True, text=True, check=True, timeout=120).stdout.splitlines():
+        if ln.startswith("{"):
+            lines.append(json.loads(ln))
+            print(ln, flush=True)
+    out = os.path.join(os.path.dirname(here), "profiles", "cplx_dense_bench.jsonl")
+    with open(out, "w") as f:
+        f.write("".join(json.dumps(x) + "\n" for x in lines))
+
+
 def zq_dense_leg(gen):
     """The dense Z_q stages at a prime above 13 (zqdense.hip, plans created with dense_zq=True): crt, crtInv and the
     poly-mul on slabs of about 2^22 words at m = 179, 257 and 797 (a list modulus with a CRT basis each, and the NTT prime
@@ -1467,6 +1563,9 @@ def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
     if "--zq-dense" in sys.argv:         # the dense Z_q stages leg alone
         zq_dense_leg(gen)
+        return
+    if "--cplx-dense" in sys.argv:       # the dense complex CRT leg alone
+        cplx_dense_leg(gen)
         return
     if "--gauss-dense" in sys.argv:      # the dense Gaussian stage leg alone
         gauss_dense_leg(gen)
