@@ -133,8 +133,19 @@ LOLHIP_API int64_t lolhip_plan_gauss_table(const lolhip_plan *p, int k, int tran
  *       it was.  The cost is memory: per component and per such matrix the plan holds, on the host and on the device, a
  *       transposed copy (8 d^2 bytes beside the 8 d^2 it had) and, where the moduli fit the matrix cores, W <= 4 int8
  *       limb planes (W d'^2 bytes, d' = d rounded up to 32) - 15 MB per component for both directions at m = 797, about
- *       1.6 GB at a prime index near 8192 (lolhip_plan_zq_table reads them back). */
+ *       1.6 GB at a prime index near 8192 (lolhip_plan_zq_table reads them back).
+ *   LOLHIP_ROUTE_SCAN_ZQ  (lolhip_plan_create_opts only; lolhip_plan_create_routes refuses the bit, and the value 2u is
+ *       not defined)  the six prime ops over Z_q - lolhip_l_batch, lolhip_linv_batch, lolhip_mulgpow_batch,
+ *       lolhip_mulgdec_batch, lolhip_divgpow_batch, lolhip_divgdec_batch and every pipeline that runs those stage
+ *       programs (the challenges' and RLWE instances' basis changes, encrypt, decrypt, hints, modSwitch, ...) - run the
+ *       stages of a prime above 13 as prefix sums, totals and neighbour differences on an LDS tile of polynomials
+ *       (k_zq_scan: O(log) or O(1) modular additions per word) where the scalar interpreter spends up to p - 1 per
+ *       output.  Modular addition is associative and exact: the same residues.  Taken when n <= 8192, the program about
+ *       to be launched holds an L / L^-1 / mulG / divG stage of a prime above 13, nothing but such stages and diagonals,
+ *       at most 24 stages in all, and would go to the scalar interpreter; every other launch of the plan is what it was
+ *       (lolhip_plan_scan_route answers per op).  Needs no CRT basis, no tables and no plan memory. */
 #define LOLHIP_ROUTE_DENSE_ZQ 1u
+#define LOLHIP_ROUTE_SCAN_ZQ 4u
 LOLHIP_API int lolhip_plan_create_routes(const lolhip_pp *pps, int npps, const int64_t *qs, int T, int host_only,
                                          uint32_t flags, uint32_t routes, lolhip_plan **out);
 /* Which kernel a Z_q transform of this plan launches.  what: 0 a lone crt, 1 a lone crtInv, 2 the poly-mul.
@@ -153,6 +164,13 @@ LOLHIP_API int lolhip_plan_create_routes(const lolhip_pp *pps, int npps, const i
  * tile leaves the inverse program, which runs on half of it, a whole register tile of columns (32 on the matrix cores,
  * 8 / 4 on the vector ALU at 4- / 8-byte words); below that the composed form measured faster. */
 LOLHIP_API int lolhip_plan_zq_route(const lolhip_plan *p, int what);
+/* Whether the scan kernel (LOLHIP_ROUTE_SCAN_ZQ) runs the stage program of prime op `op`, LOLHIP_OP_L ...
+ * LOLHIP_OP_DIVGDEC: 1 if so, 0 otherwise - a null plan, an op out of that range, a plan that has not opted in, n > 8192,
+ * an index whose primes are all <= 13 (the vector interpreter's, or a 2-power's).  A function of the prime powers, the
+ * moduli, the route word and two debug switches read at launch (GENERIC_SCALAR: 0 everywhere; ZQ_SCAN: an opted-in plan
+ * takes the scan kernel at primes up to 13 as well, also where the vector interpreter would run; GENERIC_SCALAR wins),
+ * so host-only plans answer it.  divG's LOLHIP_ERR_NOT_DIVISIBLE is decided before any launch whatever the route. */
+LOLHIP_API int lolhip_plan_scan_route(const lolhip_plan *p, int op);
 /* A dense stage's matrix as the device reads it (inspection, tests).  inverse: the lone crtInv's program, else the lone
  * crt's; stage: index into that program (lolhip_plan_table 10 / 11); t: component.  limb = -1: the transposed word
  * matrix of the vector-ALU route, d * d residues in [0, q_t), entry [c][row].  limb >= 0: that int8 limb plane of the
@@ -1292,7 +1310,14 @@ LOLHIP_API int lolhip_copy_slab(void *stream, void *dst, const void *src, int64_
  *                         kind one of elt (element-wise), dense-rows (lanes along the rows, stride < 64), dense-cols
  *                         (lanes along r); the one-launch poly-mul lists the forward program, "*", the inverse program;
  *   LOLHIP_ZQ_DENSE_GRID=<G>  the grid is G workgroups (at least 1) instead of one per (tile, component), so that a
- *                         small batch exercises the grid-stride loop. */
+ *                         small batch exercises the grid-stride loop.
+ * ZQ_SCAN is one more name for lolhip_debug_set (read at launch: see lolhip_plan_scan_route), and two more variables are
+ * read at every launch of the scan kernel (plans created with LOLHIP_ROUTE_SCAN_ZQ):
+ *   LOLHIP_ZQ_SCAN_INFO   (set to anything) each launch prints one line to stderr:
+ *                         "k_zq_scan: n <n>, B <B>, T <T>, word <4|8>, items <I>, lds <bytes> B, grid <G>, threads <t>, stages <kind>:<p>:<d>:<rts>:<layout> ...",
+ *                         kind one of l, linv, gpow, gdec, ginvpow, ginvdec, diag; layout one of lanes (stride below a
+ *                         wave: the wave scans across lanes), cols (a lane walks one column), elt (element-wise);
+ *   LOLHIP_ZQ_SCAN_GRID=<G>  the grid is G workgroups (at least 1) instead of one per (tile, component). */
 LOLHIP_API int lolhip_debug_set(const char *name, int value);
 
 /* number of HIP devices visible (0 without a GPU); never initialises a context */

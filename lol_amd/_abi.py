@@ -16,6 +16,7 @@ EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EX
 ELT_I64, ELT_F64, ELT_C64 = range(3)
 PLAN_DENSE_GAUSS = 1
 ROUTE_DENSE_ZQ = 1
+ROUTE_SCAN_ZQ = 4            # honoured by lolhip_plan_create_opts only; 2 is not defined
 PLAN_DENSE_CPLX = 2          # honoured by lolhip_plan_create_opts only
 
 
@@ -82,7 +83,7 @@ ABI = _rows(
     ("plan_create_opts", ci, pp, ci, _i64p, ci, ci, C.POINTER(_PlanOpts), vpp),
     ("plan_cplx_route", ci, vp),
     ("plan_cplx_table", i64, vp, ci, ci, ci, f64p, i64),
-    ("plan_zq_route", ci, vp, ci),
+    ("plan_zq_route plan_scan_route", ci, vp, ci),
     ("plan_zq_table", i64, vp, ci, ci, ci, ci, _i64p, i64),
     ("plan_destroy ext_destroy khprf_destroy tunnel_chain_destroy ptround_destroy pt_tunnel_destroy ringmul_destroy lprf_destroy", None, vp),
     ("plan_n plan_m", i64, vp),

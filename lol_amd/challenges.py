@@ -182,8 +182,10 @@ def large_prime(m):
 def route(cp, host_only=True, dense_gauss=False):
     """("plan" | "ring", Plan): lolhip_plan_has_crt decides, as for the single-secret entries.  dense_gauss: the plan
     opts in to the dense stage of the Gaussian map, which the error of a Cont or Disc challenge needs at a prime above 13.
-    At such an index the plan also routes its Z_q transforms (a s of every kind, RLWR included) to the dense stages."""
-    plan = Plan.for_index(cp.m, [cp.q], host_only=host_only, dense_gauss=dense_gauss, dense_zq=large_prime(cp.m))
+    At such an index the plan also routes its Z_q transforms (a s of every kind, RLWR included) to the dense stages and
+    its basis changes (L, LInv) to the scan kernel."""
+    plan = Plan.for_index(cp.m, [cp.q], host_only=host_only, dense_gauss=dense_gauss, dense_zq=large_prime(cp.m),
+                          scan_zq=large_prime(cp.m))
     return ("plan" if plan.has_crt else "ring"), plan
 
 
@@ -336,7 +338,7 @@ class DeviceEngine:
     in to the dense stage of the Gaussian map (a Cont or Disc error at a prime above 13; nothing changes elsewhere)"""
 
     def __init__(self, m, q):
-        plan = Plan.for_index(m, [q], dense_gauss=True, dense_zq=large_prime(m))
+        plan = Plan.for_index(m, [q], dense_gauss=True, dense_zq=large_prime(m), scan_zq=large_prime(m))
         self.r = RLWE(plan) if plan.has_crt else RingRLWE(plan)
         self.n = plan.n
 

@@ -23,7 +23,7 @@ using namespace lolhip;
 namespace lolhip {
 namespace {
 const char* const kSwitchNames[SW_COUNT] = {"GENERIC_SCALAR", "NO_FUSED2", "NO_POW2_PART", "POLYMUL_UNFUSED",
-                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE", "ZQ_DENSE_VALU", "ZQ_DENSE_MFMA", "CPLX_DENSE", "CPLX_DENSE_VALU"};
+                                            "KEYSWITCH_UNFUSED", "NO_T1", "NO_PIPE", "FORCE_PIPE", "NO_OWN_DIAG", "NO_MERGE", "NO_LAZY", "NO_KRON", "NO_TRUNC", "ELT_GLOBAL", "LPRF_VALU", "RLWE_RING_UNFUSED", "GAUSS_DENSE", "ZQ_DENSE_VALU", "ZQ_DENSE_MFMA", "CPLX_DENSE", "CPLX_DENSE_VALU", "ZQ_SCAN"};
 std::atomic<int> g_switch[SW_COUNT];
 std::once_flag g_switch_once;
 void switches_init() {
@@ -53,9 +53,10 @@ int device_count() {
 
 int make_plan(const lolhip_pp* pps, int npps, const int64_t* qs, int T, const int64_t* omega_pp,
               const int64_t* mhatinv, int host_only, lolhip_plan** out, uint32_t flags = 0, uint32_t routes = 0,
-              uint32_t known_flags = LOLHIP_PLAN_DENSE_GAUSS) {      // the flag bits the calling creator honours
+              uint32_t known_flags = LOLHIP_PLAN_DENSE_GAUSS,        // the flag and route bits the calling creator honours
+              uint32_t known_routes = LOLHIP_ROUTE_DENSE_ZQ) {
   std::vector<PP> v;
-  if (!out || T < 1 || !qs || !to_pps(pps, npps, v) || (flags & ~known_flags)) return LOLHIP_ERR_INVALID;
+  if (!out || T < 1 || !qs || !to_pps(pps, npps, v) || (flags & ~known_flags) || (routes & ~known_routes)) return LOLHIP_ERR_INVALID;
   *out = nullptr;
   std::vector<u64> q;
   for (int t = 0; t < T; ++t) {
@@ -144,6 +145,24 @@ void zq_fill(const Plan& P, const StageProgram& sp, size_t at, ZqDenseLaunch& z)
   }
 }
 
+// Whether the launch of stage program sp takes the scan kernel (ZqScanLaunch::route, kernels.h).  ONE decision, read by
+// run_prog and by lolhip_plan_scan_route: the plan opted in (LOLHIP_ROUTE_SCAN_ZQ), GENERIC_SCALAR is off, n <= 8192
+// (one LDS buffer of a polynomial), the program would go to the scalar interpreter, it holds at most ZQ_MAX_STAGES
+// stages, nothing but prime-op stages and diagonals (what the kernel runs in place; true of every prime-op program),
+// and a prime-op stage of a prime above 13.  ZQ_SCAN (tests, measurements) drops the last condition and the
+// interpreter condition, so the indices the vector interpreter runs can be compared against it.
+int zq_scan_route(const Plan& P, const StageProgram& sp) {
+  if (!(P.routes & LOLHIP_ROUTE_SCAN_ZQ) || sw(SW_GENERIC_SCALAR) || P.n > 8192) return 0;
+  const bool forced = sw(SW_ZQ_SCAN);
+  if ((!forced && use_mixed(P, sp)) || sp.stages.size() > (size_t)ZQ_MAX_STAGES) return 0;
+  bool hit = false;
+  for (const Stage& st : sp.stages) {
+    if (zq_scan_stage(st)) hit = hit || st.p > 13 || forced;
+    else if (st.kind != ST_DIAG && st.kind != ST_SCALE) return 0;
+  }
+  return hit ? 1 : 0;
+}
+
 bool q_below(const Plan& P, int bits) {
   for (u64 q : P.qs) if (q >> bits) return false;
   return true;
@@ -185,7 +204,8 @@ int need_device(const Plan& P) {
 int need_device(const lolhip_plan* p) { return p ? need_device(p->P) : LOLHIP_ERR_INVALID; }
 
 int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, int64_t B, const int64_t* src) {
-  if (use_mixed(P, sp)) return hip_status(launch_mixed(mixed_launch(P, s, y, src ? src : y, B, sp)));
+  const int scan = zq_scan_route(P, sp);          // before the vector interpreter: ZQ_SCAN takes its indices too
+  if (!scan && use_mixed(P, sp)) return hip_status(launch_mixed(mixed_launch(P, s, y, src ? src : y, B, sp)));
   GenericLaunch a;
   a.stream = s; a.y = y; a.B = B; a.T = P.T; a.n = P.n;
   a.stages = sp.d_stages; a.nstages = sp.nstages;
@@ -200,6 +220,14 @@ int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, i
   }
   a.q32 = true;
   for (u64 q : P.qs) if (q >= ((u64)1 << 32)) a.q32 = false;
+  if (scan) {                           // the scan kernel reads src itself
+    a.scan.route = scan;
+    a.scan.src = (src && src != y) ? src : nullptr;
+    a.scan.host_stages = sp.stages.data();
+    for (size_t i = 0; i < sp.stages.size(); ++i)
+      a.scan.kind[i] = !zq_scan_stage(sp.stages[i]) ? ZS_ELT : sp.stages[i].rts >= 64 ? ZS_COLS : ZS_LANES;
+    return hip_status(launch_generic(a));
+  }
   a.zq.route = zq_dense_route(P, sp);
   if (a.zq.route) {                     // the dense kernels read src themselves
     zq_fill(P, sp, 0, a.zq);
@@ -365,7 +393,7 @@ int lolhip_plan_create_opts(const lolhip_pp* pps, int npps, const int64_t* qs, i
   if (out) *out = nullptr;
   if (!opts || opts->size != sizeof(lolhip_plan_opts)) return LOLHIP_ERR_INVALID;
   return make_plan(pps, npps, qs, T, nullptr, nullptr, host_only, out, opts->flags, opts->routes,
-                   LOLHIP_PLAN_DENSE_GAUSS | LOLHIP_PLAN_DENSE_CPLX);
+                   LOLHIP_PLAN_DENSE_GAUSS | LOLHIP_PLAN_DENSE_CPLX, LOLHIP_ROUTE_DENSE_ZQ | LOLHIP_ROUTE_SCAN_ZQ);
 }
 int lolhip_plan_cplx_route(const lolhip_plan* p) { return p ? p->P.cplx_route : 0; }
 int64_t lolhip_plan_cplx_table(const lolhip_plan* p, int inverse, int stage, int form, double* out, int64_t cap) {
@@ -386,6 +414,19 @@ int lolhip_plan_zq_route(const lolhip_plan* p, int what) {
   if (what == 2) return zq_polymul_route(p->P);
   const CrtRoute r = crt_route(p->P);
   return r == ROUTE_POW2 ? 0 : zq_dense_route(p->P, crt_route_prog(p->P, r, what == 1));
+}
+int lolhip_plan_scan_route(const lolhip_plan* p, int op) {
+  if (!p) return 0;
+  const Plan& P = p->P;
+  switch (op) {
+    case LOLHIP_OP_L: return zq_scan_route(P, P.prog_l);
+    case LOLHIP_OP_LINV: return zq_scan_route(P, P.prog_linv);
+    case LOLHIP_OP_MULGPOW: return zq_scan_route(P, P.prog_gpow);
+    case LOLHIP_OP_MULGDEC: return zq_scan_route(P, P.prog_gdec);
+    case LOLHIP_OP_DIVGPOW: return zq_scan_route(P, P.prog_ginvpow);
+    case LOLHIP_OP_DIVGDEC: return zq_scan_route(P, P.prog_ginvdec);
+    default: return 0;
+  }
 }
 int64_t lolhip_plan_zq_table(const lolhip_plan* p, int inverse, int stage, int t, int limb, int64_t* out, int64_t cap) {
   if (!p || t < 0 || t >= p->P.T || stage < 0 || limb < -1) return 0;

@@ -77,6 +77,18 @@ struct ZqDenseLaunch {
   i64 pl_off[ZQ_MAX_STAGES];
 };
 
+// The scan route of the prime ops' stage programs (zqscan.hip; plans created with LOLHIP_ROUTE_SCAN_ZQ).  It rides in
+// GenericLaunch as the dense route does.  Per stage the host decides the layout, the kernel and the info line obey:
+// element-wise (diagonals); the wave scans across lanes (stride below a wave); a lane walks one column (stride of at
+// least a wave).
+enum ZqScanKind : uint8_t { ZS_ELT = 0, ZS_LANES = 1, ZS_COLS = 2 };
+struct ZqScanLaunch {
+  int route = 0;                 // 0: not taken (everything below unused); 1: k_zq_scan
+  const i64* src = nullptr;      // input slab when it is not y (null: in place)
+  const Stage* host_stages = nullptr;   // the program's host copy (the info line)
+  uint8_t kind[ZQ_MAX_STAGES] = {};   // ZqScanKind
+};
+
 struct GenericLaunch {
   hipStream_t stream;
   i64* y;
@@ -92,9 +104,11 @@ struct GenericLaunch {
   size_t scratch_bytes;
   bool q32;          // every modulus < 2^32: 32-bit operand products in the dot-product stages
   ZqDenseLaunch zq;  // route 0 unless the plan opted in and the program holds a dense stage of a prime above 13
+  ZqScanLaunch scan; // route 0 unless the plan opted in and the program holds a prime-op stage of a prime above 13
 };
 hipError_t launch_generic(const GenericLaunch& a);
 hipError_t launch_zq_dense(const GenericLaunch& a);   // zqdense.hip; called by launch_generic only
+hipError_t launch_zq_scan(const GenericLaunch& a);    // zqscan.hip; called by launch_generic only
 
 // vector-per-thread interpreter + fused mixed-radix poly-mul (mixed.hip); every prime <= 13, n <= 8192
 struct MixedLaunch {

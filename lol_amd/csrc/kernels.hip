@@ -11,7 +11,9 @@
 //                    primes > 13 or n > 8192 (the vector interpreter and the fused mixed-radix
 //                    poly-mul are in mixed.hip).  launch_generic hands a program with a stage of a
 //                    prime above 13 to the dense Z_q kernels (zqdense.hip) when the plan was created
-//                    with LOLHIP_ROUTE_DENSE_ZQ and n <= 8192; every other plan launches k_generic as before
+//                    with LOLHIP_ROUTE_DENSE_ZQ and n <= 8192, and a prime-op program (L, L^-1, mulG, divG) with such a
+//                    prime to the scan kernel (zqscan.hip) when it was created with LOLHIP_ROUTE_SCAN_ZQ; every other
+//                    plan launches k_generic as before
 //   k_pointwise_mul  mulRq (mul.cpp:14-30) and mulGCRT/divGCRT (CPP.hs:230-231)
 //   k_gather / k_twace_crt   twace*/embed* (Extension.hs:54-129)
 //
@@ -297,6 +299,7 @@ k_generic(i64* __restrict__ y, i64 B, int T, int n, const Stage* __restrict__ st
 hipError_t launch_generic(const GenericLaunch& a) {
   if (a.B == 0) return hipSuccess;
   if (a.zq.route) return launch_zq_dense(a);      // opted-in plans, programs with a dense stage above 13 (zqdense.hip)
+  if (a.scan.route) return launch_zq_scan(a);     // opted-in plans, the prime ops' programs at a prime above 13 (zqscan.hip)
   const size_t lds_budget = 152 * 1024;
   const size_t per_poly = 2 * (size_t)a.n * sizeof(u64);
   int ppw = 1;

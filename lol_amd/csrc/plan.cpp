@@ -307,7 +307,7 @@ static bool merge_stages(std::vector<Stage>& st, PoolBuilder& pool, const std::v
 int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>& qs,
                     const u64* omega_pp_in, const i64* mhatinv_in, uint32_t flags, uint32_t routes) {
   if (flags & ~(uint32_t)(LOLHIP_PLAN_DENSE_GAUSS | LOLHIP_PLAN_DENSE_CPLX)) return LOLHIP_ERR_INVALID;
-  if (routes & ~(uint32_t)LOLHIP_ROUTE_DENSE_ZQ) return LOLHIP_ERR_INVALID;
+  if (routes & ~(uint32_t)(LOLHIP_ROUTE_DENSE_ZQ | LOLHIP_ROUTE_SCAN_ZQ)) return LOLHIP_ERR_INVALID;
   P.flags = flags;
   P.routes = routes;
   if (!valid_pps(pps) || qs.empty() || qs.size() > 64) return LOLHIP_ERR_INVALID;

@@ -89,6 +89,10 @@ inline bool zq_dense_stage(const Stage& s) {
   return (s.kind == ST_DFTP || s.kind == ST_CRTP || s.kind == ST_CRTPINV) && s.p > 13;
 }
 
+// the stages the scan route runs as prefix sums, totals and neighbour differences (zqscan.hip; plans created with
+// LOLHIP_ROUTE_SCAN_ZQ): L, L^-1, mulG and divG of one prime
+inline bool zq_scan_stage(const Stage& s) { return s.kind >= ST_L && s.kind <= ST_GINVDEC; }
+
 // dense complex stages at primes above 13 (plans created with LOLHIP_PLAN_DENSE_CPLX; floatpath.hip k_cplx_dense)
 constexpr int CPLX_DENSE_MAX_P = 1021;              // 84 MB of matrix forms for both directions at the cap
 constexpr int CPLX_MAX_STAGES = 12;                 // two route bits per stage above the count in launch_cplx's word
@@ -216,7 +220,7 @@ int plan_upload(Plan& P);
 // A/B switches of the launch paths (development and tests): read ONCE from the environment
 // (LOLHIP_<NAME>) into atomics; tests flip them through lolhip_debug_set, never through setenv
 // (getenv racing with setenv is undefined behaviour, and plans are used from concurrent threads).
-enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_ZQ_DENSE_VALU, SW_ZQ_DENSE_MFMA, SW_CPLX_DENSE, SW_CPLX_DENSE_VALU, SW_COUNT };
+enum Switch { SW_GENERIC_SCALAR, SW_NO_FUSED2, SW_NO_POW2_PART, SW_POLYMUL_UNFUSED, SW_KEYSWITCH_UNFUSED, SW_NO_T1, SW_NO_PIPE, SW_FORCE_PIPE, SW_NO_OWN_DIAG, SW_NO_MERGE, SW_NO_LAZY, SW_NO_KRON, SW_NO_TRUNC, SW_ELT_GLOBAL, SW_LPRF_VALU, SW_RLWE_RING_UNFUSED, SW_GAUSS_DENSE, SW_ZQ_DENSE_VALU, SW_ZQ_DENSE_MFMA, SW_CPLX_DENSE, SW_CPLX_DENSE_VALU, SW_ZQ_SCAN, SW_COUNT };
 bool sw(Switch which);
 inline bool pow2_no_t1() { return sw(SW_NO_T1); }
 

@@ -31,7 +31,7 @@ from ._abi import (  # noqa: F401  (the constants and types are part of this mod
     OK, ERR_INVALID, ERR_MODULUS, ERR_NO_CRT, ERR_ROOT, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_DIVISIBLE, ERR_DEVICE,
     OP_CRT, OP_CRTINV, OP_MUL, OP_POLYMUL, OP_L, OP_LINV, OP_MULGPOW, OP_MULGDEC, OP_DIVGPOW, OP_DIVGDEC, OP_MULGCRT,
     OP_DIVGCRT, EXT_TWACE_POWDEC, EXT_TWACE_CRT, EXT_EMBED_POW, EXT_EMBED_DEC, EXT_EMBED_CRT, EXT_COEFFS,
-    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, ROUTE_DENSE_ZQ, PLAN_DENSE_CPLX, LolHipError, NoDeviceError, _PP, _PlanOpts, _i64p, _i32p, _check, _len, bind)
+    ELT_I64, ELT_F64, ELT_C64, PLAN_DENSE_GAUSS, ROUTE_DENSE_ZQ, ROUTE_SCAN_ZQ, PLAN_DENSE_CPLX, LolHipError, NoDeviceError, _PP, _PlanOpts, _i64p, _i32p, _check, _len, bind)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -296,23 +296,26 @@ class Plan(_Handle):
     list (CPP.hs:325-337) and the moduli (Backend.hs:195-199)."""
     _kind = "plan"
 
-    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False, dense_zq=False, dense_cplx=False):
+    def __init__(self, pps, qs, host_only=False, omega_pp=None, mhatinv=None, dense_gauss=False, dense_zq=False, dense_cplx=False, scan_zq=False):
         """dense_gauss: the Gaussian map (gaussianDec and every sampler behind it) also takes primes above 13, as dense
         stages (LOLHIP_PLAN_DENSE_GAUSS; default roots only).  dense_zq: crt, crtInv and what is composed of them run the
         stages of a prime above 13 as dense products out of an LDS tile (LOLHIP_ROUTE_DENSE_ZQ; default roots only): the
         same residues from another kernel.  dense_cplx: crtC / crtInvC also take primes above 13 (up to 1021), as dense
         stages on the FP64 matrix cores or the vector ALU (LOLHIP_PLAN_DENSE_CPLX, lolhip_plan_create_opts; default roots
-        only; cplxRoute() says whether the index is served).  The three compose."""
+        only; cplxRoute() says whether the index is served).  scan_zq: L, LInv, mulGPow/Dec and divGPow/Dec over Z_q run
+        the stages of a prime above 13 as scans on an LDS tile (LOLHIP_ROUTE_SCAN_ZQ, lolhip_plan_create_opts; default
+        roots only; needs no CRT basis; scanRoute(op) says which ops take it): the same residues from another kernel.
+        The four compose."""
         self.pps, arr, npp = _pps(list(pps))
         self.qs = [int(q) for q in qs]
         self.host_only = bool(host_only)
         qa = (C.c_int64 * len(self.qs))(*self.qs)
         what = f"plan_create(pps={self.pps}, qs={self.qs})"
-        if dense_cplx:
+        if dense_cplx or scan_zq:
             if omega_pp is not None or mhatinv is not None:
-                raise ValueError("dense_cplx plans take the default roots")
-            opts = _PlanOpts(C.sizeof(_PlanOpts), (PLAN_DENSE_GAUSS if dense_gauss else 0) | PLAN_DENSE_CPLX,
-                             ROUTE_DENSE_ZQ if dense_zq else 0)
+                raise ValueError(f"{'dense_cplx' if dense_cplx else 'scan_zq'} plans take the default roots")
+            opts = _PlanOpts(C.sizeof(_PlanOpts), (PLAN_DENSE_GAUSS if dense_gauss else 0) | (PLAN_DENSE_CPLX if dense_cplx else 0),
+                             (ROUTE_DENSE_ZQ if dense_zq else 0) | (ROUTE_SCAN_ZQ if scan_zq else 0))
             self._create("plan_create_opts", arr, npp, qa, len(self.qs), int(host_only), C.byref(opts), what=what)
         elif dense_zq:
             if omega_pp is not None or mhatinv is not None:
@@ -337,6 +340,7 @@ class Plan(_Handle):
         self.dense_gauss = bool(dense_gauss)
         self.dense_zq = bool(dense_zq)
         self.dense_cplx = bool(dense_cplx)
+        self.scan_zq = bool(scan_zq)
 
     @classmethod
     def for_index(cls, m, qs, **kw):
@@ -400,6 +404,11 @@ class Plan(_Handle):
         launches, 1 the dense stages on the vector ALU, 2 on the matrix cores.  For the poly-mul 0 also means composed of
         lone transforms, which may themselves be dense."""
         return int(lib().lolhip_plan_zq_route(self._h, int(what)))
+
+    def scanRoute(self, op):
+        """Whether the scan kernel runs prime op `op` (OP_L ... OP_DIVGDEC) on this plan: 1, or 0 - what a plan without
+        scan_zq launches."""
+        return int(lib().lolhip_plan_scan_route(self._h, int(op)))
 
     def zqTable(self, stage, t=0, limb=-1, inverse=False):
         """A dense stage's matrix as the device reads it, for stage `stage` of program(inverse) and component t: the
@@ -1238,11 +1247,12 @@ class RingMul(_WorkHandle):
     (taken mod q_t), results lie in [0, q_t)."""
     _kind = "ringmul"
 
-    def __init__(self, plan_q, plan_Q=None, dense_zq=None):
-        """dense_zq: passed to the plan_Q made here (None: what plan_q has)"""
+    def __init__(self, plan_q, plan_Q=None, dense_zq=None, scan_zq=None):
+        """dense_zq, scan_zq: passed to the plan_Q made here (None: what plan_q has)"""
         if plan_Q is None:
             plan_Q = Plan(plan_q.pps, self.moduli(plan_q.pps, plan_q.qs), host_only=plan_q.host_only,
-                          dense_zq=plan_q.dense_zq if dense_zq is None else dense_zq)
+                          dense_zq=plan_q.dense_zq if dense_zq is None else dense_zq,
+                          scan_zq=plan_q.scan_zq if scan_zq is None else scan_zq)
         self.plan_q, self.plan_Q = plan_q, plan_Q
         self.n, self.T, self.K = plan_q.n, plan_q.T, plan_Q.T
         self._create("ringmul_create", plan_q._h, plan_Q._h)

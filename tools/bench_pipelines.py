@@ -18,6 +18,7 @@ profiles/challenge_bench.jsonl) and of the Gaussian map at primes above 13, the 
 (`--gauss-dense`: that leg alone, also written to profiles/gauss_dense_bench.jsonl; `--cplx-dense`: the dense complex
 CRT leg alone, written to profiles/cplx_dense_bench.jsonl).
 `--zq-dense`: the dense Z_q stages at primes above 13 alone, also written to profiles/zq_dense_bench.jsonl.
+`--zq-scan`: the scan route of the prime ops at primes above 13 alone, also written to profiles/zq_scan_bench.jsonl.
 Operands resident in HBM, HIP events on the launch stream.  Prints one JSON object per line; `alg_bytes` is the compulsory traffic
 of the *fused ideal* (each input slab read once, each output written once)."""
 import json
@@ -1559,8 +1560,100 @@ def zq_dense_leg(gen):
         f.write("".join(json.dumps(x) + "\n" for x in lines))
 
 
+def zq_scan_leg(gen):
+    """The scan route of the prime ops at a prime above 13 (zqscan.hip, plans created with scan_zq=True): L, divGPow and
+    divGDec on slabs of about 2^22 words at m = 17, 67, 179, 257, 797 and 2176 (128 * 17: the column layout), each over a
+    modulus below 2^32 and over a 61-bit one.  Per line three things alternate in one process: the opted-in plan
+    (`scan`), a default plan of the same parameters (`scalar`: exactly the launches of a plan without the route) and
+    lolhip_copy_slab of the same bytes (`copy`: the floor of a read-once / write-once kernel).  Three rounds, ten timed
+    calls each after two warm-up calls, HIP events; the median round with min and max beside it.  `tile` is the
+    launcher's own line (LOLHIP_ZQ_SCAN_INFO).  Then one whole Disc challenge of I = 32 instances of L = 3 samples,
+    generate and verify, at m = 257 and m = 797: the plan lol_amd.challenges builds and the same plan without the bit.
+    Also written to profiles/zq_scan_bench.jsonl."""
+    import statistics
+    import tempfile
+    L = lol_amd.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    lines = []
+
+    def tile_of(call):
+        sys.stderr.flush()
+        with tempfile.TemporaryFile() as f:
+            keep = os.dup(2)
+            os.environ["LOLHIP_ZQ_SCAN_INFO"] = "1"
+            os.dup2(f.fileno(), 2)
+            try:
+                call()
+                torch.cuda.synchronize()
+            finally:
+                os.dup2(keep, 2); os.close(keep)
+                del os.environ["LOLHIP_ZQ_SCAN_INFO"]
+            f.seek(0)
+            got = [ln for ln in f.read().decode().splitlines() if ln.startswith("k_zq_scan")]
+        return got[0] if got else ""
+
+    def emit(d):
+        lines.append(d)
+        print(json.dumps(d), flush=True)
+
+    def case(m, qs):
+        pps = lol_amd.factor_pps(m)
+        P, D = lol_amd.Plan(pps, qs, scan_zq=True), lol_amd.Plan(pps, qs)
+        B = max(8, 2 ** 22 // (P.n * P.T))
+        a = rnd(gen, qs, B, P.n)
+        y = a.clone()
+        nbytes = a.numel() * 8
+        ops = {"L": (4, L.lolhip_l_batch), "divGPow": (8, L.lolhip_divgpow_batch), "divGDec": (9, L.lolhip_divgdec_batch)}
+        for op, (code, entry) in ops.items():
+            assert P.scanRoute(code) == 1 and D.scanRoute(code) == 0
+            fns = {"scan": lambda: entry(P._h, st, y.data_ptr(), B), "scalar": lambda: entry(D._h, st, y.data_ptr(), B),
+                   "copy": lambda: L.lolhip_copy_slab(st, y.data_ptr(), a.data_ptr(), nbytes, 0)}
+            ms = {k: [] for k in fns}
+            tile = tile_of(fns["scan"])
+            assert tile and not tile_of(fns["scalar"])
+            for _ in range(3):
+                for label, fn in fns.items():
+                    y.copy_(a)
+                    assert fn() == 0
+                    ms[label].append(timeit(fn))
+            for label in fns:
+                med = statistics.median(ms[label])
+                emit({"op": op, "route": label, "config": f"m={m} n={P.n} qs={qs} B={B}", "word": 4 if max(qs) < 2 ** 32 else 8,
+                      "ms": round(med, 4), "ms_min": round(min(ms[label]), 4), "ms_max": round(max(ms[label]), 4),
+                      "alg_GBps": round(2 * nbytes / med / 1e6, 1), "tile": tile if label == "scan" else ""})
+
+    for m in (17, 67, 179, 257, 797, 2176):
+        case(m, [lol_amd.good_q(m, 2 ** 31)])
+        case(m, [lol_amd.good_q(m, 2 ** 60)])
+    # one whole Disc challenge, generate and verify, with and without the bit
+    key, I, Ls = bytes(range(32)), 32, 3
+    for m, q in ((257, 15802417), (797, 741587779)):
+        svar = 1.0 / m
+        mk = lambda scan: lol_amd.RLWE(lol_amd.Plan.for_index(m, [q], dense_gauss=True, dense_zq=True, scan_zq=scan))
+        rs = {"scan": mk(True), "scalar": mk(False)}
+        bound = lol_amd.RLWE.errorBound(m, svar, 2.0 ** -25, kind="disc")
+        data = {k: r.instances("disc", I, Ls, svar=svar, key=key, ctr_s=0, ctr=0) for k, r in rs.items()}
+        calls = {"chall_generate": lambda k: rs[k].instances("disc", I, Ls, svar=svar, key=key, ctr_s=0, ctr=0),
+                 "chall_verify": lambda k: rs[k].validInstances("disc", *data[k], bound=bound)}
+        for op, fn in calls.items():
+            ms = {k: [] for k in rs}
+            for _ in range(3):
+                for k in rs:
+                    ms[k].append(timeit(lambda: fn(k)))
+            for k in rs:
+                med = statistics.median(ms[k])
+                emit({"op": op, "route": k, "config": f"Disc m={m} q={q} I={I} L={Ls}", "ms": round(med, 4),
+                      "ms_min": round(min(ms[k]), 4), "ms_max": round(max(ms[k]), 4)})
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "zq_scan_bench.jsonl")
+    with open(out, "w") as f:
+        f.write("".join(json.dumps(x) + "\n" for x in lines))
+
+
 def main():
     gen = torch.Generator(device="cuda"); gen.manual_seed(1)
+    if "--zq-scan" in sys.argv:          # the scan route of the prime ops leg alone
+        zq_scan_leg(gen)
+        return
     if "--zq-dense" in sys.argv:         # the dense Z_q stages leg alone
         zq_dense_leg(gen)
         return
