@@ -140,7 +140,7 @@ void zq_fill(const Plan& P, const StageProgram& sp, size_t at, ZqDenseLaunch& z)
     const Stage& st = sp.stages[i];
     const ZqDenseMat* zm = zq_mat_of(P, st);
     if (zm && st.d > z.dmax) z.dmax = st.d;
-    z.kind[at + i] = !zm ? ZQ_ELT : st.rts >= 64 ? ZQ_COLS : ZQ_ROWS;
+    z.kind[at + i] = !zm ? ZQ_ELT : lanes_along_r(st) ? ZQ_COLS : ZQ_ROWS;
     z.mt_off[at + i] = zm ? zm->mt_off : -1; z.dp[at + i] = zm ? zm->dp : 0; z.pl_off[at + i] = zm ? zm->pl_off : -1;
   }
 }
@@ -225,7 +225,7 @@ int run_prog(const Plan& P, const StageProgram& sp, hipStream_t s, int64_t* y, i
     a.scan.src = (src && src != y) ? src : nullptr;
     a.scan.host_stages = sp.stages.data();
     for (size_t i = 0; i < sp.stages.size(); ++i)
-      a.scan.kind[i] = !zq_scan_stage(sp.stages[i]) ? ZS_ELT : sp.stages[i].rts >= 64 ? ZS_COLS : ZS_LANES;
+      a.scan.kind[i] = !zq_scan_stage(sp.stages[i]) ? ZS_ELT : lanes_along_r(sp.stages[i]) ? ZS_COLS : ZS_LANES;
     return hip_status(launch_generic(a));
   }
   a.zq.route = zq_dense_route(P, sp);
@@ -400,7 +400,7 @@ int64_t lolhip_plan_cplx_table(const lolhip_plan* p, int inverse, int stage, int
   if (!p || p->P.cplx_route != 2 || stage < 0 || form < 0 || form > 3) return 0;
   const Plan& P = p->P;
   const std::vector<Stage>& st = P.prog_crtc[inverse ? 1 : 0].stages;
-  if (stage >= (int)st.size() || cplx_stage_route(P.cplx_word[inverse ? 1 : 0], stage) == CPLX_REG) return 0;
+  if (stage >= (int)st.size() || stage_route(P.cplx_word[inverse ? 1 : 0], stage) == CPLX_REG) return 0;
   const Stage& s = st[(size_t)stage];
   if (s.kind == ST_DIAG || s.kind == ST_SCALE) return 0;
   const int64_t d = s.d, dpr = (d + 15) / 16 * 16, dpc = (d + 3) / 4 * 4;
@@ -496,7 +496,8 @@ int64_t lolhip_plan_table(const lolhip_plan* p, int which, int k, int64_t* out, 
         const std::vector<Stage>& st = (dir ? P.prog_crtinv : P.prog_crt).stages;
         for (size_t i = 0; i < st.size(); ++i) {
           tmp.push_back(st[i].kind); tmp.push_back(st[i].p); tmp.push_back(st[i].d); tmp.push_back(st[i].rts);
-          tmp.push_back(P.cplx_route == 2 ? cplx_stage_route(P.cplx_word[dir], (int)i) : 0);
+          const int r = P.cplx_route == 2 ? stage_route(P.cplx_word[dir], (int)i) : 0;
+          tmp.push_back(r == CPLX_VALU_COLS ? CPLX_VALU : r);       // the table tells the unit, not the layout
         }
       }
       src = &tmp;
@@ -662,7 +663,7 @@ int lolhip_gaussian_dec_batch(const lolhip_plan* p, void* stream, double* y, int
   if (!p->P.gauss_route) return LOLHIP_ERR_INVALID;           // n > 8192, or a prime > 13 on a plan that has not opted in
   if (B < 0 || (B > 0 && !y)) return LOLHIP_ERR_INVALID;
   const Plan& P = p->P;
-  return hip_status(launch_gauss((hipStream_t)stream, y, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages,
+  return hip_status(launch_gauss((hipStream_t)stream, y, B, P.n, P.prog_gauss.d_stages, P.gauss_word,
                                  P.d_rconsts));
 }
 

@@ -177,7 +177,7 @@ int lolhip_chall_generate_batch(const lolhip_plan* pq, void* stream, int kind, i
       double* g = reinterpret_cast<double*>(c.e);
       if (launch_enc_gauss(s, g, B, n, k, ctr, CHACHA_DOM_RLWE_GAUSS, deviation(P, svar)) != hipSuccess) return LOLHIP_ERR_HIP;
       if (!two_power(P) &&
-          launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
+          launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.gauss_word, P.d_rconsts) != hipSuccess)
         return LOLHIP_ERR_HIP;
       if (launch_rlwe_cont_sample(s, x, g, static_cast<double*>(b_out), B * n, (double)P.qs[0]) != hipSuccess)
         return LOLHIP_ERR_HIP;
@@ -292,7 +292,7 @@ int lolhip_chall_ring_generate_batch(const lolhip_ringmul* h, const lolhip_plan*
       double* g = reinterpret_cast<double*>(c.e);
       if (launch_enc_gauss(s, g, B, n, t.key, ctr, CHACHA_DOM_RLWE_GAUSS, t.sigma) != hipSuccess) return LOLHIP_ERR_HIP;
       if (!two_power(P) &&
-          launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
+          launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.gauss_word, P.d_rconsts) != hipSuccess)
         return LOLHIP_ERR_HIP;
       if (launch_rlwe_cont_sample(s, c.x, g, static_cast<double*>(b_out), B * n, (double)P.qs[0]) != hipSuccess)
         return LOLHIP_ERR_HIP;

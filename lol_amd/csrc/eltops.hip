@@ -19,13 +19,13 @@
 //                   beyond the LDS, and forced by the ELT_GLOBAL switch.  Same vec_op, same bits.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 #include "elementwise_dev.h"
 #include "eltops.h"
+#include "kernel_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -280,17 +280,8 @@ hipError_t launch_lds(const EltLaunch& a, double dr, u64 dinv, i64 qmax) {
   const size_t lds = (size_t)padded(G * nW) * sizeof(E);
   if (lds + ELT_GROUP * sizeof(int) > ELT_LDS_BYTES) return hipErrorInvalidValue;   // bad[] is static LDS
   if (lds > 64 * 1024) {
-    int dev = -1;
-    hipError_t er = hipGetDevice(&dev);
+    hipError_t er = allow_big_lds<&k_elt_lds<OP, E>>((int)(ELT_LDS_BYTES - ELT_GROUP * sizeof(int)));
     if (er != hipSuccess) return er;
-    static std::atomic<unsigned long long> done{0};
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!(done.load(std::memory_order_acquire) >> dev & 1)) {
-      er = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_elt_lds<OP, E>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(ELT_LDS_BYTES - ELT_GROUP * sizeof(int)));
-      if (er != hipSuccess) return er;
-      done.fetch_or(1ull << dev, std::memory_order_release);
-    }
   }
   const unsigned threads = lds <= 40 * 1024 ? 256 : lds <= 80 * 1024 ? 512 : 1024;
   const i64 chunks = (a.B + G - 1) / G;

@@ -24,17 +24,16 @@
 // stages of the small primes, in one launch.  Tolerance contract, so each route sums in its own order.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
+#include "kernel_dev.h"
 #include "kernels.h"
+#include "tile_dev.h"
 
 namespace lolhip {
 
 namespace {
-
-__device__ __forceinline__ int fdiv40(int x, u64 M) { return (int)(((u64)(u32)x * M) >> 40); }   // x / v, M = floor(2^40/v)+1
 
 struct cd { double re, im; };
 __device__ __forceinline__ cd cmul(cd a, cd b) { return cd{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
@@ -157,90 +156,35 @@ k_gauss(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages, 
 }
 
 // ---- dense stages of tensorGaussianDec ---------------------------------------------------------
-// out[col, row] = (sum_c M[row d + c] v[col, c]) / sqrt 2 over the columns col = (item, blk, r) of the tile, element c of
-// a column at item n + blk d rts + c rts + r.  src is the LDS tile; dst is the other LDS buffer or, for the last stage
-// of the program, the slab itself (same layout), so a stage never runs in place.
+// out[col, row] = (sum_c M[row d + c] v[col, c]) / sqrt 2 over the columns of the tile (tile_dev.h), in either layout:
+// the matrix is the transposed copy for the rows layout, src the LDS tile, dst the other LDS buffer or the slab.
 constexpr int GD_J = 8;          // register tile: columns (rows layout) or rows (cols layout) per thread
 
-__device__ __forceinline__ u64 magic40_dev(int v) { return ((u64)1 << 40) / (u64)(v > 0 ? v : 1) + 1; }
-
-// base address of column col: nq = n / d columns per item
-__device__ __forceinline__ int gauss_col_base(const Stage& st, int col, int n, int nq, u64 m_nq) {
-  const int item = fdiv40(col, m_nq), q = col - item * nq;
-  const int blk = fdiv40(q, st.m_rts), r = q - blk * st.rts;
-  return item * n + blk * st.d * st.rts + r;
+__device__ __forceinline__ void gauss_dense(const Stage& st, bool cols, const double* __restrict__ src, double* __restrict__ dst,
+                                            int n, int items, const double* __restrict__ cst) {
+  const int d = st.d;
+  auto dots = [&](const double* __restrict__ M) {
+    return [&, M](auto mat, auto in, double (&acc)[GD_J]) {
+#pragma unroll
+      for (int j = 0; j < GD_J; ++j) acc[j] = 0.0;
+      for (int c = 0; c < d; ++c) {
+#pragma unroll
+        for (int j = 0; j < GD_J; ++j) acc[j] = fma(M[mat(c, j)], src[in(c, j)], acc[j]);
+      }
+    };
+  };
+  auto put = [&](int x, int, double v) { dst[x] = v / 1.4142135623730951; };
+  if (!cols) tile_dense_rows<GD_J, double>(st, n, items, dots(cst + st.wp_off), put);
+  else tile_dense_cols<GD_J, double>(st, n, items, dots(cst + st.mat_off), put);
 }
 
-// Lanes along the rows (stride below a wave): a thread owns one output row across GD_J columns.  The matrix element
-// comes from the transposed copy (consecutive lanes, consecutive words) and feeds GD_J multiply-adds; the GD_J inputs
-// are LDS reads at an address the lanes of one column group share (a broadcast).
-__device__ __forceinline__ void gauss_dense_rows(const Stage& st, const double* __restrict__ src, double* __restrict__ dst,
-                                                 int n, int items, const double* __restrict__ cst) {
-  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq, ngroups = (ncols + GD_J - 1) / GD_J;
-  const u64 m_nq = magic40_dev(nq);
-  const double* __restrict__ Mt = cst + st.wp_off;
-  for (int w = threadIdx.x; w < d * ngroups; w += blockDim.x) {
-    const int cg = fdiv40(w, st.m_d), row = w - cg * d;
-    int base[GD_J];
-    double acc[GD_J];
-#pragma unroll
-    for (int j = 0; j < GD_J; ++j) {
-      const int col = cg * GD_J + j;
-      base[j] = gauss_col_base(st, col < ncols ? col : ncols - 1, n, nq, m_nq);      // a dead column re-reads the last live one
-      acc[j] = 0.0;
-    }
-    for (int c = 0; c < d; ++c) {
-      const double m = Mt[c * d + row];
-#pragma unroll
-      for (int j = 0; j < GD_J; ++j) acc[j] = fma(m, src[base[j] + c * rts], acc[j]);
-    }
-#pragma unroll
-    for (int j = 0; j < GD_J; ++j)
-      if (cg * GD_J + j < ncols) dst[base[j] + row * rts] = acc[j] / 1.4142135623730951;
-  }
-}
-
-// Lanes along r (stride of at least a wave): a wave owns GD_J rows of 64 consecutive columns.  The input is one
-// conflict-free LDS read per thread and feeds GD_J multiply-adds; the GD_J matrix elements are wave-uniform.
-__device__ __forceinline__ void gauss_dense_cols(const Stage& st, const double* __restrict__ src, double* __restrict__ dst,
-                                                 int n, int items, const double* __restrict__ cst) {
-  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq;
-  const int nrg = (d + GD_J - 1) / GD_J, nchunks = (ncols + 63) >> 6;
-  const u64 m_nq = magic40_dev(nq);
-  const double* __restrict__ M = cst + st.mat_off;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
-  const int nwaves = (int)(blockDim.x >> 6);
-  for (int wi = wave; wi < nrg * nchunks; wi += nwaves) {
-    const int rg = wi / nchunks, chunk = wi - rg * nchunks, row0 = rg * GD_J;
-    const int col = chunk * 64 + lane;
-    const int base = gauss_col_base(st, col < ncols ? col : ncols - 1, n, nq, m_nq);
-    int moff[GD_J];
-    double acc[GD_J];
-#pragma unroll
-    for (int j = 0; j < GD_J; ++j) {
-      moff[j] = (row0 + j < d ? row0 + j : d - 1) * d;                                // a dead row re-reads the last live one
-      acc[j] = 0.0;
-    }
-    for (int c = 0; c < d; ++c) {
-      const double v = src[base + c * rts];
-#pragma unroll
-      for (int j = 0; j < GD_J; ++j) acc[j] = fma(M[moff[j] + c], v, acc[j]);
-    }
-    if (col < ncols) {
-#pragma unroll
-      for (int j = 0; j < GD_J; ++j)
-        if (row0 + j < d) dst[base + (row0 + j) * rts] = acc[j] / 1.4142135623730951;
-    }
-  }
-}
-
-// One tile of `items` polynomials per workgroup pass.  routes: the route word of launch_gauss (kernels.h).  nbuf = 2 when
+// One tile of `items` polynomials per workgroup pass.  word: the stage word of launch_gauss (kernels.h).  nbuf = 2 when
 // a dense stage is followed by another stage (LDS ping-pong); the last stage, when dense, writes the slab directly.
 __global__ void __launch_bounds__(256)
-k_gauss_dense(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages, int routes, const double* __restrict__ cst,
+k_gauss_dense(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages, int word, const double* __restrict__ cst,
               int items) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int nstages = routes & 255;
+  const int nstages = word & 255;
   const i64 ntiles = (B + items - 1) / items;
   for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const i64 b0 = t * items;
@@ -253,7 +197,7 @@ k_gauss_dense(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ st
     bool in_lds = true;
     for (int s = 0; s < nstages; ++s) {
       const Stage st = stages[s];
-      const int route = (routes >> (8 + 2 * s)) & 3;            // gauss_stage_route (kernels.h)
+      const int route = stage_route(word, s);
       if (route == GAUSS_REG) {
         const int nvec = n / st.d;
         const u64 m_nvec = magic40_dev(nvec);
@@ -272,8 +216,7 @@ k_gauss_dense(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ st
       } else {
         const bool last = s == nstages - 1;
         double* dst = last ? yt : oth;
-        if (route == GAUSS_ROWS) gauss_dense_rows(st, cur, dst, n, live, cst);
-        else gauss_dense_cols(st, cur, dst, n, live, cst);
+        gauss_dense(st, route != GAUSS_ROWS, cur, dst, n, live, cst);
         if (last) in_lds = false;
         else { double* t2 = cur; cur = oth; oth = t2; }
       }
@@ -292,13 +235,6 @@ k_gauss_dense(double* __restrict__ y, i64 B, int n, const Stage* __restrict__ st
 // path is a tolerance, not a bit pattern (include/lolhip.h), so the order of summation is each route's own.
 constexpr int CD_J = 4;          // register tile of the vector-ALU routes: 4 complex accumulators per thread
 
-// column col of the tile: tile-relative (base) and polynomial-relative (loc) position of its element 0
-__device__ __forceinline__ void cplx_col(const Stage& st, int col, int n, int nq, u64 m_nq, int& base, int& loc) {
-  const int item = fdiv40(col, m_nq), q = col - item * nq;
-  const int blk = fdiv40(q, st.m_rts), r = q - blk * st.rts;
-  loc = blk * st.d * st.rts + r;
-  base = item * n + loc;
-}
 // entry of the stage's folded diagonal at position x of the polynomial (as cplx_stage_vec applies it)
 __device__ __forceinline__ cd cplx_tw(const Stage& st, const cd* __restrict__ cst, int x) {
   const int xd = fdiv40(x, st.m_twdiv);
@@ -309,75 +245,26 @@ __device__ __forceinline__ void cplx_fma(cd& acc, cd m, cd v) {
   acc.im = fma(m.re, v.im, fma(m.im, v.re, acc.im));
 }
 
-// Vector ALU, lanes along the rows (stride below a wave): a thread owns one output row across CD_J columns; the matrix
-// element comes from the transposed copy (consecutive lanes, consecutive entries).
-__device__ __forceinline__ void cplx_dense_rows(const Stage& st, const cd* __restrict__ src, cd* __restrict__ dst, int n, int items,
-                                                const cd* __restrict__ cst) {
-  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq, ngroups = (ncols + CD_J - 1) / CD_J;
-  const u64 m_nq = magic40_dev(nq);
-  const cd* __restrict__ Mt = cst + st.wp_off;
-  for (int w = threadIdx.x; w < d * ngroups; w += blockDim.x) {
-    const int cg = fdiv40(w, st.m_d), row = w - cg * d;
-    int base[CD_J], loc[CD_J];
-    cd acc[CD_J];
+// Vector ALU, either layout (tile_dev.h): the matrix is the transposed copy for the rows layout
+__device__ __forceinline__ void cplx_dense_valu(const Stage& st, bool cols, const cd* __restrict__ src, cd* __restrict__ dst, int n,
+                                                int items, const cd* __restrict__ cst) {
+  const int d = st.d;
+  auto dots = [&](const cd* __restrict__ M) {
+    return [&, M](auto mat, auto in, cd (&acc)[CD_J]) {
 #pragma unroll
-    for (int j = 0; j < CD_J; ++j) {
-      const int col = cg * CD_J + j;
-      cplx_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq, base[j], loc[j]);       // a dead column re-reads the last live one
-      acc[j] = cd{0.0, 0.0};
-    }
-    for (int c = 0; c < d; ++c) {
-      const cd m = Mt[c * d + row];
+      for (int j = 0; j < CD_J; ++j) acc[j] = cd{0.0, 0.0};
+      for (int c = 0; c < d; ++c) {
 #pragma unroll
-      for (int j = 0; j < CD_J; ++j) cplx_fma(acc[j], m, src[base[j] + c * rts]);
-    }
-#pragma unroll
-    for (int j = 0; j < CD_J; ++j)
-      if (cg * CD_J + j < ncols) {
-        cd o = acc[j];
-        if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc[j] + row * rts));
-        dst[base[j] + row * rts] = o;
+        for (int j = 0; j < CD_J; ++j) cplx_fma(acc[j], M[mat(c, j)], src[in(c, j)]);
       }
-  }
-}
-
-// Vector ALU, lanes along r (stride of at least a wave): a wave owns CD_J rows of 64 consecutive columns; the matrix
-// elements are wave-uniform.
-__device__ __forceinline__ void cplx_dense_cols(const Stage& st, const cd* __restrict__ src, cd* __restrict__ dst, int n, int items,
-                                                const cd* __restrict__ cst) {
-  const int d = st.d, rts = st.rts, nq = n / d, ncols = items * nq;
-  const int nrg = (d + CD_J - 1) / CD_J, nchunks = (ncols + 63) >> 6;
-  const u64 m_nq = magic40_dev(nq);
-  const cd* __restrict__ M = cst + st.mat_off;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
-  const int nwaves = (int)(blockDim.x >> 6);
-  for (int wi = wave; wi < nrg * nchunks; wi += nwaves) {
-    const int rg = wi / nchunks, chunk = wi - rg * nchunks, row0 = rg * CD_J;
-    const int col = chunk * 64 + lane;
-    int base, loc;
-    cplx_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq, base, loc);
-    int moff[CD_J];
-    cd acc[CD_J];
-#pragma unroll
-    for (int j = 0; j < CD_J; ++j) {
-      moff[j] = (row0 + j < d ? row0 + j : d - 1) * d;                                // a dead row re-reads the last live one
-      acc[j] = cd{0.0, 0.0};
-    }
-    for (int c = 0; c < d; ++c) {
-      const cd v = src[base + c * rts];
-#pragma unroll
-      for (int j = 0; j < CD_J; ++j) cplx_fma(acc[j], M[moff[j] + c], v);
-    }
-    if (col < ncols) {
-#pragma unroll
-      for (int j = 0; j < CD_J; ++j)
-        if (row0 + j < d) {
-          cd o = acc[j];
-          if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc + (row0 + j) * rts));
-          dst[base + (row0 + j) * rts] = o;
-        }
-    }
-  }
+    };
+  };
+  auto put = [&](int x, int loc, cd o) {
+    if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc));
+    dst[x] = o;
+  };
+  if (cols) tile_dense_cols<CD_J, cd>(st, n, items, dots(cst + st.mat_off), put);
+  else tile_dense_rows<CD_J, cd>(st, n, items, dots(cst + st.wp_off), put);
 }
 
 // Matrix cores: v_mfma_f64_16x16x4_f64, D (16 x 16) += A (16 x 4) B (4 x 16).  Lane l holds A[l & 15][l >> 4],
@@ -414,8 +301,7 @@ __device__ __forceinline__ void cplx_dense_mfma(const Stage& st, const cd* __res
 #pragma unroll
     for (int t = 0; t < CM_CT; ++t) {
       const int col = (cg * CM_CT + t) * 16 + li;
-      int loc;
-      cplx_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq, base[t], loc);
+      base[t] = tile_col(st, col < ncols ? col : ncols - 1, n, nq, m_nq).base;
       are[t] = cplx_d4{0.0, 0.0, 0.0, 0.0};
       aim[t] = cplx_d4{0.0, 0.0, 0.0, 0.0};
     }
@@ -447,11 +333,10 @@ __device__ __forceinline__ void cplx_dense_mfma(const Stage& st, const cd* __res
         const int row = rt * 16 + (tr ? li : lk + 4 * reg);
         const int col = (cg * CM_CT + t) * 16 + (tr ? lk + 4 * reg : li);
         if (row < d && col < ncols) {
-          int b, loc;
-          cplx_col(st, col, n, nq, m_nq, b, loc);
+          const TileCol tc = tile_col(st, col, n, nq, m_nq);
           cd o = cd{are[t][reg], aim[t][reg]};
-          if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, loc + row * rts));
-          dst[b + row * rts] = o;
+          if (st.tw_off >= 0) o = cmul(o, cplx_tw(st, cst, tc.loc + row * rts));
+          dst[tc.base + row * rts] = o;
         }
       }
     }
@@ -477,7 +362,7 @@ k_cplx_dense(cd* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages,
     bool in_lds = true;
     for (int s = 0; s < nstages; ++s) {
       const Stage st = stages[s];
-      const int route = (word >> (8 + 2 * s)) & 3;              // cplx_stage_route (kernels.h)
+      const int route = stage_route(word, s);
       if (st.kind == ST_DIAG || st.kind == ST_SCALE) {
         for (int x = threadIdx.x; x < live * n; x += blockDim.x)
           cur[x] = cmul(cur[x], cplx_tw(st, cst, x - fdiv40(x, m_n) * n));
@@ -505,8 +390,7 @@ k_cplx_dense(cd* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages,
         const bool last = s == nstages - 1;
         cd* dst = last ? yt : oth;
         if (route == CPLX_MFMA) cplx_dense_mfma(st, cur, dst, n, live, cst);
-        else if (st.rts >= 64) cplx_dense_cols(st, cur, dst, n, live, cst);
-        else cplx_dense_rows(st, cur, dst, n, live, cst);
+        else cplx_dense_valu(st, route == CPLX_VALU_COLS, cur, dst, n, live, cst);
         if (last) in_lds = false;
         else { cd* t2 = cur; cur = oth; oth = t2; }
       }
@@ -520,30 +404,14 @@ k_cplx_dense(cd* __restrict__ y, i64 B, int n, const Stage* __restrict__ stages,
 
 }  // namespace
 
-// k_cplx / k_gauss_dense / k_cplx_dense with more than 64 KiB of dynamic LDS: the attribute, once per device
-template <typename K>
-static hipError_t allow_big_lds(K kernel, std::atomic<unsigned long long>& done, int bytes = 128 * 1024) {
-  int dev = -1;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!(done.load(std::memory_order_acquire) >> dev & 1)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    done.fetch_or(1ull << dev, std::memory_order_release);
-  }
-  return hipSuccess;
-}
-
-hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* cconsts) {
-  const int ns = nstages & 255;
+hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int word, const double* cconsts) {
+  const int ns = word & 255;
   if (B == 0 || ns == 0) return hipSuccess;
   const bool info = getenv("LOLHIP_CPLX_INFO") != nullptr;
-  if ((nstages >> 8) == 0) {                                // register stages only
+  if ((word >> 8) == 0) {                                   // register stages only
     const size_t lds = (size_t)n * sizeof(cd);
     if (lds > 64 * 1024) {
-      static std::atomic<unsigned long long> done{0};
-      hipError_t e = allow_big_lds(&k_cplx, done);
+      hipError_t e = allow_big_lds<&k_cplx>(128 * 1024);
       if (e != hipSuccess) return e;
     }
     i64 grid = B < 4096 ? B : 4096;
@@ -558,41 +426,34 @@ hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stag
   // batch; one item where a polynomial (or its ping-pong pair) is larger than that (up to CPLX_LDS_BUDGET: plan.cpp).
   int nbuf = 1;
   for (int i = 0; i + 1 < ns; ++i)
-    if (cplx_stage_route(nstages, i) != CPLX_REG) nbuf = 2;
+    if (stage_route(word, i) != CPLX_REG) nbuf = 2;
   const size_t per = (size_t)nbuf * (size_t)n * sizeof(cd);
-  i64 cap = (i64)(64 * 1024 / per);
-  i64 items = (B + 511) / 512;
-  if (items > cap) items = cap;
-  if (items > B) items = B;
-  if (items < 1) items = 1;
+  const i64 items = tile_items(B, (i64)(64 * 1024 / per), 1);
   const size_t lds = per * (size_t)items;
   if (lds > CPLX_LDS_BUDGET) return hipErrorInvalidValue;   // excluded on the host (Plan::cplx_route)
   if (lds > 64 * 1024) {
-    static std::atomic<unsigned long long> done{0};
-    hipError_t e = allow_big_lds(&k_cplx_dense, done, (int)CPLX_LDS_BUDGET);
+    hipError_t e = allow_big_lds<&k_cplx_dense>((int)CPLX_LDS_BUDGET);
     if (e != hipSuccess) return e;
   }
   const i64 ntiles = (B + items - 1) / items;
   const i64 grid = ntiles < 4096 ? ntiles : 4096;
   if (info) {
     char line[320];
-    int at = snprintf(line, sizeof(line), "k_cplx_dense: n %lld, B %lld, items %lld, bufs %d, lds %zu B, grid %lld, stages",
-                      (long long)n, (long long)B, (long long)items, nbuf, lds, (long long)grid);
-    static const char* const names[4] = {"reg", "dense-valu", "dense-mfma", "?"};
-    for (int i = 0; i < ns && at > 0 && at < (int)sizeof(line); ++i)
-      at += snprintf(line + at, sizeof(line) - (size_t)at, " %s", names[cplx_stage_route(nstages, i)]);
-    fprintf(stderr, "%s\n", line);
+    const int at = snprintf(line, sizeof(line), "k_cplx_dense: n %lld, B %lld, items %lld, bufs %d, lds %zu B, grid %lld, stages",
+                            (long long)n, (long long)B, (long long)items, nbuf, lds, (long long)grid);
+    static const char* const names[4] = {"reg", "dense-valu", "dense-mfma", "dense-valu"};
+    tile_info(line, at, ns, [&](char* p, size_t room, int i) { return snprintf(p, room, " %s", names[stage_route(word, i)]); });
   }
-  hipLaunchKernelGGL(k_cplx_dense, dim3((unsigned)grid), dim3(256), lds, s, reinterpret_cast<cd*>(y), B, (int)n, stages, nstages,
+  hipLaunchKernelGGL(k_cplx_dense, dim3((unsigned)grid), dim3(256), lds, s, reinterpret_cast<cd*>(y), B, (int)n, stages, word,
                      reinterpret_cast<const cd*>(cconsts), (int)items);
   return hipGetLastError();
 }
 
-hipError_t launch_gauss(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* rconsts) {
-  const int ns = nstages & 255;
+hipError_t launch_gauss(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int word, const double* rconsts) {
+  const int ns = word & 255;
   if (B == 0 || ns == 0) return hipSuccess;
   const bool info = getenv("LOLHIP_GAUSS_INFO") != nullptr;
-  if ((nstages >> 8) == 0) {                                // register stages only
+  if ((word >> 8) == 0) {                                   // register stages only
     const size_t lds = (size_t)n * sizeof(double);          // <= 64 KiB
     i64 grid = B < 4096 ? B : 4096;
     if (info) fprintf(stderr, "k_gauss: n %lld, B %lld, stages reg\n", (long long)n, (long long)B);
@@ -605,35 +466,26 @@ hipError_t launch_gauss(hipStream_t s, double* y, i64 B, i64 n, const Stage* sta
   int nbuf = 1;
   bool rows = false;
   for (int i = 0; i < ns; ++i) {
-    if (i + 1 < ns && gauss_stage_route(nstages, i) != GAUSS_REG) nbuf = 2;
-    if (gauss_stage_route(nstages, i) == GAUSS_ROWS) rows = true;
+    if (i + 1 < ns && stage_route(word, i) != GAUSS_REG) nbuf = 2;
+    if (stage_route(word, i) == GAUSS_ROWS) rows = true;
   }
   const size_t per = (size_t)nbuf * (size_t)n * sizeof(double);          // <= 128 KiB (n <= 8192)
-  i64 cap = (i64)((rows ? 64 : 32) * 1024 / per);
-  i64 want = (B + 511) / 512;
-  want = (want + GD_J - 1) / GD_J * GD_J;
-  i64 items = want < cap ? want : cap;
-  if (items > GD_J) items = items / GD_J * GD_J;
-  if (items > B) items = B;
-  if (items < 1) items = 1;
+  const i64 items = tile_items(B, (i64)((rows ? 64 : 32) * 1024 / per), GD_J);
   const size_t lds = per * (size_t)items;
   if (lds > 64 * 1024) {
-    static std::atomic<unsigned long long> done{0};
-    hipError_t e = allow_big_lds(&k_gauss_dense, done);
+    hipError_t e = allow_big_lds<&k_gauss_dense>(128 * 1024);
     if (e != hipSuccess) return e;
   }
   const i64 ntiles = (B + items - 1) / items;
   const i64 grid = ntiles < 4096 ? ntiles : 4096;
   if (info) {
     char line[256];
-    int at = snprintf(line, sizeof(line), "k_gauss_dense: n %lld, B %lld, items %lld, bufs %d, lds %zu B, grid %lld, stages",
-                      (long long)n, (long long)B, (long long)items, nbuf, lds, (long long)grid);
+    const int at = snprintf(line, sizeof(line), "k_gauss_dense: n %lld, B %lld, items %lld, bufs %d, lds %zu B, grid %lld, stages",
+                            (long long)n, (long long)B, (long long)items, nbuf, lds, (long long)grid);
     static const char* const names[4] = {"reg", "dense-rows", "dense-cols", "?"};
-    for (int i = 0; i < ns && at > 0 && at < (int)sizeof(line); ++i)
-      at += snprintf(line + at, sizeof(line) - (size_t)at, " %s", names[gauss_stage_route(nstages, i)]);
-    fprintf(stderr, "%s\n", line);
+    tile_info(line, at, ns, [&](char* p, size_t room, int i) { return snprintf(p, room, " %s", names[stage_route(word, i)]); });
   }
-  hipLaunchKernelGGL(k_gauss_dense, dim3((unsigned)grid), dim3(256), lds, s, y, B, (int)n, stages, nstages, rconsts, (int)items);
+  hipLaunchKernelGGL(k_gauss_dense, dim3((unsigned)grid), dim3(256), lds, s, y, B, (int)n, stages, word, rconsts, (int)items);
   return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 
 #include "pipeline.h"
 #include "plan.h"
+#include "tile_host.h"
 
 namespace lolhip {
 
@@ -153,21 +154,19 @@ bool mixed_keyswitch_big_ok(i64 n);
 hipError_t launch_mixed_keyswitch(const MixedKeySwitchLaunch& a);
 hipError_t launch_mixed(const MixedLaunch& a);
 
-// floating-point side (floatpath.hip): y [B][n] complex doubles (re, im interleaved) / doubles, in place
-// launch_cplx: as launch_gauss below, the low 8 bits of nstages are the number of stages and above them sit two bits per
-// stage, its route.  A plain count (every stage CPLX_REG) launches k_cplx, as it always did; a word with a dense stage
-// launches k_cplx_dense over Plan::prog_crtc (plan.h), whose dense stages carry the offsets of their matrix forms in
-// the complex pool.  LOLHIP_CPLX_INFO prints one line per launch.
-enum CplxRoute : int { CPLX_REG = 0, CPLX_VALU = 1, CPLX_MFMA = 2 };      // register vectors; dense on the vector ALU / on the matrix cores
-inline int cplx_stage_route(int nstages, int s) { return (nstages >> (8 + 2 * s)) & 3; }
-hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* cconsts);
-// launch_gauss: the low 8 bits of nstages are the number of stages; above them sit two bits per stage, its route
-// (gauss_stage_route).  A program of register stages therefore passes its plain count.  plan_upload packs the word
-// into StageProgram::nstages of prog_gauss: the launcher sees only device copies of the stages, and the routes are what
-// pick the kernel, its LDS tile and the info line (LOLHIP_GAUSS_INFO).
+// floating-point side (floatpath.hip): y [B][n] complex doubles (re, im interleaved) / doubles, in place.  `word` is a
+// stage word (stage_route, tile_host.h): the routes are what pick the kernel, its LDS tile and the info line.
+// launch_cplx: a plain count (every stage CPLX_REG) launches k_cplx, as it always did; a word with a dense stage
+// (Plan::cplx_word) launches k_cplx_dense over Plan::prog_crtc (plan.h), whose dense stages carry the offsets of their
+// matrix forms in the complex pool.  LOLHIP_CPLX_INFO prints one line per launch.
+// register vectors; dense on the vector ALU, lanes along the rows; dense on the matrix cores; the vector ALU, lanes along r.
+// Two values mean the vector ALU: ask a route whether it is CPLX_REG or CPLX_MFMA, never whether it is CPLX_VALU.
+enum CplxRoute : int { CPLX_REG = 0, CPLX_VALU = 1, CPLX_MFMA = 2, CPLX_VALU_COLS = 3 };
+hipError_t launch_cplx(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int word, const double* cconsts);
+// launch_gauss: Plan::gauss_word over Plan::prog_gauss; a plain count launches k_gauss.  LOLHIP_GAUSS_INFO prints one
+// line per launch.
 enum GaussRoute : int { GAUSS_REG = 0, GAUSS_ROWS = 1, GAUSS_COLS = 2 };   // register vectors; dense, lanes along rows / along r
-inline int gauss_stage_route(int nstages, int s) { return (nstages >> (8 + 2 * s)) & 3; }
-hipError_t launch_gauss(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int nstages, const double* rconsts);
+hipError_t launch_gauss(hipStream_t s, double* y, i64 B, i64 n, const Stage* stages, int word, const double* rconsts);
 
 // 16-byte-per-lane copy of a slab: the measured ceiling of a read-once/write-once kernel (bench.py's yardstick)
 hipError_t launch_copy16(hipStream_t s, void* dst, const void* src, size_t bytes, int variant);

@@ -214,11 +214,7 @@ static hipError_t launch_keyswitch_L(const KeySwitchLaunch& a) {
   const i64 grid = (items + PPW - 1) / PPW;
   if (grid == 0) return hipSuccess;
   if (lds_bytes > 64 * 1024) {
-    static KernelDev tab[MAX_DEV];
-    hipError_t e = kernel_dev_setup(tab, [&]() -> hipError_t {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_keyswitch<L, AR>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    });
+    hipError_t e = allow_big_lds<&k_keyswitch<L, AR>>((int)lds_bytes);
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL((k_keyswitch<L, AR>), dim3((unsigned)grid), dim3(NT * PPW), lds_bytes, a.stream, a.c2, a.hint,

@@ -670,7 +670,7 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
           // conditions, so that every stage has both dense routes to compare; CPLX_DENSE_VALU wins over everything.
           const size_t per = nbufs[dir] * (size_t)P.n * 16, items = per < 64 * 1024 ? 64 * 1024 / per : 1;
           const bool wide = s.d >= CPLX_MFMA_MIN_D && items * (size_t)(P.n / s.d) >= (size_t)CPLX_MFMA_MIN_COLS;
-          word |= ((!valu && (force || wide)) ? CPLX_MFMA : CPLX_VALU) << (8 + 2 * (int)i);
+          word |= ((!valu && (force || wide)) ? CPLX_MFMA : lanes_along_r(s) ? CPLX_VALU_COLS : CPLX_VALU) << (8 + 2 * (int)i);
         }
         P.prog_crtc[dir].stages = st;
         P.cplx_word[dir] = word;
@@ -717,6 +717,9 @@ int plan_build_host(Plan& P, const std::vector<PP>& pps, const std::vector<u64>&
     }
     finish(pb.st);
     P.prog_gauss.stages = pb.st;
+    P.gauss_word = (int)pb.st.size();
+    for (size_t si = 0; si < pb.st.size() && si < 12; ++si)
+      if (pb.st[si].wp_off) P.gauss_word |= (lanes_along_r(pb.st[si]) ? GAUSS_COLS : GAUSS_ROWS) << (8 + 2 * (int)si);
   }
 
   P.is_pow2 = P.has_crt && K == 1 && pps[0].p == 2 && pps[0].e >= 5 && pps[0].e <= 15;
@@ -868,11 +871,6 @@ int plan_upload(Plan& P) {
   if ((rc = P.d_rconsts.upload(P.host_rconsts))) return rc;
   if (!P.host_zq_mt.empty() && (rc = P.d_zq_mt.upload(P.host_zq_mt))) return rc;
   if (!P.host_zq_planes.empty() && (rc = P.d_zq_planes.upload(P.host_zq_planes))) return rc;
-  // the route word of launch_gauss (kernels.h): a dense stage runs with lanes along r where the stride fills a wave
-  for (size_t si = 0; si < P.prog_gauss.stages.size() && si < 12; ++si) {
-    const Stage& st = P.prog_gauss.stages[si];
-    if (st.wp_off) P.prog_gauss.nstages |= (st.rts >= 64 ? GAUSS_COLS : GAUSS_ROWS) << (8 + 2 * (int)si);
-  }
   if ((rc = P.d_gcrt.upload(P.gcrt))) return rc;
   if ((rc = P.d_ginvcrt.upload(P.ginvcrt))) return rc;
   if ((rc = P.d_lift.upload(P.lift_consts))) return rc;

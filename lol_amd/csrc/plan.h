@@ -168,6 +168,7 @@ struct Plan {
   // one predicate per family (one LDS-resident polynomial each).  gauss_route: 0 refused; 1 n <= 8192 and register stages only (every odd prime <= 13); 2 n <= 8192, the
   // plan was created with LOLHIP_PLAN_DENSE_GAUSS and an odd prime (below 2^15) takes the dense stage: a prime above
   // 13, or every odd prime under the GAUSS_DENSE switch.  A function of (pps, flags, switch), so host-only plans have it.
+  // gauss_word is launch_gauss's stage word over prog_gauss (kernels.h), as cplx_word below.
   uint32_t flags = 0;                       // LOLHIP_PLAN_* of lolhip_plan_create_flags
   // dense Z_q stages at primes above 13 (lolhip_plan_create_routes, LOLHIP_ROUTE_DENSE_ZQ).  Built by plan_build_host for
   // opted-in plans with n <= 8192 only; empty otherwise.  zq_W: limbs of the matrix-core form (2..4), 0 when a modulus
@@ -181,7 +182,7 @@ struct Plan {
   int zq_W = 0, zq_fold = 0;
   DevBuf<u64> d_zq_mt;
   DevBuf<int8_t> d_zq_planes;
-  int gauss_route = 0;
+  int gauss_route = 0, gauss_word = 0;
   // crtC / crtInvC (floatpath.hip).  cplx_route: 0 refused; 1 n <= 8192 and every prime <= 13: k_cplx, register stages
   // only; 2 the plan was created with LOLHIP_PLAN_DENSE_CPLX and at least one stage is dense (a DFT_p, CRT_p or CRT_p^-1 of a prime above 13): every
   // prime <= CPLX_DENSE_MAX_P, both programs <= CPLX_MAX_STAGES stages and nbuf * 16 n <= CPLX_LDS_BUDGET bytes, nbuf = 2

@@ -12,9 +12,8 @@
 //   k_rlwr_*         the rounding R_q -> R_p of RLWR.hs:34-44, written out or compared and counted per sample
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "elementwise_dev.h"
+#include "kernel_dev.h"
 #include "rlwe.h"
 #include "rlwe_dev.h"
 #include "rng_dev.h"
@@ -149,18 +148,8 @@ hipError_t launch_gsqnorm(hipStream_t st, const V* e, V* out, i64 B, i64 n, cons
   }
   const size_t lds = (size_t)S * (size_t)n * sizeof(V);
   if (lds > 64 * 1024) {
-    // per device, as for every kernel that needs more than 64 KiB of LDS
-    int dev = -1;
-    hipError_t er = hipGetDevice(&dev);
+    hipError_t er = allow_big_lds<&k_gsqnorm<V>>(128 * 1024);
     if (er != hipSuccess) return er;
-    static std::atomic<unsigned long long> done{0};
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!(done.load(std::memory_order_acquire) >> dev & 1)) {
-      er = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gsqnorm<V>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               128 * 1024);
-      if (er != hipSuccess) return er;
-      done.fetch_or(1ull << dev, std::memory_order_release);
-    }
   }
   const i64 tiles = (B + S - 1) / S;
   const unsigned grid = (unsigned)(tiles < NORM_GRID ? tiles : NORM_GRID);

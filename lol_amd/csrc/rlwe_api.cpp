@@ -143,7 +143,7 @@ int lolhip_rlwe_sample_batch(const lolhip_plan* pq, void* stream, int kind, int6
   double* g = reinterpret_cast<double*>(e);
   if (launch_enc_gauss(s, g, B, n, k, ctr, CHACHA_DOM_RLWE_GAUSS, deviation(P, svar)) != hipSuccess) return LOLHIP_ERR_HIP;
   if (!two_power(P) &&
-      launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
+      launch_gauss(s, g, B, n, P.prog_gauss.d_stages, P.gauss_word, P.d_rconsts) != hipSuccess)
     return LOLHIP_ERR_HIP;
   return hip_status(launch_rlwe_cont_sample(s, x, g, static_cast<double*>(b_out), B * n, (double)P.qs[0]));
 }

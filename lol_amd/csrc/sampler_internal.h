@@ -57,7 +57,7 @@ inline int sample_error(const Plan& P, hipStream_t s, double* d, const int64_t* 
   if (two_power(P))
     return hip_status(launch_enc_error(s, nullptr, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma));
   if (launch_enc_gauss(s, d, B, P.n, key, ctr, domain, sigma) != hipSuccess) return LOLHIP_ERR_HIP;
-  if (launch_gauss(s, d, B, P.n, P.prog_gauss.d_stages, P.prog_gauss.nstages, P.d_rconsts) != hipSuccess)
+  if (launch_gauss(s, d, B, P.n, P.prog_gauss.d_stages, P.gauss_word, P.d_rconsts) != hipSuccess)
     return LOLHIP_ERR_HIP;
   return hip_status(launch_enc_error(s, d, rep, p, out, B, P.n, P.T, P.d_mod, mode, key, ctr, domain, sigma));
 }

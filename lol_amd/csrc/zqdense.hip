@@ -19,12 +19,12 @@
 // arithmetic.  Residues are canonical everywhere, so the result is the scalar interpreter's, bit for bit.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 
-#include "generic_dev.h"
+#include "kernel_dev.h"
 #include "kernels.h"
+#include "tile_dev.h"
 
 namespace lolhip {
 
@@ -32,16 +32,6 @@ namespace {
 
 constexpr int ZD_TPB = 256;
 constexpr size_t ZD_LDS_BUDGET = ZQ_LDS_BUDGET;
-
-__device__ __forceinline__ int fdiv40(int x, u64 M) { return (int)(((u64)(u32)x * M) >> 40); }   // x / v, M = floor(2^40/v)+1
-__device__ __forceinline__ u64 magic40_dev(int v) { return ((u64)1 << 40) / (u64)(v > 0 ? v : 1) + 1; }
-
-// LDS address of element 0 of column col: nq = n / d columns per item
-__device__ __forceinline__ int zq_col_base(const Stage& st, int col, int n, int nq, u64 m_nq) {
-  const int item = fdiv40(col, m_nq), q = col - item * nq;
-  const int blk = fdiv40(q, st.m_rts), r = q - blk * st.rts;
-  return item * n + blk * st.d * st.rts + r;
-}
 
 template <typename Wd> constexpr int zd_j() { return sizeof(Wd) == 4 ? 8 : 4; }
 
@@ -87,18 +77,9 @@ __device__ __forceinline__ void zq_dots(int d, int fold, const ModCtx& mc, Mat m
   }
 }
 
-// the stage's diagonal on output element x of the tile (x = item * n + index in the polynomial), then the store
-template <typename Wd>
-__device__ __forceinline__ void zq_put(const Stage& st, Wd* __restrict__ dst, int x, u64 v, int n, u64 m_n,
-                                       const u64* __restrict__ cst, const ModCtx& mc) {
-  if (st.tw_off >= 0) {
-    const int xi = x - fdiv40(x, m_n) * n;
-    const int xd = fdiv40(xi, st.m_twdiv);
-    v = gmul<sizeof(Wd) == 4>(v, cst[st.tw_off + xd - fdiv40(xd, st.m_twmod) * st.tw_mod], mc);
-  }
-  dst[x] = (Wd)v;
-}
-
+// The two layouts of tile_dense_rows / tile_dense_cols (tile_dev.h), written out over Z_q with tile_col_base: in this form
+// the products' inner loop keeps one of its J column addresses in a register; through the skeleton every one of them is
+// recomputed per term.
 template <typename Wd>
 __device__ __forceinline__ void zq_dense_rows(const Stage& st, const Wd* __restrict__ src, Wd* __restrict__ dst, int n,
                                               int items, const u64* __restrict__ Mt, const u64* __restrict__ cst,
@@ -112,7 +93,7 @@ __device__ __forceinline__ void zq_dense_rows(const Stage& st, const Wd* __restr
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       const int col = cg * J + j;
-      base[j] = zq_col_base(st, col < ncols ? col : ncols - 1, n, nq, m_nq);      // a dead column re-reads the last live one
+      base[j] = tile_col_base(st, col < ncols ? col : ncols - 1, n, nq, m_nq);      // a dead column re-reads the last live one
     }
     u64 out[J];
     zq_dots<Wd, J>(d, fold, mc, [&](int c, int) { return Mt[c * d + row]; },
@@ -136,7 +117,7 @@ __device__ __forceinline__ void zq_dense_cols(const Stage& st, const Wd* __restr
   for (int wi = wave; wi < nrg * nchunks; wi += nwaves) {
     const int rg = wi / nchunks, chunk = wi - rg * nchunks, row0 = rg * J;
     const int col = chunk * 64 + lane;
-    const int base = zq_col_base(st, col < ncols ? col : ncols - 1, n, nq, m_nq);
+    const int base = tile_col_base(st, col < ncols ? col : ncols - 1, n, nq, m_nq);
     int moff[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) moff[j] = (row0 + j < d ? row0 + j : d - 1) * d;   // a dead row re-reads the last live one
@@ -179,7 +160,7 @@ __device__ __forceinline__ void zq_dense_mfma(const Stage& st, const u32* __rest
     const int ct = wi / nrt, rt = wi - ct * nrt;
     const int col = ct * 32 + r32;
     const bool cok = col < ncols;
-    const int base = zq_col_base(st, cok ? col : ncols - 1, n, nq, m_nq);
+    const int base = tile_col_base(st, cok ? col : ncols - 1, n, nq, m_nq);
     v16i acc[NA];
 #pragma unroll
     for (int s = 0; s < NA; ++s)
@@ -317,26 +298,10 @@ k_zq_dense(const ZqArgs a) {
   }
 }
 
-// more than 64 KiB of dynamic LDS: the attribute, once per device and kernel
-template <typename K>
-hipError_t allow_big_lds(K kernel, std::atomic<unsigned long long>& done) {
-  int dev = -1;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!(done.load(std::memory_order_acquire) >> dev & 1)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ZD_LDS_BUDGET);
-    if (e != hipSuccess) return e;
-    done.fetch_or(1ull << dev, std::memory_order_release);
-  }
-  return hipSuccess;
-}
-
 template <typename Wd, int MW>
 hipError_t launch_zq_kernel(const ZqArgs& a, i64 grid, size_t lds, hipStream_t stream) {
   if (lds > 64 * 1024) {
-    static std::atomic<unsigned long long> done{0};
-    const hipError_t e = allow_big_lds(&k_zq_dense<Wd, MW>, done);
+    const hipError_t e = allow_big_lds<&k_zq_dense<Wd, MW>>((int)ZD_LDS_BUDGET);
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL((k_zq_dense<Wd, MW>), dim3((unsigned)grid), dim3(ZD_TPB), lds, stream, a);
@@ -371,12 +336,7 @@ hipError_t launch_zq_dense(const GenericLaunch& g) {
     const i64 big = (i64)(ZD_LDS_BUDGET / per), full = (32 + (pm ? 2 : 1) * (g.n / z.dmax) - 1) / ((pm ? 2 : 1) * (g.n / z.dmax));
     cap = big < full ? big : full;
   }
-  i64 want = (g.B + 511) / 512;
-  want = (want + J - 1) / J * J;
-  i64 items = want < cap ? want : cap;
-  if (items > J) items = items / J * J;
-  if (items > g.B) items = g.B;
-  if (items < 1) items = 1;
+  const i64 items = tile_items(g.B, cap, J);
   const size_t lds = per * (size_t)items;
   const i64 ntiles = (g.B + items - 1) / items;
   i64 grid = ntiles * g.T;
@@ -387,12 +347,12 @@ hipError_t launch_zq_dense(const GenericLaunch& g) {
   }
   if (getenv("LOLHIP_ZQ_DENSE_INFO")) {
     char line[512];
-    int at = snprintf(line, sizeof(line), "k_zq_dense: route %d, W %d, n %lld, B %lld, T %d, word %zu, items %lld, lds %zu B, grid %lld, polymul %d, stages",
-                      z.route, mfma ? z.W : 0, (long long)g.n, (long long)g.B, g.T, word, (long long)items, lds, (long long)grid, pm ? 1 : 0);
+    const int at = snprintf(line, sizeof(line), "k_zq_dense: route %d, W %d, n %lld, B %lld, T %d, word %zu, items %lld, lds %zu B, grid %lld, polymul %d, stages",
+                            z.route, mfma ? z.W : 0, (long long)g.n, (long long)g.B, g.T, word, (long long)items, lds, (long long)grid, pm ? 1 : 0);
     static const char* const names[3] = {"elt", "dense-rows", "dense-cols"};
-    for (int i = 0; i < nst && at > 0 && at < (int)sizeof(line); ++i)          // the poly-mul: "*" before the inverse program
-      at += snprintf(line + at, sizeof(line) - (size_t)at, "%s %s", pm && i == g.nstages ? " *" : "", names[z.kind[i] < 3 ? z.kind[i] : 0]);
-    fprintf(stderr, "%s\n", line);
+    tile_info(line, at, nst, [&](char* p, size_t room, int i) {              // the poly-mul: "*" before the inverse program
+      return snprintf(p, room, "%s %s", pm && i == g.nstages ? " *" : "", names[z.kind[i] < 3 ? z.kind[i] : 0]);
+    });
   }
   ZqArgs a;
   a.y = g.y; a.src = z.src ? z.src : g.y; a.B = g.B; a.ntiles = ntiles;

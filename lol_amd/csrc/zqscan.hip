@@ -26,8 +26,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "generic_dev.h"
 #include "kernels.h"
+#include "tile_dev.h"
 
 namespace lolhip {
 
@@ -36,9 +36,6 @@ namespace {
 constexpr int ZS_MAX_TPB = 512;          // two workgroups of a 64 KiB tile per CU, at the kernel's 4 waves per SIMD
 constexpr size_t ZS_TILE_BYTES = 64 * 1024;       // two workgroups per CU; within ZQ_LDS_BUDGET
 static_assert(ZS_TILE_BYTES <= ZQ_LDS_BUDGET, "the tile must fit the dynamic LDS of a workgroup");
-
-__device__ __forceinline__ int fdiv40(int x, u64 M) { return (int)(((u64)(u32)x * M) >> 40); }   // x / v, M = floor(2^40/v)+1
-__device__ __forceinline__ u64 magic40_dev(int v) { return ((u64)1 << 40) / (u64)(v > 0 ? v : 1) + 1; }
 
 // what the stage stores at element i of a vector: v the input there, prev the input one step below (unused at i = 0),
 // P the inclusive prefix sum, S the total, W the weighted total, last the input at d - 1: stage_eval's expressions
@@ -69,18 +66,6 @@ template <bool Q32> __device__ __forceinline__ u64 zs_wfin(u64 acc, const ModCtx
   if constexpr (Q32) return rem128(0, acc, mc); else return acc;
 }
 
-// the stage's diagonal on element x of the tile (x = item * n + index in the polynomial), then the store
-template <typename Wd>
-__device__ __forceinline__ void zs_put(const Stage& st, Wd* __restrict__ buf, int x, u64 v, int n, u64 m_n,
-                                       const u64* __restrict__ cst, const ModCtx& mc) {
-  if (st.tw_off >= 0) {
-    const int xi = x - fdiv40(x, m_n) * n;
-    const int xd = fdiv40(xi, st.m_twdiv);
-    v = gmul<sizeof(Wd) == 4>(v, cst[st.tw_off + xd - fdiv40(xd, st.m_twmod) * st.tw_mod], mc);
-  }
-  buf[x] = (Wd)v;
-}
-
 template <typename Wd>
 __device__ __forceinline__ void zs_cols(const Stage& st, Wd* __restrict__ buf, int n, int items, const u64* __restrict__ cst,
                                         const ModCtx& mc) {
@@ -107,7 +92,7 @@ __device__ __forceinline__ void zs_cols(const Stage& st, Wd* __restrict__ buf, i
     for (int i = 0; i < d; ++i) {
       const u64 v = buf[base + i * rts];
       P = addmod(P, v, q);
-      zs_put(st, buf, base + i * rts, zs_out<Q32>(kind, p, i, v, prev, P, S, W, last, mc), n, m_n, cst, mc);
+      zq_put(st, buf, base + i * rts, zs_out<Q32>(kind, p, i, v, prev, P, S, W, last, mc), n, m_n, cst, mc);
       prev = v;
     }
   }
@@ -215,7 +200,7 @@ __device__ __forceinline__ void zs_lanes(const Stage& st, Wd* __restrict__ buf, 
 #pragma unroll
       for (int u = 0; u < U; ++u)
         if (ok[u] && i < d)
-          zs_put(st, buf, base[u] + k * seg, zs_out<Q32>(kind, p, i, v[u], prev[u], P[u], S[u], W[u], last[u], mc), n, m_n, cst, mc);
+          zq_put(st, buf, base[u] + k * seg, zs_out<Q32>(kind, p, i, v[u], prev[u], P[u], S[u], W[u], last[u], mc), n, m_n, cst, mc);
       if (k + 1 < rounds) {
 #pragma unroll
         for (int u = 0; u < U; ++u) { carry[u] = zs_from<Wd>(P[u], top); pv[u] = zs_from<Wd>(v[u], top); }
@@ -307,19 +292,14 @@ hipError_t launch_zq_scan(const GenericLaunch& g) {
       continue;
     }
     if (!zq_scan_stage(st) || st.d < 1 || st.rts < 1 || g.n % ((i64)st.d * st.rts) != 0) return hipErrorInvalidValue;
-    if ((z.kind[i] == ZS_LANES) != (st.rts < 64) || z.kind[i] > ZS_COLS) return hipErrorInvalidValue;
+    if ((z.kind[i] == ZS_COLS) != lanes_along_r(st) || z.kind[i] > ZS_COLS) return hipErrorInvalidValue;
   }
   const size_t word = g.q32 ? 4 : 8;
   // The tile: as many items as 64 KiB of LDS hold (two workgroups per CU), but no more than leave about 512 tiles to the
   // batch, and no fewer than make 1024 words (four for each of a workgroup's 256 threads); n = 8192 at 8-byte words is
   // one item of exactly 64 KiB.
   const size_t per = (size_t)g.n * word;
-  const i64 cap = (i64)(ZS_TILE_BYTES / per);
-  i64 want = (g.B + 511) / 512;
-  if (want < (1024 + g.n - 1) / g.n) want = (1024 + g.n - 1) / g.n;
-  i64 items = want < cap ? want : cap;
-  if (items > g.B) items = g.B;
-  if (items < 1) items = 1;
+  const i64 items = tile_items(g.B, (i64)(ZS_TILE_BYTES / per), 1, (1024 + g.n - 1) / g.n);
   const size_t lds = per * (size_t)items;
   // a workgroup whose tile fills its share of a CU's LDS should also fill its share of the SIMDs
   const int threads = items * g.n >= 4096 ? ZS_MAX_TPB : 256;
@@ -332,14 +312,13 @@ hipError_t launch_zq_scan(const GenericLaunch& g) {
   }
   if (getenv("LOLHIP_ZQ_SCAN_INFO")) {
     char line[1024];
-    int at = snprintf(line, sizeof(line), "k_zq_scan: n %lld, B %lld, T %d, word %zu, items %lld, lds %zu B, grid %lld, threads %d, stages",
-                      (long long)g.n, (long long)g.B, g.T, word, (long long)items, lds, (long long)grid, threads);
+    const int at = snprintf(line, sizeof(line), "k_zq_scan: n %lld, B %lld, T %d, word %zu, items %lld, lds %zu B, grid %lld, threads %d, stages",
+                            (long long)g.n, (long long)g.B, g.T, word, (long long)items, lds, (long long)grid, threads);
     static const char* const layouts[3] = {"elt", "lanes", "cols"};
-    for (int i = 0; i < g.nstages && at > 0 && at < (int)sizeof(line); ++i) {
+    tile_info(line, at, g.nstages, [&](char* p, size_t room, int i) {
       const Stage& st = z.host_stages[i];
-      at += snprintf(line + at, sizeof(line) - (size_t)at, " %s:%d:%d:%d:%s", zs_kind_name(st.kind), st.p, st.d, st.rts, layouts[z.kind[i]]);
-    }
-    fprintf(stderr, "%s\n", line);
+      return snprintf(p, room, " %s:%d:%d:%d:%s", zs_kind_name(st.kind), st.p, st.d, st.rts, layouts[z.kind[i]]);
+    });
   }
   ZsArgs a;
   a.y = g.y; a.src = z.src ? z.src : g.y; a.B = g.B; a.ntiles = ntiles;
